@@ -12,8 +12,8 @@ i.e. the warm-up transitions WITH their adaptation and the post-warm-up draws.  
 transitions of all chains, the first half of the K steps adapting, the second half drawing, so the driver's K = 20
 is exactly the 1 000 + 1 000 run.  Untimed, as §8d says ("excluding setup and H2D of the initial state"): engine
 creation, θ0 upload, find_good_stepsize.  W warm-up steps (same loop, throw-away engine) run first; then the timed
-region — exactly K steps — bracketed by barrier + synchronize, MAX over ranks, repeated `--repeats` times (default:
-until >= 1 s of timed work and at least 3 runs when they are short), the MEDIAN run is reported (all runs listed).
+region — exactly K steps — bracketed by barrier + synchronize, MAX over ranks, run once (`--full`: repeated `--repeats` times,
+default until >= 1 s of timed work and at least 3 runs when they are short), the MEDIAN run is reported (all runs listed).
 `value` = Σ n_steps over all chains, ranks and both phases of that run ÷ its wall time.  The post-adaptation rate (the
 round-1 headline) and the warm-up rate are sub-fields of `config`.
 
@@ -34,8 +34,14 @@ kernel sources they were taken on: if the digest does not match the library in u
 
 Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL).  `--gpus N` without a torchrun environment
 re-executes itself under `python -m torch.distributed.run --nproc-per-node N`.  Chains shard with no data-path
-collective (weak scaling, Philox chain offset = rank·chains); the only collectives are the timing reductions and the
-final gather of per-dimension moments, which goes through the C ABI (ahmc_gather_moments over RCCL).
+collective (weak scaling, Philox chain offset = rank·chains); the only collectives are the timing reductions and (`--full`)
+the final gather of per-dimension moments, which goes through the C ABI (ahmc_gather_moments over RCCL).
+
+Plain run vs `--full`: a plain `bench.py --steps K --warmup W` does what the headline needs and nothing else — setup, W
+warm-up steps, ONE timed run of exactly K steps, the roofline from that run's own launch timings, the line.  `--full` adds
+what else the benchmark measures: repeated timed runs (median reported), the ESS of the draws, the final gather of the
+moments, the CPU baseline, the other single-GPU configs as `config.secondary` (default invocation) and `bench_detail.json`.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -212,6 +218,71 @@ def cpu_baseline(A, cfg, n_adapts, n_draws, seed, chains, threads):
     return (r["leap_adapt"] + r["leap_draw"]) / r["dt"], r["leap_draw"] / max(r["dt_draw"], 1e-9), r["dt"], threads
 
 
+DUMP_BUDGET = 64 * 2**20     # bytes of all --dump-outputs files together
+DUMP_DRAWS_BUDGET = 36 * 2**20
+DUMP_STATS_BUDGET = 16 * 2**20
+DUMP_METRIC_BUDGET = 8 * 2**20
+DUMP_SEED = 0x5EEDD0
+
+
+def _chain_sample(N, k):
+    """a fixed, seeded sample of k of the N chains (sorted; all of them when k >= N)"""
+    if k >= N:
+        return np.arange(N)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=k, replace=False))
+
+
+def dump_outputs(out_dir, eng, draws, n_draws, T, dtype):
+    """--dump-outputs: what a caller of the timed path receives from its LAST step, as float32 / float64 .npy files (<= DUMP_BUDGET):
+      draws_last_step.npy  (t, n, D)  θ after each of the last t = min(T, n_draws) post-warm-up transitions (the draws buffer the
+                                      timed region filled), for a seeded sample of n <= 256 chains (draws_chains.npy)
+      theta_final.npy      (D, n)     θ after the last transition, same chains (only with --no-draws-out: no draws buffer)
+      stat_<field>.npy     (m,)       the per-chain statistics of the last transition (Engine.stats) for every chain, or a seeded
+                                      sample of them when N is large (stat_chains.npy)
+      stepsize.npy         (m,)       the adapted step size of the same chains
+      metric.npy           (D, n) | (D, D)   the adapted M⁻¹: the sampled chains' diagonals / the shared dense matrix
+    Chain indices are stored as float64.  Rank 0's chains only."""
+    import ahmc_amd as A
+
+    os.makedirs(out_dir, exist_ok=True)
+    D, N, isz = eng.D, eng.N, np.dtype(dtype).itemsize
+    files = {}
+    if draws is not None:
+        t = max(1, min(T, n_draws, DUMP_DRAWS_BUDGET // (D * isz)))
+        pick = _chain_sample(N, max(1, min(256, DUMP_DRAWS_BUDGET // (t * D * isz))))
+        import torch
+
+        idx = torch.as_tensor(pick, device=draws.device)
+        files["draws_last_step"] = draws[n_draws - t:n_draws].index_select(1, idx).cpu().numpy()
+    else:
+        pick = _chain_sample(N, max(1, min(256, DUMP_DRAWS_BUDGET // (D * isz))))
+        files["theta_final"] = np.ascontiguousarray(eng.theta().reshape(D, N)[:, pick])
+    files["draws_chains"] = pick.astype(np.float64)
+    st = eng.stats()
+    spick = _chain_sample(N, max(1, DUMP_STATS_BUDGET // ((len(st) + 2) * 8)))
+    for name, v in st.items():
+        v = np.asarray(v)[spick]
+        files[f"stat_{name}"] = v.astype(np.float64) if v.dtype.kind in "biu" else v
+    files["stat_chains"] = spick.astype(np.float64)
+    files["stepsize"] = np.asarray(eng.get_stepsize())[spick]
+    m = eng.get_metric()
+    if m is not None:
+        if eng.metric_kind == A.capi.METRIC_DIAG and m.shape == (D, N):
+            m = m[:, pick]
+        elif m.nbytes > DUMP_METRIC_BUDGET:   # a dense M⁻¹ too large for the budget: a seeded sample of its columns
+            cols = _chain_sample(m.shape[1], max(1, DUMP_METRIC_BUDGET // (m.shape[0] * isz) - 1))
+            m = m[:, cols]
+            files["metric_columns"] = cols.astype(np.float64)
+        files["metric"] = np.ascontiguousarray(m)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f"--dump-outputs: {total} bytes over the {DUMP_BUDGET}-byte budget")
+    for name, a in files.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(files)
+
+
 def respawn_under_torchrun(n):
     """`bench.py --gpus N` outside a torchrun environment: become the launcher (one rank per GPU)"""
     s = socket.socket()
@@ -248,10 +319,11 @@ class SetupFailed(RuntimeError):
     """a config's setup failed on some rank and ALL ranks know (they agreed before the first collective of its timed loop)"""
 
 
-def run_config(ctx, cfg_name, steps, T, warm_trans, repeats, cpu_budget_s, dim=0, chains=0):
+def run_config(ctx, cfg_name, steps, T, warm_trans, repeats, cpu_budget_s, dim=0, chains=0, dump_dir=None):
     """One bench line for one config: W untimed transitions on a throw-away engine, then the timed sample loop (median of
-    `repeats` runs on fresh engines), the final gather, the roofline of the dominant kernel and — rank 0 of a one-GPU run — the CPU
-    baseline on a bounded sample of the same loop.  Returns the JSON object on rank 0, None elsewhere."""
+    `repeats` runs on fresh engines), the roofline of the dominant kernel, with `--full` the final gather and — rank 0 of a one-GPU
+    run — the CPU baseline on a bounded sample of the same loop; `dump_dir`: the last run's outputs (dump_outputs).  Returns the
+    JSON object on rank 0, None elsewhere."""
     A, lib, torch, dist, args = ctx["A"], ctx["lib"], ctx["torch"], ctx["dist"], ctx["args"]
     rank, local_rank, world, stream = ctx["rank"], ctx["local_rank"], ctx["world"], ctx["stream"]
     cfg = dict(CONFIGS[cfg_name])
@@ -316,7 +388,8 @@ def run_config(ctx, cfg_name, steps, T, warm_trans, repeats, cpu_budget_s, dim=0
         sample_loop(eng, kernel, nwa, nwd, barrier_for(eng), draws_ptr=draws.data_ptr() if (draws is not None and nwd <= n_draws) else None)
         eng.close()
 
-    want_ess = draws is not None and args.ess != 0 and n_draws >= 8   # every config: one thread per (dimension, chain) series, any D
+    # every config: one thread per (dimension, chain) series, any D; on by default with --full only
+    want_ess = draws is not None and (args.ess > 0 or (args.ess < 0 and args.full)) and n_draws >= 8
     ess_buf = torch.empty((N, D), dtype=tdt, device=dev) if want_ess else None
 
     runs = []
@@ -355,13 +428,17 @@ def run_config(ctx, cfg_name, steps, T, warm_trans, repeats, cpu_budget_s, dim=0
     order = sorted(range(len(runs)), key=lambda i: runs[i]["value"])
     med = runs[order[len(order) // 2]]   # median run (the engine of the LAST run is still open for the gather)
 
-    # final gather of the pooled per-dimension moments of the last run's draws through the C ABI (RCCL all-reduce inside)
-    from ahmc_amd.shard import EngineComm
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, eng, draws, n_draws, T, np_dtype)
 
-    comm = EngineComm(eng, dist, dev)
-    g = comm.gather_moments()
-    ci = eng.comm_info()               # what the communicator's own all-reduces counted when it was attached
-    mean, var = g["mean"], g["var"]
+    comm = g = ci = None
+    if args.full:
+        # final gather of the pooled per-dimension moments of the last run's draws through the C ABI (RCCL all-reduce inside)
+        from ahmc_amd.shard import EngineComm
+
+        comm = EngineComm(eng, dist, dev)
+        g = comm.gather_moments()
+        ci = eng.comm_info()               # what the communicator's own all-reduces counted when it was attached
 
     ess_info = None
     if want_ess:
@@ -471,7 +548,6 @@ def run_config(ctx, cfg_name, steps, T, warm_trans, repeats, cpu_budget_s, dim=0
                 "workload": f"{cfg['text']}, {N} chains/GPU, D={D}; timed = the whole sample loop: {n_adapts} adapting transitions + {n_draws} draws "
                             f"(find_good_stepsize and the initial H2D are setup, untimed)",
                 "chains_per_gpu": N, "D": D, "parallelism": f"chain-shard x{world}",
-                "ranks_seen": ci["ranks_seen"], "chains_total_seen": ci["chains_total"],
                 "transitions_per_step": T, "n_adapts": n_adapts, "n_draws": n_draws,
                 "untimed_warmup_transitions": warm_trans,
                 "leapfrogs": {"adapt": med["leap_adapt_all"], "draw": med["leap_draw_all"]},
@@ -486,15 +562,18 @@ def run_config(ctx, cfg_name, steps, T, warm_trans, repeats, cpu_budget_s, dim=0
                                     "ms_per_transition": med["dt_draw_max"] / n_draws * 1e3,
                                     "mean_leapfrogs_per_transition": med["leap_draw_all"] / (n_draws * N * world),
                                     "divergent": med["div_all"]},
-                "max_abs_mean": float(np.abs(mean).max()), "max_abs_var_minus_1": float(np.abs(var - 1).max()) if cfg["target"] == "iso" else None,
-                "gathered_draws": g["n_draws"], "gather": g["how"],
                 "draws_materialised_in_timed_region": (None if args.no_draws_out else
                                                        {"shape_D_N_K": [D, N, n_draws], "gib": D * N * n_draws * itemsize / 2**30, "where": "device (HBM)"}),
                 "ess": ess_info,
             },
             "roofline": roof,
         }
-        if not args.no_cpu_baseline and world == 1 and cpu_budget_s > 0:  # (the contract: rank 0 at N = 1 only)
+        if g is not None:
+            out["config"].update({"ranks_seen": ci["ranks_seen"], "chains_total_seen": ci["chains_total"],
+                                  "max_abs_mean": float(np.abs(g["mean"]).max()),
+                                  "max_abs_var_minus_1": float(np.abs(g["var"] - 1).max()) if cfg["target"] == "iso" else None,
+                                  "gathered_draws": g["n_draws"], "gather": g["how"]})
+        if args.full and not args.no_cpu_baseline and world == 1 and cpu_budget_s > 0:  # (the contract: rank 0 at N = 1 only)
             try:
                 cores = usable_cores()
                 cpu_chains = args.cpu_chains or min(N, 256 * cores)
@@ -529,7 +608,8 @@ def run_config(ctx, cfg_name, steps, T, warm_trans, repeats, cpu_budget_s, dim=0
                     out["cpu_baseline"]["single_thread"] = {"value": v1, "cores": 1, "sample": f"{c1} chains, {t1n} transitions of the same loop, {cdt1:.1f} s"}
             except Exception as ex:  # the baseline leg must never take the GPU number down with it
                 out["cpu_baseline"] = {"value": None, "error": repr(ex)}
-    comm.close()
+    if comm is not None:
+        comm.close()
     eng.close()
     return out
 
@@ -669,24 +749,34 @@ def main():
     ap.add_argument("--warmup", type=int, default=2, help="W untimed steps of the same loop on a throw-away engine")
     ap.add_argument("--transitions-per-step", type=int, default=100)
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None, help="default: cfg2 (the headline) with the other one-GPU configs as config.secondary")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only")
+    ap.add_argument("--no-secondary", action="store_true", help="headline only (with --full)")
+    ap.add_argument("--full", action="store_true", help="also what the headline does not need: repeated timed runs, ESS, the final gather "
+                    "of the moments, the CPU baseline, the other one-GPU configs as config.secondary (default invocation), bench_detail.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path computed in its "
+                    "last step (a seeded sample of the last step's draws, the last transition's per-chain statistics, the adapted step sizes "
+                    "and metric) as DIR/<name>.npy, float32 / float64, <= 64 MiB in all; rank 0's chains")
     ap.add_argument("--chains", type=int, default=0, help="chains per GPU (0 = the config's)")
     ap.add_argument("--dim", type=int, default=0, help="D (0 = the config's)")
     ap.add_argument("--adapt-fraction", type=float, default=0.5, help="share of the K steps that adapt (SURVEY 8d: 1000 of 2000)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed runs (0 = until >= 1 s of timed work, at least 3 when a run is < 4 s)")
+    ap.add_argument("--repeats", type=int, default=-1, help="timed runs (0 = until >= 1 s of timed work, at least 3 when a run is < 4 s; "
+                    "default: 1, with --full 0)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--cpu-chains", type=int, default=0, help="0 = 256 per usable host core, capped at --chains")
     ap.add_argument("--cpu-transitions", type=int, default=0, help="transitions of the CPU sample (0 = sized for ~12 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(the CPU baseline runs with --full only)")
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64", help="f64 = the reference default and the headline; f32 = what the "
                     "reference's CUDA smoke test uses (test/CUDA/cuda.jl:18), reported for information")
     ap.add_argument("--ess", type=int, default=-1, help="ESS of the TIMED run's draws (every chain, every dimension; device reduction through ahmc_ess): "
-                    "0 = off, anything else = on (every config; outside the timed region)")
+                    "0 = off, 1 = on, -1 (default) = on with --full (every config; outside the timed region)")
     ap.add_argument("--no-draws-out", action="store_true", help="do not materialise the draws in the timed region (A/B of its cost; the reported line always does)")
-    ap.add_argument("--detail", default="bench_detail.json", help="file (relative to the repository) that receives the FULL record; the printed line "
-                    "is its compact form (<= 6 000 characters).  '' = none")
+    ap.add_argument("--detail", default=None, help="file (relative to the repository) that receives the FULL record; the printed line "
+                    "is its compact form (<= 6 000 characters).  '' = none; default: bench_detail.json with --full, none otherwise")
     ap.add_argument("--launch-check", action="store_true", help="spawn/rendezvous check only (gloo, no GPU, no compute)")
     args = ap.parse_args()
+    if args.detail is None:
+        args.detail = "bench_detail.json" if args.full else ""
+    if args.repeats < 0:
+        args.repeats = 0 if args.full else 1
 
     if args.gpus > 1 and "RANK" not in os.environ:
         respawn_under_torchrun(args.gpus)  # does not return
@@ -717,10 +807,10 @@ def main():
            "stream": torch.cuda.Stream(device=local_rank)}
     headline = args.config or "cfg2"
     T = args.transitions_per_step
-    out = run_config(ctx, headline, args.steps, T, args.warmup * T, args.repeats, 12.0, dim=args.dim, chains=args.chains)
+    out = run_config(ctx, headline, args.steps, T, args.warmup * T, args.repeats, 12.0, dim=args.dim, chains=args.chains, dump_dir=args.dump_outputs)
     # The other BASELINE configs a single GPU holds, each with its own value / roofline / cpu_baseline, beside the headline — in
-    # the default invocation only (what the driver runs).  At N > 1: the configs BASELINE.json quotes on exactly N GPUs.
-    if args.config is None and not args.no_secondary and not args.dim and args.dtype == "f64":
+    # the default invocation with --full only.  At N > 1: the configs BASELINE.json quotes on exactly N GPUs.
+    if args.full and args.config is None and not args.no_secondary and not args.dim and args.dtype == "f64":
         sec = {}
         ctx["single_thread_leg"] = False
         for name, (st, t2, wt, rp, cpu_s) in SECONDARY.items():

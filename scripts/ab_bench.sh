@@ -5,7 +5,7 @@ for spec in "$@"; do
   name=${spec%%:*}; envs=""; [ "$spec" != "$name" ] && envs=$(echo ${spec#*:} | tr ',' ' ')
   lib=""; base=${name%%@*}
   [ "$base" != "base" ] && lib="AHMC_HIP_LIB=$PWD/advancedhmc.jl_amd/csrc/variants/libahmc_hip_$base.so"
-  env $lib $envs timeout 300 python bench.py --no-cpu-baseline --no-secondary --ess 0 --repeats ${AB_REPEATS:-1} --detail $PWD/$O/$name.json ${AB_ARGS:-} > $O/$name.line 2> $O/$name.err
+  env $lib $envs timeout 300 python bench.py --full --no-cpu-baseline --no-secondary --ess 0 --repeats ${AB_REPEATS:-1} --detail $PWD/$O/$name.json ${AB_ARGS:-} > $O/$name.line 2> $O/$name.err
   python - "$O/$name.json" "$name" <<'PY'
 import json, sys
 try:

@@ -75,7 +75,7 @@ def _check_headline(d, steps, warmup, chains, n_adapts, n_draws):
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", ["cfg2", "cfg3"])
 def test_bench_json_contract(config, tmp_path):
-    d, full = _run_bench(["--config", config, "--steps", "4", "--warmup", "1", "--transitions-per-step", "20", "--chains", "4096",
+    d, full = _run_bench(["--full", "--config", config, "--steps", "4", "--warmup", "1", "--transitions-per-step", "20", "--chains", "4096",
                           "--cpu-chains", "64", "--cpu-transitions", "24", "--repeats", "2"], tmp_path)
     _check_headline(d, 4, 1, 4096, 40, 40)
     assert len(d["config"]["runs"]) == 2 and d["cpu_baseline"]["single_thread_value"] > 0
@@ -88,10 +88,10 @@ def test_bench_json_contract(config, tmp_path):
 
 @pytest.mark.gpu
 def test_bench_default_invocation_line(tmp_path):
-    """What the driver runs — `python bench.py` with no --config — on reduced chains: ONE line under 6 000 characters that carries the
+    """`python bench.py --full` with no --config, on reduced chains: ONE line under 6 000 characters that carries the
     headline AND config.secondary.{cfg3, cfg5, cfg4}, each with value / ms_per_step / steps / workload / dtype / roofline / cpu_baseline.
     (Round 4: this invocation was never tested, its line grew to 31.9 KB and the driver's 8 KB capture lost the headline.)"""
-    d, full = _run_bench(["--steps", "4", "--warmup", "1", "--transitions-per-step", "20", "--chains", "2048", "--cpu-chains", "64",
+    d, full = _run_bench(["--full", "--steps", "4", "--warmup", "1", "--transitions-per-step", "20", "--chains", "2048", "--cpu-chains", "64",
                           "--cpu-transitions", "24", "--repeats", "1"], tmp_path, timeout=1500)
     _check_headline(d, 4, 1, 2048, 40, 40)
     sec = d["config"]["secondary"]
@@ -108,6 +108,89 @@ def test_bench_default_invocation_line(tmp_path):
         assert o["ess_per_sec"] is not None and o["ess_per_sec"] > 0     # the second half of BASELINE's metric, every config
         assert full["config"]["secondary"][name]["value"] == pytest.approx(o["value"], rel=1e-5)
     assert sec["cfg4"]["roofline"]["achieved"] > 0
+
+
+def _dump_once(bench, A, lib, out_dir):
+    import numpy as np
+    import torch
+
+    cfg = dict(bench.CONFIGS["cfg2"], D=8)
+    N, n_adapts, n_draws, T = 96, 10, 12, 5
+    eng, kernel = bench.build_engine(A, lib, cfg, N, cfg["seed"], 0)
+    draws = torch.empty((n_draws, N, cfg["D"]), dtype=torch.float64)
+    bench.sample_loop(eng, kernel, n_adapts, n_draws, eng.sync, draws_ptr=draws.data_ptr())
+    names = bench.dump_outputs(str(out_dir), eng, draws, n_draws, T, np.float64)
+    theta = eng.theta()
+    eng.close()
+    return names, theta
+
+
+def test_dump_outputs_on_the_cpu_checker(oracle, tmp_path):
+    """--dump-outputs' writer on the CPU checker (same C ABI as the HIP engine): float32 / float64 files only, under the budget, the
+    last step's draws of the sampled chains end in their final θ, and the same arguments write the same arrays twice"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import importlib
+
+    import ahmc_amd as A
+
+    bench = importlib.import_module("bench")
+    names, theta = _dump_once(bench, A, oracle, tmp_path / "a")
+    names2, _ = _dump_once(bench, A, oracle, tmp_path / "b")
+    assert names == names2
+    for k in ("draws_last_step", "draws_chains", "stat_n_steps", "stat_log_density", "stat_chains", "stepsize", "metric"):
+        assert k in names, k
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.testing.assert_array_equal(a, b, err_msg=name)
+        total += (tmp_path / "a" / f"{name}.npy").stat().st_size
+    assert total <= bench.DUMP_BUDGET
+    d = np.load(tmp_path / "a" / "draws_last_step.npy")
+    pick = np.load(tmp_path / "a" / "draws_chains.npy").astype(np.int64)
+    assert d.shape == (5, len(pick), 8)
+    np.testing.assert_array_equal(d[-1], theta[:, pick].T)
+    assert np.load(tmp_path / "a" / "metric.npy").shape == (8, len(pick))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full): ONE timed run of exactly --steps steps and the headline keys, none of what --full adds (CPU baseline,
+    ESS, secondary configs, side file); --dump-outputs writes float32 / float64 arrays under the budget, the same ones on a second run
+    with the same arguments"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import importlib
+
+    bench = importlib.import_module("bench")
+    lines = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--transitions-per-step", "20",
+               "--chains", "4096", "--dump-outputs", str(tmp_path / run)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines.append(json.loads(res.stdout.strip().splitlines()[-1]))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True and d["unit"] == "leapfrog-steps/s"
+    c = d["config"]
+    assert len(c["runs"]) == 1 and c["n_adapts"] == 40 and c["n_draws"] == 40
+    assert "cpu_baseline" not in d and "secondary" not in c and "ess_per_sec" not in c and "detail" not in c
+    total = (c["warmup_phase"]["mean_leapfrogs_per_transition"] * c["n_adapts"] + c["post_adaptation"]["mean_leapfrogs_per_transition"] * c["n_draws"]) * 4096
+    assert abs(d["ms_per_step"] * d["steps"] / 1e3 * d["value"] - total) < 1e-4 * total
+    names = sorted(f for f in os.listdir(tmp_path / "a") if f.endswith(".npy"))
+    assert names == sorted(f for f in os.listdir(tmp_path / "b") if f.endswith(".npy"))
+    assert "draws_last_step.npy" in names and "stat_n_steps.npy" in names
+    assert sum((tmp_path / "a" / f).stat().st_size for f in names) <= bench.DUMP_BUDGET
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64), (f, a.dtype)
+        np.testing.assert_array_equal(a, b, err_msg=f)
+    assert np.load(tmp_path / "a" / "draws_last_step.npy").shape[:1] == (20,)
 
 
 def _stub_full_record():
