@@ -541,6 +541,9 @@ class Engine:
     # -- configuration --
     def set_target(self, target):
         p = None if target.params is None else np.ascontiguousarray(target.params, dtype=self.dtype)
+        if isinstance(target, (PluginTarget, ObjectTarget)) and self.info("wide"):
+            # (refused before anything is compiled: a plugin is built for ONE fused geometry, and a wide context has none)
+            self._call("ahmc_set_target_plugin", b"", None, 0)
         if isinstance(target, PluginTarget):
             from .build import build_target_plugin
 
@@ -870,12 +873,18 @@ class Engine:
 
     INFO = {"group_lanes": 0, "elems_per_lane": 1, "nuts_launches": 2, "nuts_batch": 3, "iteration": 4, "nuts_kernel_ns": 5,
             "nuts_warm_launches": 6, "nuts_warm_kernel_ns": 7, "dense_gemm_launches": 8, "dense_gemm_small_launches": 9, "dense_pipelines": 10,
-            "dense_pool": 11, "nuts_draw_batch": 12, "dense_epoch_launches": 13, "stepsize_scalar": 14}
+            "dense_pool": 11, "nuts_draw_batch": 12, "dense_epoch_launches": 13, "stepsize_scalar": 14, "wide": 15}
+
+    # keys the CPU checker (oracle/) does not answer, and what they mean there: it has no thread geometry, so no wide mode either
+    CHECKER_ONLY_ZERO = ("wide",)
 
     def info(self, key):
-        """engine introspection (ahmc_get_info): thread geometry, NUTS launch count / batch, iteration"""
+        """engine introspection (ahmc_get_info): thread geometry, NUTS launch count / batch, iteration, wide context"""
         v = C.c_int64()
-        self._call("ahmc_get_info", self.INFO[key], C.byref(v))
+        code = self.lib.dll.ahmc_get_info(self._ctx, self.INFO[key], C.byref(v))
+        if code == capi.ERR_ARGUMENT and key in self.CHECKER_ONLY_ZERO and not self.lib.backend.startswith("hip"):
+            return 0
+        self.lib.check(code, self._ctx)
         return v.value
 
 

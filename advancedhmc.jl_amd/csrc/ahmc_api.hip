@@ -6,6 +6,7 @@
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
 #include "ahmc_dense_mn.hpp"
+#include "ahmc_wide.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: the entry points are resolved at run time (ahmc_multi_host.hpp)
@@ -94,6 +95,7 @@ template <class T>
 struct Ctx : CtxBase {
   int64_t D = 0, N = 0;
   int G = 0, E = 0;  // thread geometry chosen for D
+  bool wide = false;  // no fused geometry covers D (D > 4096, or AHMC_FORCE_WIDE=1): G = E = 0, the step-synchronous engine serves everything
   // phase point
   T *vbase = nullptr, *tbase = nullptr;  // slabs; the per-field pointers are aliases into them
   int32_t* ibase = nullptr;
@@ -366,6 +368,21 @@ const TargetOps<T>* ops_for(const Ctx<T>* c) {
   return nullptr;
 }
 
+// what a wide context refuses: the message names the dimension limit
+template <class T>
+std::string wide_refusal(const Ctx<T>* c, const std::string& what) {
+  return what + " is not implemented beyond the fused kernels' dimension limit D <= 4096 (this context: D = " + std::to_string(c->D) +
+         (c->D <= 4096 ? ", wide by AHMC_FORCE_WIDE=1)" : ")");
+}
+
+// the fused kernels (ops_for(c)->…, k_kinetic) exist for the compiled geometries only: a wide context has none
+template <class T>
+int fused_guard(Ctx<T>* c, const char* what) {
+  if (!c->wide && has_geometry(c->G, c->E)) return AHMC_OK;
+  return fail(c, AHMC_ERR_UNSUPPORTED, std::string(what) + ": no fused kernel for D = " + std::to_string(c->D) + " (a wide context: D > 4096 or AHMC_FORCE_WIDE=1, "
+                                       "served by the step-synchronous engine only)");
+}
+
 template <class T>
 int check_builtin(Ctx<T>* c, const char* what) {
   if (c->target_kind == AHMC_TARGET_PLUGIN && !c->plugin_ops) return fail(c, AHMC_ERR_STATE, std::string(what) + ": no target plugin is bound");
@@ -374,11 +391,13 @@ int check_builtin(Ctx<T>* c, const char* what) {
                                    "ahmc_ext_* (whole transitions, find_good_stepsize) or ahmc_lf_pre / ahmc_lf_post (single leapfrogs)");
   if (dense_engine(c))
     return fail(c, AHMC_ERR_UNSUPPORTED, std::string(what) + " is not implemented for DenseEuclideanMetric / AHMC_TARGET_DENSE_GAUSS");
-  return AHMC_OK;
+  return fused_guard(c, what);
 }
 
 template <class T>
 int launch_fill_caches_builtin(Ctx<T>* c) {
+  int rc = fused_guard(c, "fill_caches");
+  if (rc) return rc;
   KP<T> p = make_kp(c);
   p.no_lk = c->metric_kind == AHMC_METRIC_DENSE ? 1 : 0;  // ℓκ = −½ rᵀM⁻¹r comes from the dense engine
   if (const TargetOps<T>* o = ops_for(c)) o->fill_caches(c->G, c->E, group_grid(c), c->stream, p);
@@ -407,10 +426,11 @@ int launch_kinetic(Ctx<T>* c) {
     return rc ? rc : dn_velocity(c);
   }
   KP<T> p = make_kp(c);
-  with_geometry(c->G, c->E, [&](auto g, auto e) {
+  const bool launched = with_geometry(c->G, c->E, [&](auto g, auto e) {
     hipLaunchKernelGGL((k_kinetic<T, decltype(g)::value, decltype(e)::value>), dim3(group_grid(c)), dim3(decltype(g)::value > 64 ? decltype(g)::value : 256), 0,
                        c->stream, p);
   });
+  if (!launched) return fused_guard(c, "kinetic energy");
   HIPCHK(hipGetLastError());
   return AHMC_OK;
 }
@@ -425,6 +445,7 @@ int set_metric(Ctx<T>* c, int kind, const T* minv, int64_t n) {
     return AHMC_OK;
   }
   if (kind == AHMC_METRIC_DENSE) {
+    if (c->wide) return fail(c, AHMC_ERR_UNSUPPORTED, wide_refusal(c, "set_metric: DenseEuclideanMetric"));
     if (!minv) return fail(c, AHMC_ERR_ARGUMENT, "set_metric: M⁻¹ pointer is NULL");
     if (n != c->D * c->D) return fail(c, AHMC_ERR_ARGUMENT, "AxesMismatch: dense M⁻¹ must have D*D elements");
     return dn_set_metric(c, minv);
@@ -463,6 +484,7 @@ int plan_nuts(Ctx<T>* c, int max_depth, int criterion, int& blocks, int& wpb, si
   const size_t scalar_bytes = (size_t)(NUTS_NSC * NLEV + NUTS_NAT) * CPW * sizeof(T) + (size_t)(NUTS_NSI * NLEV + NUTS_NAI) * CPW * sizeof(int);
   const int64_t n_chunks = (c->N + CPW - 1) / CPW;
   int occ = 0;  // single-wave workgroups per CU
+  if (int rc = fused_guard(c, "k_nuts")) return rc;
   const TargetOps<T>* o = ops_for(c);
   if (!o) return fail(c, AHMC_ERR_STATE, "k_nuts: the context's target has no fused kernels");
   // the scratch sized here is indexed by kernels of another translation unit (or of a plugin): same layout constants, or no launch
@@ -896,6 +918,7 @@ template <class T>
 int compat_step_loop(Ctx<T>* c, int64_t n_abs, bool fwd, int64_t& done) {
   if (c->integ_kind == AHMC_INTEGRATOR_TEMPERED)
     return fail(c, AHMC_ERR_UNSUPPORTED, "ahmc_set_ref_compat: the coupled early exit is not implemented for TemperedLeapfrog (the step index of a launch of one step)");
+  if (int rc = fused_guard(c, "ahmc_set_ref_compat")) return rc;
   if (!c->compat_flag) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->compat_flag), sizeof(int)));
   const TargetOps<T>* o = ops_for(c);
   if (!o) return fail(c, AHMC_ERR_STATE, "ahmc_set_ref_compat: the context's target has no fused kernels");
@@ -919,6 +942,7 @@ int compat_step_loop(Ctx<T>* c, int64_t n_abs, bool fwd, int64_t& done) {
 // of the transition's integration (fresh momentum from the transition's own counter-based stream, one step at a time) on a copy of the state
 template <class T>
 int compat_hmc_stop_step(Ctx<T>* c, int64_t L, double refresh_alpha, int64_t& L_eff) {
+  if (int rc = fused_guard(c, "ahmc_set_ref_compat")) return rc;
   const size_t DN = (size_t)c->D * (size_t)c->N, nv = 3 * DN, ns = 14 * (size_t)c->N;
   if (!c->compat_save) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->compat_save), (nv + ns) * sizeof(T)));
   HIPCHK(hipMemcpyAsync(c->compat_save, c->vbase, nv * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
@@ -1329,8 +1353,13 @@ static int32_t create_impl(int32_t device, int32_t dtype, int64_t D, int64_t N, 
     delete c;
     return code;
   };
-  if (!pick_geometry(D, c->G, c->E))
-    return bail("ahmc_create: D > 4096 has no HIP kernel geometry", AHMC_ERR_UNSUPPORTED);
+  // wide: no fused geometry for D (or the experiment switch AHMC_FORCE_WIDE=1, read here, once per context): G = E = 0 and every
+  // call goes to the step-synchronous engine (dense_engine), which strides over a run-time D (ahmc_wide.hpp for the built-in families)
+  const char* fw = getenv("AHMC_FORCE_WIDE");
+  if ((fw && atoi(fw) != 0) || !pick_geometry(D, c->G, c->E)) {
+    c->wide = true;
+    c->G = c->E = 0;
+  }
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return bail(std::string("hipSetDevice: ") + hipGetErrorString(e), AHMC_ERR_RUNTIME);
   hipDeviceProp_t prop;
@@ -1429,6 +1458,7 @@ int32_t ahmc_set_target(ahmc_ctx* ctx, int32_t kind, const void* params, int64_t
     }
     if (kind == AHMC_TARGET_FUNNEL && c->D < 2) return fail(c, AHMC_ERR_ARGUMENT, "funnel needs D >= 2");
     if (kind == AHMC_TARGET_HIER_GAUSS && c->D < 3) return fail(c, AHMC_ERR_ARGUMENT, "hier_gauss needs D >= 3");
+    if (kind == AHMC_TARGET_DENSE_GAUSS && c->wide) return fail(c, AHMC_ERR_UNSUPPORTED, wide_refusal(c, "set_target: the dense Gaussian (AHMC_TARGET_DENSE_GAUSS)"));
     if (n_params != need || (need > 0 && !params)) return fail(c, AHMC_ERR_ARGUMENT, "set_target: wrong parameter count for this family");
     // the new parameters go into a buffer of their own and replace the old ones only once they are on the device: a failure
     // on the way leaves the context with its previous target intact
@@ -1458,6 +1488,7 @@ int32_t ahmc_set_target(ahmc_ctx* ctx, int32_t kind, const void* params, int64_t
 int32_t ahmc_set_target_plugin(ahmc_ctx* ctx, const char* plugin_so, const void* params, int64_t n_params) {
   FOR_CTX_MUT(ctx, {
     if (!plugin_so) return fail(c, AHMC_ERR_ARGUMENT, "set_target_plugin: path is NULL");
+    if (c->wide) return fail(c, AHMC_ERR_UNSUPPORTED, wide_refusal(c, "set_target_plugin: a target plugin (compiled into one fused geometry)"));
     if (n_params < 0 || (n_params > 0 && !params)) return fail(c, AHMC_ERR_ARGUMENT, "set_target_plugin: bad parameter array");
     void* dl = dlopen(plugin_so, RTLD_NOW | RTLD_LOCAL);
     if (!dl) return fail(c, AHMC_ERR_ARGUMENT, std::string("set_target_plugin: cannot load ") + plugin_so + ": " + dlerror());
@@ -1835,6 +1866,7 @@ int32_t ahmc_sample_reserve(ahmc_ctx* ctx, const ahmc_kernel_cfg* cfg, int64_t n
 
 int32_t ahmc_set_ref_compat(ahmc_ctx* ctx, int32_t on) {
   FOR_CTX_MUT(ctx, {
+    if (on != 0 && c->wide) return fail(c, AHMC_ERR_UNSUPPORTED, wide_refusal(c, "ahmc_set_ref_compat (the step-synchronous engine has no coupled early exit)"));
     c->ref_compat = on != 0;
     return AHMC_OK;
   });
@@ -2182,6 +2214,7 @@ int32_t ahmc_get_info(ahmc_ctx* ctx, int32_t what, int64_t* out) {
     switch (what) {
       case AHMC_INFO_GROUP_LANES: *out = c->G; break;
       case AHMC_INFO_ELEMS_PER_LANE: *out = c->E; break;
+      case AHMC_INFO_WIDE: *out = c->wide ? 1 : 0; break;
       case AHMC_INFO_NUTS_LAUNCHES: *out = c->nuts_launches; break;
       case AHMC_INFO_NUTS_BATCH: *out = nuts_batch(c); break;
       case AHMC_INFO_ITERATION: *out = (int64_t)c->iteration; break;

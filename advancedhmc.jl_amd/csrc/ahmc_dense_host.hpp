@@ -2,9 +2,11 @@
 // after Ctx / make_kp / launch_fill_caches).  See ahmc_dense.hpp for the design.
 #pragma once
 
+// the step-synchronous engine serves the context: a dense metric or target, a user kernel, or a wide context (no fused geometry:
+// every target there, ExternalTarget included — its ask / tell runs on this engine anyway, and ℓκ comes from dn_velocity)
 template <class T>
 bool dense_engine(const Ctx<T>* c) {
-  return c->metric_kind == AHMC_METRIC_DENSE || c->target_kind == AHMC_TARGET_DENSE_GAUSS || c->target_kind == AHMC_TARGET_KERNEL;
+  return c->wide || c->metric_kind == AHMC_METRIC_DENSE || c->target_kind == AHMC_TARGET_DENSE_GAUSS || c->target_kind == AHMC_TARGET_KERNEL;
 }
 
 // lp[c] ← sanitize(lp[c]) for the listed chains (PhasePoint: a non-finite ℓπ → −Inf, src/hamiltonian.jl:95-104)
@@ -40,11 +42,33 @@ int dn_user_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = tru
   return AHMC_OK;
 }
 
-// (ℓπ, g) of the listed chains for a target that is not the dense Gaussian: the user's kernel, or the built-in family's /
-// the plugin's group kernel (which has no chain list: it evaluates every chain)
+// wide context, built-in family: (ℓπ, g′) of the listed chains by k_w_target (ahmc_wide.hpp).  θ′ from X, g′ to Y, addressed as
+// dn_gemm's pool operands (ptidx null, cs = 0: the plain (D, N) arrays); ℓπ to c->lp, sanitised.
+template <class T>
+int dn_wide_target(Ctx<T>* c, const int* list, int64_t n, const T* X, T* Y, const int* ptidx = nullptr, int64_t ps = 0, int64_t cs = 0) {
+  if (n <= 0) return AHMC_OK;
+  if (cs == 0) cs = c->D;
+  const dim3 grid((unsigned)n), block(WT_THREADS);
+  switch (c->target_kind) {
+#define AHMC_W_LAUNCH(TK) hipLaunchKernelGGL((k_w_target<T, TK>), grid, block, 0, c->stream, (const T*)c->tparams, X, Y, c->lp, (int)c->D, n, list, ptidx, ps, cs)
+    case AHMC_TARGET_ISO_GAUSS: AHMC_W_LAUNCH(0); break;
+    case AHMC_TARGET_DIAG_GAUSS: AHMC_W_LAUNCH(1); break;
+    case AHMC_TARGET_FUNNEL: AHMC_W_LAUNCH(2); break;
+    case AHMC_TARGET_HIER_GAUSS: AHMC_W_LAUNCH(3); break;
+#undef AHMC_W_LAUNCH
+    default: return fail(c, AHMC_ERR_UNSUPPORTED, "wide context: no step-synchronous kernel for this target kind");
+  }
+  HIPCHK(hipGetLastError());
+  return AHMC_OK;
+}
+
+// (ℓπ, g) of the listed chains for a target that is not the dense Gaussian: the user's kernel; on a wide context the built-in
+// family's k_w_target; else the built-in family's / the plugin's group kernel (which has no chain list: it evaluates every chain)
 template <class T>
 int dn_other_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
-  return c->target_kind == AHMC_TARGET_KERNEL ? dn_user_target(c, list, n, sanitize_lp) : launch_fill_caches_builtin(c);
+  if (c->target_kind == AHMC_TARGET_KERNEL) return dn_user_target(c, list, n, sanitize_lp);
+  if (c->wide) return dn_wide_target(c, list, n, (const T*)c->th, c->g);
+  return launch_fill_caches_builtin(c);
 }
 
 template <class T>
@@ -599,6 +623,7 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   DP<T> q = make_dp(c);
   q.n_trans = n_trans;
   const bool dm = c->metric_kind == AHMC_METRIC_DENSE, dt = c->target_kind == AHMC_TARGET_DENSE_GAUSS;
+  const bool wt = c->wide && c->target_kind != AHMC_TARGET_KERNEL;  // wide built-in family: k_w_target reads θ′ from / writes g′ to the pool point itself
   const T* minv_d = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
   const int pc = c->minv_per_chain ? 1 : 0;
   T* Wcur = dm ? c->dn_W + (size_t)DS_CUR_W * c->D * c->N : nullptr;
@@ -632,7 +657,7 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
     q2.n_trans = n_trans; q2.n_pt = c->dn_npt; q2.n_rho = c->dn_nrho; q2.n_active = c->dn_active; q2.list = nullptr; q2.n_list = c->N;
     CS = (int64_t)c->dn_npt * PS;
     q2.dense_metric = dm ? 1 : 0;
-    q2.staged = dt ? 0 : 1;
+    q2.staged = (dt || wt) ? 0 : 1;
     if (adapt_i0 >= 0) {
       q2.adapt_ss = 1;
       q2.i0 = adapt_i0;
@@ -817,6 +842,9 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
           c->stream = h.s;
         } else if (dt && dm && c->dn_fused_ok) {
           rc = dn_gemm(c, c->tparams, gX, gY, h.n_list, h.list, c->dn_C, gW, pti, ps, ps, cs, cs);  // g′ = Pθ′ and w′ = (M⁻¹P)θ′, one launch
+          if (rc) return bail(rc);
+        } else if (wt) {
+          rc = dn_wide_target(c, h.list, h.n_list, gX, gY, pti, ps, cs);  // (ℓπ sanitised in the kernel; a wide context has no dense metric)
           if (rc) return bail(rc);
         } else {
           // (a target that is not the dense Gaussian reads θ′ from / leaves g′ in the context's arrays: the pool is "staged")

@@ -23,13 +23,18 @@ namespace ahmc {
   X(128, 4) X(256, 4) X(512, 4) X(128, 8) X(256, 8) X(512, 8) AHMC_GEOMETRIES_EXTRA(X)
 #endif
 
-// call f(std::integral_constant<int,G>{}, std::integral_constant<int,E>{}) for a run-time geometry
+// call f(std::integral_constant<int,G>{}, std::integral_constant<int,E>{}) for a run-time geometry; false (nothing called)
+// for a geometry that was not compiled — the host checks has_geometry first (a wide context has G = E = 0)
 template <class F>
-inline void with_geometry(int G, int E, F&& f) {
+inline bool with_geometry(int G, int E, F&& f) {
 #define AHMC_GEO_CASE(g, e) \
-  if (G == g && E == e) { f(std::integral_constant<int, g>{}, std::integral_constant<int, e>{}); return; }
+  if (G == g && E == e) { f(std::integral_constant<int, g>{}, std::integral_constant<int, e>{}); return true; }
   AHMC_GEOMETRIES(AHMC_GEO_CASE)
 #undef AHMC_GEO_CASE
+  return false;
+}
+inline bool has_geometry(int G, int E) {
+  return with_geometry(G, E, [](auto, auto) {});
 }
 
 constexpr int AHMC_N_TARGETS = 4;  // iso, diag, funnel, hier (AHMC_TARGET_* 0..3)

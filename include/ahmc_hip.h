@@ -113,7 +113,16 @@ enum {
 
 /* Allocate a context for N chains of dimension D on `device`.  `stream` is a hipStream_t to
  * enqueue on (NULL → the library creates its own).  Replaces the implicit allocation done by
- * sample_init / resize (src/sampler.jl:25-46).                                               */
+ * sample_init / resize (src/sampler.jl:25-46).
+ * D <= 4096 gets a thread geometry of the fused kernels (AHMC_INFO_GROUP_LANES / _ELEMS_PER_LANE).
+ * D > 4096 — or any D when the environment variable AHMC_FORCE_WIDE=1 is set at this call (an
+ * experiment switch for tests and A/B runs) — makes a WIDE context (AHMC_INFO_WIDE = 1): every
+ * call runs on the step-synchronous engine, whose chains live in HBM.  A wide context serves
+ * Unit / Diag metrics (shared or per-chain M⁻¹), the four built-in families, AHMC_TARGET_KERNEL and
+ * AHMC_TARGET_EXTERNAL, NUTS (max_depth <= 17) and static HMC with every integrator, adaptor and
+ * sampling call; it refuses DenseEuclideanMetric, AHMC_TARGET_DENSE_GAUSS, target plugins and
+ * ahmc_set_ref_compat with AHMC_ERR_UNSUPPORTED.  Memory: 16·max_depth + 37 D-vectors
+ * per chain for NUTS.                                                          */
 int32_t ahmc_create(int32_t device, int32_t dtype, int64_t D, int64_t N, void* stream,
                     ahmc_ctx** out);
 int32_t ahmc_destroy(ahmc_ctx* ctx);
@@ -472,7 +481,9 @@ typedef enum {
   AHMC_INFO_DENSE_EPOCH_LAUNCHES = 13,      /* launches of the chain-complete dense kernel (k_dense_epoch, round 4) since ahmc_create  */
   AHMC_INFO_STEPSIZE_SCALAR = 14            /* 1: the context holds ONE nominal step size (ahmc_set_stepsize with n = 1, not adapted per chain
                                                since) — ahmc_get_stepsize always fills N values, so a checkpoint asks here whether to hand
-                                               back one (FixedIntegrationTime takes nothing else, src/trajectory.jl:241-243)          */
+                                               back one (FixedIntegrationTime takes nothing else, src/trajectory.jl:241-243)          */,
+  AHMC_INFO_WIDE = 15                       /* 1: a wide context (D > 4096, or AHMC_FORCE_WIDE=1 at ahmc_create): no fused-kernel geometry,
+                                               every call runs on the step-synchronous engine; GROUP_LANES / ELEMS_PER_LANE are 0    */
 } ahmc_info;
 int32_t ahmc_get_info(ahmc_ctx* ctx, int32_t what, int64_t* out);
 
