@@ -158,6 +158,14 @@ SIGNATURES = {
     "ahmc_ess": (_i32, [_vp, _vp, _i64, _vp]),
 }
 
+# include/ahmc_diag.h: optional entry points (the HIP engine exports them, the CPU checker does not); bound when present
+AHMC_DIAG_VERSION = 1
+DIAG_SIGNATURES = {
+    "ahmc_diag_version": (_i32, []),
+    "ahmc_diag_summary": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "ahmc_diag_rank_normalize": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -182,6 +190,16 @@ class CLib:
         if v != AHMC_ABI_VERSION:
             raise ImportError(f"{self.path}: ABI version {v}, expected {AHMC_ABI_VERSION}")
         self.backend = self.dll.ahmc_backend().decode()
+        # ahmc_diag.h: all of it or none of it
+        diag = [getattr(self.dll, name, None) for name in DIAG_SIGNATURES]
+        self.has_diag = all(fn is not None for fn in diag)
+        if self.has_diag:
+            for fn, (res, args) in zip(diag, DIAG_SIGNATURES.values()):
+                fn.restype = res
+                fn.argtypes = args
+            v = self.dll.ahmc_diag_version()
+            if v != AHMC_DIAG_VERSION:
+                raise ImportError(f"{self.path}: ahmc_diag version {v}, expected {AHMC_DIAG_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

@@ -856,6 +856,33 @@ class Engine:
         self._call("ahmc_ess", draws_ptr if isinstance(draws_ptr, C.c_void_p) else capi.as_ptr(draws_ptr), int(n_draws), capi.as_ptr(out))
         return out
 
+    # -- convergence diagnostics on the device (include/ahmc_diag.h) --
+    def _need_diag(self, what):
+        if not getattr(self.lib, "has_diag", False):
+            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_diag.h")
+
+    def summarystats(self, draws_ptr, n_draws, max_lag=0, out=None):
+        """MCMCChains' `summarystats` columns of the (D, N, n_draws) device buffer `run(samples_out=…)` filled, pooled over all N
+        chains: a dict name → (D,) array (diagnostics.SUMMARY_NAMES; diagnostics.summarystats is the host mirror).  `out`: optional
+        (9, D) float64 buffer, host or device, that receives the rows."""
+        self._need_diag("summarystats")
+        buf = np.empty((9, self.D), dtype=np.float64) if out is None else out
+        self._call("ahmc_diag_summary", draws_ptr if isinstance(draws_ptr, C.c_void_p) else capi.as_ptr(draws_ptr), int(n_draws), int(max_lag),
+                   capi.as_ptr(buf))
+        if out is not None:
+            return out
+        from .diagnostics import SUMMARY_NAMES
+
+        return {k: buf[i].copy() for i, k in enumerate(SUMMARY_NAMES)}
+
+    def rank_normalize(self, draws_ptr, n_draws, d, folded=False, out=None):
+        """z (or the folded z_f) of dimension d: (n_draws, N) float64, element (k, c) of draw k of chain c; NaN at a dropped middle draw"""
+        self._need_diag("rank_normalize")
+        buf = np.empty((int(n_draws), self.N), dtype=np.float64) if out is None else out
+        self._call("ahmc_diag_rank_normalize", draws_ptr if isinstance(draws_ptr, C.c_void_p) else capi.as_ptr(draws_ptr), int(n_draws), int(d),
+                   1 if folded else 0, capi.as_ptr(buf))
+        return buf
+
     @property
     def stream(self):
         return self.lib.dll.ahmc_stream(self._ctx)

@@ -71,7 +71,8 @@ def _sources_digest() -> str:
         if f.endswith((".hip", ".h", ".hpp")):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
-    h.update(open(os.path.join(INCLUDE, "ahmc_hip.h"), "rb").read())
+    for hdr in ("ahmc_hip.h", "ahmc_diag.h"):
+        h.update(open(os.path.join(INCLUDE, hdr), "rb").read())
     h.update(" ".join(FLAGS + PART_B_FLAGS).encode())
     return h.hexdigest()
 

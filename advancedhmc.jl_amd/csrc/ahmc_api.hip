@@ -3,10 +3,12 @@
 // methods do, and enqueues the kernels of ahmc_kernels.hpp.  No CPU compute path exists here:
 // every numerical result comes from a kernel.
 #include "ahmc_hip.h"
+#include "ahmc_diag.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
 #include "ahmc_dense_mn.hpp"
 #include "ahmc_wide.hpp"
+#include "ahmc_diag.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: the entry points are resolved at run time (ahmc_multi_host.hpp)
@@ -409,6 +411,7 @@ int launch_fill_caches_builtin(Ctx<T>* c) {
 #include "ahmc_dense_mn_host.hpp"
 #include "ahmc_ext_host.hpp"
 #include "ahmc_multi_host.hpp"
+#include "ahmc_diag_host.hpp"
 
 void comm_destroy_raw(void* comm) {
   if (comm && rccl_api().CommDestroy) (void)rccl_api().CommDestroy(static_cast<ncclComm_t>(comm));
@@ -2382,6 +2385,20 @@ int32_t ahmc_ess(ahmc_ctx* ctx, const void* draws, int64_t n_draws, void* out) {
     if (!out_dev) HIPCHK(hipMemcpyAsync(out, dst, sizeof(T) * DN, hipMemcpyDefault, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return AHMC_OK;
+  });
+}
+
+// ---- include/ahmc_diag.h: MCMCChains' summarystats columns on the device (ahmc_diag.hpp, ahmc_diag_host.hpp) ----------------
+int32_t ahmc_diag_version(void) { return AHMC_DIAG_VERSION; }
+
+int32_t ahmc_diag_summary(ahmc_ctx* ctx, const void* draws, int64_t n_draws, int64_t max_lag, double* out) {
+  FOR_CTX(ctx, { return diag_impl(c, draws, n_draws, max_lag, -1, 0, out, "diag_summary"); });
+}
+
+int32_t ahmc_diag_rank_normalize(ahmc_ctx* ctx, const void* draws, int64_t n_draws, int64_t d, int32_t folded, double* out) {
+  FOR_CTX(ctx, {
+    if (d < 0) return fail(c, AHMC_ERR_ARGUMENT, "diag_rank_normalize: dimension out of range");
+    return diag_impl(c, draws, n_draws, 0, d, (int)folded, out, "diag_rank_normalize");
   });
 }
 

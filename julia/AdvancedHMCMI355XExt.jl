@@ -509,4 +509,6 @@ function AdvancedHMC.EBFMI(z::MI355XChains{T}) where {T}
     return out
 end
 
+include("AdvancedHMCMI355XDiag.jl")  # summarystats_device: include/ahmc_diag.h
+
 end # module
