@@ -399,6 +399,29 @@ def build_target_plugin_from_object(obj: str, dtype, G: int, E: int, n_params: i
     return out
 
 
+def build_probe_object(source: str, defines=(), force: bool = False) -> str:
+    """hipcc --genco of a file of test kernels that include the engine's device headers (tests/device_probe/) → a gfx950 code
+    object for hipModuleLoad.  Compiled with the engine's own FLAGS (so a flag change reaches the probe too), `-I include
+    -I csrc` and `-D<define>` for each of `defines`; cached outside the repository, keyed on the include closure of the
+    source, the defines and the flags."""
+    source = os.path.abspath(source)
+    defs = [f"-D{d}" for d in defines]
+    h = hashlib.sha256(_include_closure(source, (INCLUDE, CSRC)) + "\0".join(FLAGS + defs).encode()).hexdigest()[:20]
+    out_dir = os.path.join(OBJ, "probes")
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, f"{os.path.splitext(os.path.basename(source))[0]}_{h}.hsaco")
+    if os.path.exists(out) and not force:
+        return out
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    tmp = out + f".tmp{os.getpid()}"
+    cmd = [hipcc, *FLAGS, *defs, "-I", INCLUDE, "-I", CSRC, "--genco", source, "-o", tmp]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError(f"hipcc --genco failed on {source}:\n{' '.join(cmd)}\n{res.stdout}\n{res.stderr}")
+    os.replace(tmp, out)
+    return out
+
+
 def build_code_object(source: str, force: bool = False) -> str:
     """hipcc --genco of a file of user KERNELS (ahmc_set_target_kernel) → a gfx950 code object for hipModuleLoad; cached
     outside the repository by content."""

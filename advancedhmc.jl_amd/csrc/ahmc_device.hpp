@@ -38,7 +38,8 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
   return Philox4{{c0, c1, c2, c3}};
 }
 
-// 53-bit uniform in the open interval (0,1)
+// 53-bit uniform in (0, 1]: (bits + ½)·2^-53 is exact below 2^52; above, the + ½ is a tie rounded to even, so the top input
+// bits = 2^53 − 1 gives exactly 1.0 (every other input lies in (0, 1); the oracle computes the same values)
 __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {
   uint64_t bits = ((uint64_t)(hi >> 5) << 26) | (uint64_t)(lo >> 6);
   return ((double)bits + 0.5) * (1.0 / 9007199254740992.0);
@@ -152,8 +153,9 @@ __device__ __forceinline__ float leaf_exp(float x) { return exp(x); }
 // 1: the same without the overflow select (3 VALU less, same bits where it matters);
 // 2: table-assisted — x = (64 n + j)·ln2/64 + t, |t| <= ln2/128: exp(x) = 2^n · T[j] · (1 + (e^t − 1)) with a 64-entry
 //    table of 2^(j/64) (a scalar load when the chain owns the wave) and a degree-5 polynomial: ≈9 VALU less than the
-//    Horner-11 form; ≤ 1.01 ulp against the exact value (checked on 2·10^5 arguments), i.e. last-ulp differences
-//    against the device library's exp().
+//    Horner-11 form; ≤ 1.34 ulp against the exact value (½ ulp of the rounded table entry, ≤ 0.32 ulp from truncating
+//    e^t − 1 after t^5 at |t| = ln2/128, ½ ulp for the final fma; tests/test_device_primitives.py, > 2^22 arguments with both
+//    edges of every table bucket: 1.27 ulp measured), i.e. last-ulp differences against the device library's exp().
 #ifndef AHMC_LEAF_EXP
 #define AHMC_LEAF_EXP 2   // measured on cfg2 (sampling phase, in-kernel leapfrog/s): 1: 2.654e9, 2: 2.718e9
 #endif

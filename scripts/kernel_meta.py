@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Register / scratch / LDS footprint of the kernels in an object file of the build (the code object's metadata notes):
 
-    python scripts/kernel_meta.py <unit.o> [name filter]      e.g.  ~/.cache/ahmc_build/inst_f64_t2.o 'k_nuts<double, 16, 2'
+    python scripts/kernel_meta.py <unit.o | code object> [name filter]      e.g.  ~/.cache/ahmc_build/inst_f64_t2.o 'k_nuts<double, 16, 2'
 """
 import os
 import re
@@ -14,11 +14,21 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def kernel_meta(obj):
+    """`obj`: a host object / shared library with an offload section, an offload bundle (`hipcc --genco`) or a bare code object"""
     with tempfile.TemporaryDirectory(prefix="ahmc_meta_") as tmp:
         cp = os.path.join(tmp, os.path.basename(obj))
         shutil.copyfile(obj, cp)
-        subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", cp], capture_output=True, check=True)
-        co = cp + ".0.hipv4-amdgcn-amd-amdhsa--gfx950"
+        with open(cp, "rb") as f:
+            magic = f.read(24)
+        if magic.startswith(b"__CLANG_OFFLOAD_BUNDLE__"):
+            co = cp + ".gfx950.co"
+            subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                            f"--input={cp}", f"--output={co}"], capture_output=True, check=True)
+        elif b"AMDGPU" in subprocess.run([f"{LLVM}/llvm-readelf", "-h", cp], capture_output=True, text=True).stdout.encode():
+            co = cp
+        else:
+            subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", cp], capture_output=True, check=True)
+            co = cp + ".0.hipv4-amdgcn-amd-amdhsa--gfx950"
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
     out, cur = [], None
     for line in notes.splitlines():
