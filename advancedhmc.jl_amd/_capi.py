@@ -166,6 +166,16 @@ DIAG_SIGNATURES = {
     "ahmc_diag_rank_normalize": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
 }
 
+# include/ahmc_rank_update.h: optional entry points of RankUpdateEuclideanMetric (the HIP engine exports them, the CPU checker does not)
+AHMC_RANK_UPDATE_VERSION = 1
+AHMC_RANK_UPDATE_MAX_K = 32
+METRIC_RANK_UPDATE = 3  # (Python side only: the C ABI has no such AHMC_METRIC_* — the metric has entry points of its own)
+RU_SIGNATURES = {
+    "ahmc_rank_update_version": (_i32, []),
+    "ahmc_set_metric_rank_update": (_i32, [_vp, _vp, _vp, _vp, _i64]),
+    "ahmc_get_metric_rank_update": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -200,6 +210,16 @@ class CLib:
             v = self.dll.ahmc_diag_version()
             if v != AHMC_DIAG_VERSION:
                 raise ImportError(f"{self.path}: ahmc_diag version {v}, expected {AHMC_DIAG_VERSION}")
+        # ahmc_rank_update.h: likewise
+        ru = [getattr(self.dll, name, None) for name in RU_SIGNATURES]
+        self.has_rank_update = all(fn is not None for fn in ru)
+        if self.has_rank_update:
+            for fn, (res, args) in zip(ru, RU_SIGNATURES.values()):
+                fn.restype = res
+                fn.argtypes = args
+            v = self.dll.ahmc_rank_update_version()
+            if v != AHMC_RANK_UPDATE_VERSION:
+                raise ImportError(f"{self.path}: ahmc_rank_update version {v}, expected {AHMC_RANK_UPDATE_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

@@ -21,6 +21,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _capi as capi
+from . import rank_update as _ru
 from ._capi import ArgumentError
 
 
@@ -134,10 +135,69 @@ class DenseEuclideanMetric(AbstractMetric):
         self.size = (Minv.shape[0],)
 
 
+class RankUpdateEuclideanMetric(AbstractMetric):
+    """src/metric.jl:179-245.  M⁻¹ = Diagonal(A) + B·D·Bᵀ, one metric shared by all chains (the reference's is single-chain,
+    :322-323; sharing it is this engine's extension, as for DenseEuclideanMetric).  Constructors: RankUpdateEuclideanMetric(n),
+    ([T,] n), ([T,] (n,)) — the identity, k = 0 — and (A, B, D) with A the diagonal (a vector, or a 2-D diagonal matrix).
+    Fields A (the diagonal, (D,)), B (D, k), D (k, k), factorization (rank_update.WoodburyFactorization); arithmetic:
+    advancedhmc.jl_amd/rank_update.py."""
+    kind = capi.METRIC_RANK_UPDATE
+    D = None  # (the reference's field D, the k×k inner matrix — not AbstractMetric.D, the dimension: that is size[0] here)
+
+    def __init__(self, *args):
+        if len(args) == 3:
+            A, B, Dm = (np.asarray(x) for x in args)
+            if A.ndim == 2:
+                if A.shape[0] != A.shape[1] or np.count_nonzero(A - np.diag(np.diag(A))):
+                    raise ArgumentError(capi.ERR_ARGUMENT, "RankUpdateEuclideanMetric: A must be a Diagonal")
+                A = np.diag(A)
+            T = np.result_type(A, B, Dm)
+            if T not in (np.float32, np.float64):
+                T = np.dtype(np.float64)
+            if B.ndim != 2 or B.shape[0] != A.size or Dm.shape != (B.shape[1], B.shape[1]):
+                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: A {A.shape}, B {B.shape}, D {Dm.shape}")
+            self.A = np.ascontiguousarray(A, dtype=T)
+            self.B = np.asfortranarray(B, dtype=T)
+            self.D = np.asfortranarray(Dm, dtype=T)
+            if not (np.all(np.isfinite(self.A)) and np.all(self.A > 0)):
+                raise ArgumentError(capi.ERR_ARGUMENT, "DomainError: A must be a positive definite diagonal")
+            try:
+                self.factorization = _ru.woodbury_factorize(self.A, self.B, self.D)
+            except np.linalg.LinAlgError as e:
+                raise ArgumentError(capi.ERR_ARGUMENT, f"PosDefException: I + R·D·Rᵀ is not positive definite ({e})")
+        else:
+            if len(args) == 2:
+                T, n = np.dtype(args[0]), _size_tuple(args[1])[0]
+            elif len(args) == 1:
+                T, n = np.dtype(np.float64), _size_tuple(args[0])[0]
+            else:
+                raise ArgumentError(capi.ERR_ARGUMENT, "RankUpdateEuclideanMetric([T,] n), ([T,] (n,)) or (A, B, D)")
+            self.A = np.ones(n, dtype=T)
+            self.B = np.zeros((n, 0), dtype=T, order="F")
+            self.D = np.zeros((0, 0), dtype=T, order="F")
+            self.factorization = _ru.woodbury_factorize(self.A, self.B, self.D)
+        self.eltype = self.A.dtype
+        self.size = (self.A.size,)
+        self.Minv = None
+
+    @property
+    def rank(self):
+        return self.B.shape[1]
+
+    @property
+    def _diag_inv_metric(self):
+        return _ru.diag_inv_metric(self.A, self.B, self.D)
+
+    def __repr__(self):
+        return f"RankUpdateEuclideanMetric({np.array2string(self._diag_inv_metric[:6], precision=3)} ..., rank {self.rank})"
+
+
 def renew(metric, Minv):
     """src/metric.jl:31,69,117"""
     if isinstance(metric, UnitEuclideanMetric):
         return metric
+    if isinstance(metric, RankUpdateEuclideanMetric):
+        return RankUpdateEuclideanMetric(*Minv)  # (A, B, D)
     return type(metric)(np.asarray(Minv))
 
 
@@ -566,7 +626,25 @@ class Engine:
             return
         self._call("ahmc_set_target", target.kind, capi.as_ptr(p), 0 if p is None else p.size)
 
+    def _need_rank_update(self, what):
+        if not getattr(self.lib, "has_rank_update", False):
+            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_rank_update.h")
+
+    def _set_rank_update(self, A, B, Dm):
+        self._need_rank_update("RankUpdateEuclideanMetric")
+        A = np.ascontiguousarray(A, dtype=self.dtype).ravel()
+        B = np.asfortranarray(B, dtype=self.dtype)
+        Dm = np.asfortranarray(Dm, dtype=self.dtype)
+        if A.size != self.D:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"AxesMismatch: A has {A.size} elements but r has first axis {self.D}")
+        k = B.shape[1] if B.ndim == 2 else 0
+        self._call("ahmc_set_metric_rank_update", capi.as_ptr(A), capi.as_ptr(B) if k else None, capi.as_ptr(Dm) if k else None, k)
+        self.metric_kind = capi.METRIC_RANK_UPDATE
+
     def set_metric(self, metric):
+        if metric.kind == capi.METRIC_RANK_UPDATE:
+            self._set_rank_update(metric.A, metric.B, metric.D)
+            return
         if metric.kind == capi.METRIC_UNIT:
             self._call("ahmc_set_metric", metric.kind, None, 0)
         else:
@@ -576,9 +654,22 @@ class Engine:
             self._call("ahmc_set_metric", metric.kind, capi.as_ptr(M), M.size)
         self.metric_kind = metric.kind
 
+    def get_metric_rank_update(self):
+        """(A, B, D) of a RankUpdateEuclideanMetric as the context holds it (ahmc_get_metric_rank_update)"""
+        self._need_rank_update("get_metric_rank_update")
+        k = C.c_int64()
+        self._call("ahmc_get_metric_rank_update", None, None, None, C.byref(k))
+        A = np.empty(self.D, dtype=self.dtype)
+        B = np.empty((self.D, k.value), dtype=self.dtype, order="F")
+        Dm = np.empty((k.value, k.value), dtype=self.dtype, order="F")
+        self._call("ahmc_get_metric_rank_update", capi.as_ptr(A), capi.as_ptr(B) if k.value else None, capi.as_ptr(Dm) if k.value else None, None)
+        return A, B, Dm
+
     def get_metric(self):
         if self.metric_kind == capi.METRIC_UNIT:
             return None
+        if self.metric_kind == capi.METRIC_RANK_UPDATE:
+            return self.get_metric_rank_update()
         # size is whatever was set last (D, D*N or D*D): probe via a D*N then D buffer
         for shape in ((self.D, self.N), (self.D,), (self.D, self.D)):
             out = np.empty(shape, dtype=self.dtype, order="F")
@@ -792,7 +883,9 @@ class Engine:
                 "stepsize_scalar": bool(self.info("stepsize_scalar")), "accum": acc}
 
     def set_state(self, state: dict):
-        if state["metric"] is not None:
+        if state.get("metric_kind") == capi.METRIC_RANK_UPDATE:  # (A, B, D)
+            self._set_rank_update(*state["metric"])
+        elif state["metric"] is not None:
             self._call("ahmc_set_metric", state["metric_kind"], capi.as_ptr(np.asfortranarray(state["metric"], dtype=self.dtype)), state["metric"].size)
         eps = np.ascontiguousarray(state["stepsize"], dtype=self.dtype)
         if state.get("stepsize_scalar"):   # ONE nominal ϵ stays one (κ's integrator is restored as it was: FixedIntegrationTime needs it, Q6)

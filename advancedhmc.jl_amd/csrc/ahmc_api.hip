@@ -4,11 +4,13 @@
 // every numerical result comes from a kernel.
 #include "ahmc_hip.h"
 #include "ahmc_diag.h"
+#include "ahmc_rank_update.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
 #include "ahmc_dense_mn.hpp"
 #include "ahmc_wide.hpp"
 #include "ahmc_diag.hpp"
+#include "ahmc_rank_update.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: the entry points are resolved at run time (ahmc_multi_host.hpp)
@@ -27,6 +29,9 @@ using namespace ahmc;
 namespace {
 
 thread_local std::string g_create_err;
+
+// RankUpdateEuclideanMetric (include/ahmc_rank_update.h): a metric kind internal to the context — ahmc_set_metric does not accept it
+constexpr int AHMC_METRIC_RANK_UPDATE_CTX = 3;
 
 struct CtxBase {
   virtual ~CtxBase() {}
@@ -116,7 +121,7 @@ struct Ctx : CtxBase {
   int uk_block = 256, uk_cpb = 1;
   void* uk_user = nullptr;
   // metric
-  int metric_kind = AHMC_METRIC_UNIT;
+  int metric_kind = AHMC_METRIC_UNIT;  // AHMC_METRIC_* or AHMC_METRIC_RANK_UPDATE_CTX
   bool minv_per_chain = false;
   T *minv = nullptr, *sqrt_minv = nullptr;  // capacity D*N
   int64_t minv_n = 0;
@@ -231,6 +236,11 @@ struct Ctx : CtxBase {
   hipEvent_t ev_gemm[2] = {nullptr, nullptr}, ev_tree[2] = {nullptr, nullptr};  // AHMC_DENSE_SPLIT=2: GEMM stream <-> tree stream hand-over per chain half
   // WelfordCov of the shared dense metric: μ (D) [+ batch mean + column-sum partials], M, batch scatter, estimate
   T *wc_mu = nullptr, *wc_M = nullptr, *wc_S = nullptr, *wc_cov = nullptr;
+  // RankUpdateEuclideanMetric (ahmc_rank_update_host.hpp): one slab of A, 1/√A, B, Dm, Y, Tw, V⁻¹ at ru_off[0..6]
+  T* ru_buf = nullptr;
+  size_t ru_cap = 0;
+  int64_t ru_off[7] = {0, 0, 0, 0, 0, 0, 0};
+  int ru_k = 0;
   T* dn_C = nullptr;   // M⁻¹·P (dense metric + dense target), see dn_refresh_fused
   T* dn_Asw = nullptr; // P and M⁻¹·P in MFMA-fragment order (k_dense_swizzle), refreshed at the start of every batch
   int64_t dn_epoch_launches = 0;
@@ -272,7 +282,7 @@ struct Ctx : CtxBase {
     void* bufs[] = {vbase, tbase, ibase, lbase, tparams, minv, sqrt_minv, scratch, order, order_hist, adaptk_dev, hmc_H, da_m, da_eps, da_mu, da_xbar,
                     da_Hbar, wv_mu, wv_M, wv_var, ext_th, ext_alpha, redo, znorm, dn_minv, dn_uinv, dn_W, dn_es, dn_RB, dn_VB,
                     dn_S, dn_active, dn_list, wg_mu, wg_M, ext_g, wc_mu, wc_M, wc_S, wc_cov, stage[0], stage[1], dn_C, ext_gstage, ext_lpstage,
-                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp};
+                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp, ru_buf};
     for (void* b : bufs)
       if (b) (void)hipFree(b);
     for (auto* v : {&ev_pool, &ev_pending, &ev_pending_warm})
@@ -401,12 +411,13 @@ int launch_fill_caches_builtin(Ctx<T>* c) {
   int rc = fused_guard(c, "fill_caches");
   if (rc) return rc;
   KP<T> p = make_kp(c);
-  p.no_lk = c->metric_kind == AHMC_METRIC_DENSE ? 1 : 0;  // ℓκ = −½ rᵀM⁻¹r comes from the dense engine
+  p.no_lk = dn_recurrent(c) ? 1 : 0;  // ℓκ = −½ rᵀM⁻¹r comes from the dense engine
   if (const TargetOps<T>* o = ops_for(c)) o->fill_caches(c->G, c->E, group_grid(c), c->stream, p);
   HIPCHK(hipGetLastError());
   return AHMC_OK;
 }
 
+#include "ahmc_rank_update_host.hpp"
 #include "ahmc_dense_host.hpp"
 #include "ahmc_dense_mn_host.hpp"
 #include "ahmc_ext_host.hpp"
@@ -1029,6 +1040,12 @@ int adaptor_init(Ctx<T>* c, int kind, double delta, int ib, int tb, int ws) {
   c->stan_i = 0;
   c->windows_n_adapts = 0;
   if (kind == AHMC_ADAPT_NONE) return AHMC_OK;
+  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && kind != AHMC_ADAPT_STEPSIZE) {  // (the reference has no MassMatrixAdaptor for it)
+    c->adapt_kind = AHMC_ADAPT_NONE;
+    c->adapting = false;
+    return fail(c, AHMC_ERR_UNSUPPORTED, "adaptor_init: RankUpdateEuclideanMetric has no mass-matrix adaptor (MassMatrixAdaptor / NaiveHMCAdaptor / "
+                                         "StanHMCAdaptor): use StepSizeAdaptor or no adaptation");
+  }
   int rc;
   if (!c->da_m) {
     if ((rc = dev_alloc(c, &c->da_m, (size_t)c->N))) return rc;
@@ -1098,6 +1115,8 @@ int adaptor_init(Ctx<T>* c, int kind, double delta, int ib, int tb, int ws) {
 template <class T>
 int adapt(Ctx<T>* c, int64_t i, int64_t n_adapts, const T* th_ext = nullptr, const T* alpha_ext = nullptr, const T* g_ext = nullptr) {
   if (c->adapt_kind == AHMC_ADAPT_NONE || i > n_adapts) return AHMC_OK;
+  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && c->adapt_kind != AHMC_ADAPT_STEPSIZE)  // (an adaptor set up for an earlier metric)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "adapt: RankUpdateEuclideanMetric has no mass-matrix adaptor (the adaptor was set up for another metric)");
   if (i == n_adapts) c->adapting = false;
   const bool has_ss = c->adapt_kind != AHMC_ADAPT_MASSMATRIX;
   const bool has_mm = c->adapt_kind != AHMC_ADAPT_STEPSIZE && c->metric_kind == AHMC_METRIC_DIAG;
@@ -1577,6 +1596,8 @@ int32_t ahmc_set_metric(ahmc_ctx* ctx, int32_t kind, const void* Minv, int64_t n
 int32_t ahmc_get_metric(ahmc_ctx* ctx, void* out, int64_t n) {
   FOR_CTX(ctx, {
     if (c->metric_kind == AHMC_METRIC_UNIT) return fail(c, AHMC_ERR_ARGUMENT, "get_metric: unit metric has no array");
+    if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX)
+      return fail(c, AHMC_ERR_ARGUMENT, "get_metric: a RankUpdateEuclideanMetric has no M⁻¹ array: use ahmc_get_metric_rank_update (include/ahmc_rank_update.h)");
     if (n != c->minv_n) return fail(c, AHMC_ERR_ARGUMENT, "get_metric: size mismatch");
     HIPCHK(hipMemcpyAsync(out, c->metric_kind == AHMC_METRIC_DENSE ? c->dn_minv : c->minv, sizeof(T) * n, hipMemcpyDefault, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1713,6 +1734,7 @@ int32_t ahmc_lf_pre(ahmc_ctx* ctx, int32_t fwd, int64_t i, int64_t n_steps) {
   FOR_CTX_MUT(ctx, {
     if (!c->have_point) return fail(c, AHMC_ERR_STATE, "lf_pre before set_phasepoint");
     if (c->metric_kind == AHMC_METRIC_DENSE) return fail(c, AHMC_ERR_UNSUPPORTED, "lf_pre/lf_post are not implemented for DenseEuclideanMetric");
+    if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX) return fail(c, AHMC_ERR_UNSUPPORTED, "lf_pre/lf_post are not implemented for RankUpdateEuclideanMetric");
     KP<T> p = make_kp(c);
     const int64_t DN = c->D * c->N;
     hipLaunchKernelGGL((k_lf_pre<T>), dim3((unsigned)((DN + 255) / 256)), dim3(256), 0, c->stream, p, (int)fwd, i, n_steps);
@@ -1723,6 +1745,7 @@ int32_t ahmc_lf_pre(ahmc_ctx* ctx, int32_t fwd, int64_t i, int64_t n_steps) {
 
 int32_t ahmc_lf_post(ahmc_ctx* ctx, int32_t fwd, int64_t i, int64_t n_steps, const void* lp, const void* grad_neg) {
   FOR_CTX_MUT(ctx, {
+    if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX) return fail(c, AHMC_ERR_UNSUPPORTED, "lf_pre/lf_post are not implemented for RankUpdateEuclideanMetric");
     if (!lp || !grad_neg) return fail(c, AHMC_ERR_ARGUMENT, "lf_post: NULL argument");
     const int64_t DN = c->D * c->N;
     // the caller's arrays may live on the host or on the device: host arrays go through the context's persistent
@@ -1892,6 +1915,8 @@ static int32_t sample_from_impl(ahmc_ctx* ctx, const ahmc_kernel_cfg* cfg, int64
     if (!c->have_point) return fail(c, AHMC_ERR_STATE, "sample before set_position");
     if (drop_warmup && c->adapt_kind == AHMC_ADAPT_NONE)
       return fail(c, AHMC_ERR_ARGUMENT, "Cannot drop warmup samples if there is no adaptation phase.");  // src/sampler.jl:172
+    if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && c->adapt_kind != AHMC_ADAPT_NONE && c->adapt_kind != AHMC_ADAPT_STEPSIZE)
+      return fail(c, AHMC_ERR_UNSUPPORTED, "sample: RankUpdateEuclideanMetric has no mass-matrix adaptor (the adaptor was set up for another metric)");
     // a resumed run must continue where the restored state stopped: a Stan adaptor counts its own calls (state.i,
     // stan_adaptor.jl:137-159), so while it is adapting the absolute iteration is known and a mismatch is an error rather
     // than a silently wrong window schedule
@@ -2400,6 +2425,20 @@ int32_t ahmc_diag_rank_normalize(ahmc_ctx* ctx, const void* draws, int64_t n_dra
     if (d < 0) return fail(c, AHMC_ERR_ARGUMENT, "diag_rank_normalize: dimension out of range");
     return diag_impl(c, draws, n_draws, 0, d, (int)folded, out, "diag_rank_normalize");
   });
+}
+
+// ---- include/ahmc_rank_update.h: RankUpdateEuclideanMetric (ahmc_rank_update.hpp, ahmc_rank_update_host.hpp) ------------------------
+int32_t ahmc_rank_update_version(void) { return AHMC_RANK_UPDATE_VERSION; }
+
+int32_t ahmc_set_metric_rank_update(ahmc_ctx* ctx, const void* A, const void* B, const void* Dm, int64_t k) {
+  FOR_CTX_MUT(ctx, {
+    c->order_valid = false; c->sched = {};   // (as ahmc_set_metric)
+    return ru_set_metric(c, static_cast<const T*>(A), static_cast<const T*>(B), static_cast<const T*>(Dm), k);
+  });
+}
+
+int32_t ahmc_get_metric_rank_update(ahmc_ctx* ctx, void* A, void* B, void* Dm, int64_t* k) {
+  FOR_CTX(ctx, { return ru_get_metric(c, A, B, Dm, k); });
 }
 
 }  // extern "C"

@@ -6,7 +6,15 @@
 // every target there, ExternalTarget included — its ask / tell runs on this engine anyway, and ℓκ comes from dn_velocity)
 template <class T>
 bool dense_engine(const Ctx<T>* c) {
-  return c->wide || c->metric_kind == AHMC_METRIC_DENSE || c->target_kind == AHMC_TARGET_DENSE_GAUSS || c->target_kind == AHMC_TARGET_KERNEL;
+  return c->wide || c->metric_kind == AHMC_METRIC_DENSE || c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX || c->target_kind == AHMC_TARGET_DENSE_GAUSS ||
+         c->target_kind == AHMC_TARGET_KERNEL;
+}
+
+// the velocity v = M⁻¹r is carried by the recurrence v ← v − ϵ/2·w, w = M⁻¹g (a non-diagonal M⁻¹: dense or rank-update).  Whether
+// M⁻¹ is a D×D matrix (WelfordCov, dn_refresh_fused, the epoch kernels) is the separate test metric_kind == AHMC_METRIC_DENSE.
+template <class T>
+bool dn_recurrent(const Ctx<T>* c) {
+  return c->metric_kind == AHMC_METRIC_DENSE || c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX;
 }
 
 // lp[c] ← sanitize(lp[c]) for the listed chains (PhasePoint: a non-finite ℓπ → −Inf, src/hamiltonian.jl:95-104)
@@ -96,6 +104,21 @@ int dn_gemm(Ctx<T>* c, const T* A, const T* X, T* Y, int64_t ncols, const int* l
   return AHMC_OK;
 }
 
+// Y = M⁻¹X for a non-diagonal metric, with dn_gemm's operand addressing: the dense metric's GEMM or the rank update's k_ru_apply
+template <class T>
+int dn_minv_apply(Ctx<T>* c, const T* X, T* Y, int64_t ncols, const int* list = nullptr, const int* ptidx = nullptr, int64_t xps = 0, int64_t yps = 0,
+                  int64_t xcs = 0, int64_t ycs = 0) {
+  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX) return ru_apply(c, X, Y, ncols, list, ptidx, xps, yps, xcs, ycs);
+  return dn_gemm(c, c->dn_minv, X, Y, ncols, list, (const T*)nullptr, (T*)nullptr, ptidx, xps, yps, xcs, ycs);
+}
+
+// R = the momenta of the standard normals Z (ncols plain columns) for a non-diagonal metric: U⁻¹Z (dense) or k_ru_momentum
+template <class T>
+int dn_momentum_map(Ctx<T>* c, const T* Z, T* R, int64_t ncols) {
+  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX) return ru_momentum(c, Z, R, ncols);
+  return dn_gemm(c, c->dn_uinv, Z, R, ncols);
+}
+
 template <class T>
 DP<T> make_dp(Ctx<T>* c) {
   DP<T> q;
@@ -108,7 +131,7 @@ DP<T> make_dp(Ctx<T>* c) {
   q.n_active = c->dn_active;
   q.list = nullptr;
   q.n_list = c->N;
-  q.dense_metric = c->metric_kind == AHMC_METRIC_DENSE ? 1 : 0;
+  q.dense_metric = dn_recurrent(c) ? 1 : 0;
   return q;
 }
 
@@ -189,8 +212,8 @@ int dn_velocity(Ctx<T>* c, const int* list = nullptr, int64_t n = -1) {
   if (n < 0) n = c->N;
   if (n == 0) return AHMC_OK;
   T* V = c->dn_W + (size_t)DS_CUR_V * c->D * c->N;
-  if (c->metric_kind == AHMC_METRIC_DENSE) {
-    int rc = dn_gemm(c, c->dn_minv, c->r, V, n, list);
+  if (dn_recurrent(c)) {
+    int rc = dn_minv_apply(c, c->r, V, n, list);
     if (rc) return rc;
   } else {
     hipLaunchKernelGGL((k_d_vdiag<T>), dim3(dn_grid_elems(c, n)), dim3(256), 0, c->stream, c->r,
@@ -226,11 +249,11 @@ int dn_fill_caches(Ctx<T>* c) {
   return dn_velocity(c);
 }
 
-// W = M⁻¹g of the current points (dense metric): what the recurrence of dn_step starts from
+// W = M⁻¹g of the current points (dense / rank-update metric): what the recurrence of dn_step starts from
 template <class T>
 int dn_prepare_w(Ctx<T>* c) {
-  if (c->metric_kind != AHMC_METRIC_DENSE) return AHMC_OK;
-  return dn_gemm(c, c->dn_minv, c->g, c->dn_W + (size_t)DS_CUR_W * c->D * c->N, c->N);
+  if (!dn_recurrent(c)) return AHMC_OK;
+  return dn_minv_apply(c, c->g, c->dn_W + (size_t)DS_CUR_W * c->D * c->N, c->N);
 }
 
 // One leapfrog of every listed chain with its signed step es[c] (0 = motionless: caches only).
@@ -240,7 +263,7 @@ template <class T>
 int dn_step(Ctx<T>* c, const int* list = nullptr, int64_t n = -1) {
   if (n < 0) n = c->N;
   if (n == 0) return AHMC_OK;
-  const bool dm = c->metric_kind == AHMC_METRIC_DENSE;
+  const bool dm = dn_recurrent(c);
   T* V = c->dn_W + (size_t)DS_CUR_V * c->D * c->N;
   T* W = dm ? c->dn_W + (size_t)DS_CUR_W * c->D * c->N : nullptr;
   const T* minv = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
@@ -252,7 +275,7 @@ int dn_step(Ctx<T>* c, const int* list = nullptr, int64_t n = -1) {
   else rc = dn_other_target(c, list, n);                      // built-in family: (ℓπ, g′) by the group kernel; or the user's kernel
   if (rc) return rc;
   if (dm) {
-    rc = dn_gemm(c, c->dn_minv, c->g, W, n, list);  // w′ = M⁻¹g′
+    rc = dn_minv_apply(c, c->g, W, n, list);  // w′ = M⁻¹g′
     if (rc) return rc;
   }
   hipLaunchKernelGGL((k_d_post<T>), dim3(dn_grid_chains(c, n)), dim3(256), 0, c->stream, c->th, c->r, c->g, V, W, minv, pc, c->dn_es, c->lp, c->lk,
@@ -262,7 +285,7 @@ int dn_step(Ctx<T>* c, const int* list = nullptr, int64_t n = -1) {
 }
 
 // fresh momenta of n_trans consecutive transitions (iterations c->iteration + k):
-// R_k = U⁻¹ Z_k (Dense; rand_momentum src/metric.jl:311-320) or Z_k ./ √M⁻¹; V_k = M⁻¹ R_k
+// R_k = U⁻¹ Z_k (Dense; rand_momentum src/metric.jl:311-320), the rank update's map (:322-337) or Z_k ./ √M⁻¹; V_k = M⁻¹ R_k
 template <class T>
 int dn_momenta(Ctx<T>* c, int n_trans, T* R, T* V, uint32_t purpose = RNG_MOMENTUM) {
   const size_t need = (size_t)n_trans * (size_t)c->D * (size_t)c->N;
@@ -278,10 +301,10 @@ int dn_momenta(Ctx<T>* c, int n_trans, T* R, T* V, uint32_t purpose = RNG_MOMENT
   hipLaunchKernelGGL((k_normals<T>), dim3(grid), dim3(256), 0, c->stream, p, c->znorm, n_trans, purpose);
   HIPCHK(hipGetLastError());
   const int64_t cols = (int64_t)n_trans * c->N;
-  if (c->metric_kind == AHMC_METRIC_DENSE) {
-    int rc = dn_gemm(c, c->dn_uinv, c->znorm, R, cols);
+  if (dn_recurrent(c)) {
+    int rc = dn_momentum_map(c, c->znorm, R, cols);
     if (rc) return rc;
-    if (V) rc = dn_gemm(c, c->dn_minv, R, V, cols);
+    if (V) rc = dn_minv_apply(c, R, V, cols);
     return rc;
   }
   const T* sq = c->metric_kind == AHMC_METRIC_DIAG ? c->sqrt_minv : nullptr;
@@ -485,7 +508,7 @@ int dn_nuts_batch_momenta(Ctx<T>* c, int n_trans, double refresh_alpha) {
   if (refresh_alpha == 0) return dn_momenta(c, n_trans, c->dn_RB, c->dn_VB);
   rc = dn_fresh_momentum(c, refresh_alpha, c->dn_RB);
   if (rc) return rc;
-  if (c->metric_kind == AHMC_METRIC_DENSE) return dn_gemm(c, c->dn_minv, c->dn_RB, c->dn_VB, c->N);
+  if (dn_recurrent(c)) return dn_minv_apply(c, c->dn_RB, c->dn_VB, c->N);
   hipLaunchKernelGGL((k_d_vdiag<T>), dim3(dn_grid_elems(c)), dim3(256), 0, c->stream, c->dn_RB, c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr,
                      c->minv_per_chain ? 1 : 0, c->dn_VB, (int)c->D, c->N, (const int*)nullptr);
   HIPCHK(hipGetLastError());
@@ -622,7 +645,7 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   p.samples_out = samples_dev;
   DP<T> q = make_dp(c);
   q.n_trans = n_trans;
-  const bool dm = c->metric_kind == AHMC_METRIC_DENSE, dt = c->target_kind == AHMC_TARGET_DENSE_GAUSS;
+  const bool dm = dn_recurrent(c), dt = c->target_kind == AHMC_TARGET_DENSE_GAUSS;
   const bool wt = c->wide && c->target_kind != AHMC_TARGET_KERNEL;  // wide built-in family: k_w_target reads θ′ from / writes g′ to the pool point itself
   const T* minv_d = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
   const int pc = c->minv_per_chain ? 1 : 0;
@@ -844,15 +867,19 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
           rc = dn_gemm(c, c->tparams, gX, gY, h.n_list, h.list, c->dn_C, gW, pti, ps, ps, cs, cs);  // g′ = Pθ′ and w′ = (M⁻¹P)θ′, one launch
           if (rc) return bail(rc);
         } else if (wt) {
-          rc = dn_wide_target(c, h.list, h.n_list, gX, gY, pti, ps, cs);  // (ℓπ sanitised in the kernel; a wide context has no dense metric)
+          rc = dn_wide_target(c, h.list, h.n_list, gX, gY, pti, ps, cs);  // (ℓπ sanitised in the kernel)
           if (rc) return bail(rc);
+          if (dm) {  // (the rank-update metric: a wide context has no dense one)
+            rc = dn_minv_apply(c, (const T*)gY, gW, h.n_list, h.list, pti, ps, ps, cs, cs);
+            if (rc) return bail(rc);
+          }
         } else {
           // (a target that is not the dense Gaussian reads θ′ from / leaves g′ in the context's arrays: the pool is "staged")
           rc = dt ? dn_gemm(c, c->tparams, gX, gY, h.n_list, h.list, (const T*)nullptr, (T*)nullptr, pti, ps, ps, cs, cs) : dn_other_target(c, h.list, h.n_list, /*sanitize_lp=*/!pool);  // (the pool kernel sanitises ℓπ itself: one launch fewer per global step)
           if (rc) return bail(rc);
           if (dm) {
-            rc = dt ? dn_gemm(c, c->dn_minv, (const T*)gY, gW, h.n_list, h.list, (const T*)nullptr, (T*)nullptr, pti, ps, ps, cs, cs)
-                    : dn_gemm(c, c->dn_minv, (const T*)c->g, gW, h.n_list, h.list, (const T*)nullptr, (T*)nullptr, pti, (int64_t)0, ps, (int64_t)0, cs);
+            rc = dt ? dn_minv_apply(c, (const T*)gY, gW, h.n_list, h.list, pti, ps, ps, cs, cs)
+                    : dn_minv_apply(c, (const T*)c->g, gW, h.n_list, h.list, pti, (int64_t)0, ps, (int64_t)0, cs);
             if (rc) return bail(rc);
           }
         }

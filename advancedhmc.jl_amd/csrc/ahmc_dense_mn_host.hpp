@@ -7,7 +7,7 @@
 // first half of a leapfrog of every chain (k_d_pre; chains with es = 0 do not move)
 template <class T>
 int dn_pre_all(Ctx<T>* c) {
-  const bool dm = c->metric_kind == AHMC_METRIC_DENSE;
+  const bool dm = dn_recurrent(c);
   T* V = c->dn_W + (size_t)DS_CUR_V * c->D * c->N;
   T* W = dm ? c->dn_W + (size_t)DS_CUR_W * c->D * c->N : nullptr;
   const T* minv = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
@@ -17,15 +17,15 @@ int dn_pre_all(Ctx<T>* c) {
   return AHMC_OK;
 }
 // second half once g′ (and, unless dense_target, ℓπ) of the new positions are in place: w′ = M⁻¹g′ for the dense
-// metric, then k_d_post
+// or rank-update metric, then k_d_post
 template <class T>
 int dn_post_all(Ctx<T>* c, bool dense_target) {
-  const bool dm = c->metric_kind == AHMC_METRIC_DENSE;
+  const bool dm = dn_recurrent(c);
   T* V = c->dn_W + (size_t)DS_CUR_V * c->D * c->N;
   T* W = dm ? c->dn_W + (size_t)DS_CUR_W * c->D * c->N : nullptr;
   const T* minv = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
   if (dm) {
-    int rc = dn_gemm(c, c->dn_minv, c->g, W, c->N);
+    int rc = dn_minv_apply(c, c->g, W, c->N);
     if (rc) return rc;
   }
   hipLaunchKernelGGL((k_d_post<T>), dim3(dn_grid_chains(c)), dim3(256), 0, c->stream, c->th, c->r, c->g, V, W, minv, c->minv_per_chain ? 1 : 0, c->dn_es,

@@ -240,11 +240,11 @@ int ext_advance(Ctx<T>* c, const void* lp_in, const void* g_in) {
   };
   int rc = AHMC_OK;
   if (x.mode == EXT_NUTS) {
-    const bool dm = c->metric_kind == AHMC_METRIC_DENSE;
+    const bool dm = dn_recurrent(c);
     const T* minv_d = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
     T* Wcur = dm ? c->dn_W + (size_t)DS_CUR_W * c->D * c->N : nullptr;
     if (dm) {
-      rc = dn_gemm(c, c->dn_minv, c->g, Wcur, x.n_list, x.list);  // w′ = M⁻¹g′
+      rc = dn_minv_apply(c, c->g, Wcur, x.n_list, x.list);  // w′ = M⁻¹g′
       if (rc) { finish(); return rc; }
     }
     KP<T> p = ext_kp(c);

@@ -510,5 +510,6 @@ function AdvancedHMC.EBFMI(z::MI355XChains{T}) where {T}
 end
 
 include("AdvancedHMCMI355XDiag.jl")  # summarystats_device: include/ahmc_diag.h
+include("AdvancedHMCMI355XRankUpdate.jl")  # set_metric!(z, ::RankUpdateEuclideanMetric): include/ahmc_rank_update.h
 
 end # module
