@@ -980,15 +980,12 @@ int set_metric(Ctx<T>* c, int kind, const T* minv, int64_t n) {
   }
   if (kind == AHMC_METRIC_DENSE) {
     if (n != D * D) return fail(c, AHMC_ERR_ARGUMENT, "AxesMismatch: dense M⁻¹ must have D*D elements");
-    c->metric_kind = kind;
-    c->metric_per_chain = false;
-    c->minv.assign(minv, minv + n);
-    // upper Cholesky factor U, UᵀU = M⁻¹
-    std::vector<T>& U = c->chol;
-    U.assign(D * D, T(0));
+    // upper Cholesky factor U, UᵀU = M⁻¹.  DenseEuclideanMetric(M⁻¹) throws BEFORE the Hamiltonian is replaced (src/metric.jl:104-109,
+    // src/sampler.jl:3-12): a matrix that does not factorise leaves the context's metric as it was
+    std::vector<T> U(D * D, T(0));
     for (int64_t j = 0; j < D; ++j) {
       for (int64_t i = 0; i <= j; ++i) {
-        T s = c->minv[i + j * D];
+        T s = minv[i + j * D];
         for (int64_t k = 0; k < i; ++k) s -= U[k + i * D] * U[k + j * D];
         if (i == j) {
           if (!(s > 0)) return fail(c, AHMC_ERR_ARGUMENT, "PosDefException: M⁻¹ is not positive definite");
@@ -998,6 +995,10 @@ int set_metric(Ctx<T>* c, int kind, const T* minv, int64_t n) {
         }
       }
     }
+    c->metric_kind = kind;
+    c->metric_per_chain = false;
+    c->minv.assign(minv, minv + n);
+    c->chol.swap(U);
     return AHMC_OK;
   }
   return fail(c, AHMC_ERR_ARGUMENT, "set_metric: unknown metric kind");

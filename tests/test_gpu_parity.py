@@ -506,7 +506,9 @@ def test_dense_two_pipelines_equal_one(hip, rng, monkeypatch):
 def test_dense_covariance_adaptation(hip, oracle, rng):
     """WelfordCov behind the shared DenseEuclideanMetric (src/adaptation/massmatrix.jl:283-340): batch (Chan) update on
     the MFMA units == the oracle pushing the chains one after another, on identical (θ, α); then NUTS + StanHMCAdaptor
-    end to end: the adapted M⁻¹ approaches the target covariance and the trees get shorter"""
+    end to end: the adapted M⁻¹ approaches the target covariance and the trees get shorter.
+    (One partly filled k_dsyrk tile, Float64, N a multiple of 16, two differently rounded algorithms against each other: the estimate against
+    an EXACT covariance at every tile shape, K-loop tail and element type, and what an update leaves behind, is tests/test_dense_adaptation.py.)"""
     D, N = 12, 96
     L = np.linalg.cholesky(_spd(D, rng, 6.0))
     h = A.Hamiltonian(A.DenseEuclideanMetric(np.eye(D)), A.IsoGaussian(D))

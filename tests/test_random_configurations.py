@@ -525,7 +525,8 @@ def test_random_fused_warmup_equals_stepwise(hip, i):
     a run that ends inside the warm-up or some draws after it: bit for bit"""
     c = draw_case(i)
     if refused(c) or c["metric"] == "dense" or (not c["nuts"] and c["static"] == "time" and c["N"] > 1):
-        pytest.skip("refused configuration / DenseEuclideanMetric adapts through WelfordCov on its own path (test_dense_covariance_adaptation) / "
+        pytest.skip("refused configuration / DenseEuclideanMetric adapts through WelfordCov on its own path (test_dense_covariance_adaptation; run() against transition + adapt "
+                    "with a dense adaptor: tests/test_dense_adaptation.py) / "
                     "per-chain adapted step sizes + FixedIntegrationTime (Q6)")
     rng = np.random.default_rng(c["seed"] + 1)
     h, lf, kernel = build(c, np.random.default_rng(c["seed"]))
@@ -671,7 +672,8 @@ def test_random_sharding_invariance(hip, i):
     sizes, the metric and the start points, each adapting on its own): warm-up + draws, bit for bit the same chains"""
     c = draw_case(i)
     if refused(c) or c["N"] < 3 or c["metric"] == "dense" or (not c["nuts"] and c["static"] == "time"):
-        pytest.skip("refused configuration / fewer than three chains / one shared dense M⁻¹ adapts from ALL chains (pooled: test_v3_state_gather) / Q6")
+        pytest.skip("refused configuration / fewer than three chains / one shared dense M⁻¹ adapts from ALL chains (pooled: test_v3_state_gather; the dense "
+                    "estimate itself: tests/test_dense_adaptation.py) / Q6")
     rng = np.random.default_rng(c["seed"])
     D, N, dtype = c["D"], c["N"], c["dtype"]
     h, lf, kernel = build(c, rng)
