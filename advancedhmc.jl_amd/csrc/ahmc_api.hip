@@ -227,13 +227,10 @@ struct Ctx : CtxBase {
   int dn_last_pipelines = 0, dn_last_pool = 0;
   int* dn_active = nullptr;
   int* dn_list = nullptr;
-  size_t dn_slots = 0, dn_batch_elems = 0;
+  size_t dn_batch_elems = 0;
   int64_t dn_global_steps = 0, dn_chain_steps = 0;
   hipStream_t stream2 = nullptr;  // second pipeline of the dense NUTS loop (dn_nuts_transition)
-  hipStream_t stream_x[2] = {nullptr, nullptr};  // third / fourth pipeline (AHMC_DENSE_PIPES)
-  hipEvent_t ev_join_x[2] = {nullptr, nullptr};
   hipEvent_t ev_split = nullptr, ev_join = nullptr;
-  hipEvent_t ev_gemm[2] = {nullptr, nullptr}, ev_tree[2] = {nullptr, nullptr};  // AHMC_DENSE_SPLIT=2: GEMM stream <-> tree stream hand-over per chain half
   // WelfordCov of the shared dense metric: μ (D) [+ batch mean + column-sum partials], M, batch scatter, estimate
   T *wc_mu = nullptr, *wc_M = nullptr, *wc_S = nullptr, *wc_cov = nullptr;
   // RankUpdateEuclideanMetric (ahmc_rank_update_host.hpp): one slab of A, 1/√A, B, Dm, Y, Tw, V⁻¹ at ru_off[0..6]
@@ -271,11 +268,7 @@ struct Ctx : CtxBase {
     if (znorm2) (void)hipFree(znorm2);
     if (compat_save) (void)hipFree(compat_save);
     if (compat_flag) (void)hipFree(compat_flag);
-    for (int k = 0; k < 2; ++k) {
-      if (stream_x[k]) { (void)hipStreamSynchronize(stream_x[k]); (void)hipStreamDestroy(stream_x[k]); }
-      if (ev_join_x[k]) (void)hipEventDestroy(ev_join_x[k]);
-    }
-    for (hipEvent_t e : {ev_split, ev_join, ev_gemm[0], ev_gemm[1], ev_tree[0], ev_tree[1]})
+    for (hipEvent_t e : {ev_split, ev_join})
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {stage_ready[0], stage_ready[1], stage_free[0], stage_free[1]})
       if (e) (void)hipEventDestroy(e);
@@ -436,7 +429,7 @@ int launch_fill_caches(Ctx<T>* c) {
 template <class T>
 int launch_kinetic(Ctx<T>* c) {
   if (dense_engine(c)) {
-    int rc = dn_ensure(c, 2);
+    int rc = dn_ensure(c);
     return rc ? rc : dn_velocity(c);
   }
   KP<T> p = make_kp(c);
@@ -2165,8 +2158,7 @@ static int32_t sample_from_impl(ahmc_ctx* ctx, const ahmc_kernel_cfg* cfg, int64
         i += k;
         continue;
       }
-      const int dense_pool_env = getenv("AHMC_DENSE_POOL") ? atoi(getenv("AHMC_DENSE_POOL")) : 1;  // (per call, as dn_nuts_transition reads it)
-      if (adapting && fused_adapt && dense_pool_env != 0 && cfg->nuts && dense_engine(c) && c->adapt_kind == AHMC_ADAPT_STEPSIZE &&
+      if (adapting && fused_adapt && cfg->nuts && dense_engine(c) && c->adapt_kind == AHMC_ADAPT_STEPSIZE &&
           (cfg->sampler == AHMC_TS_MULTINOMIAL || cfg->sampler == AHMC_TS_SLICE) &&
           cfg->refresh_alpha == 0 && c->target_kind != AHMC_TARGET_EXTERNAL &&
           (!so || !keep || so_on_device)) {

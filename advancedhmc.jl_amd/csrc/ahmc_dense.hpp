@@ -7,9 +7,9 @@
 // the whole tree state of every chain in HBM and advances ALL chains by one leapfrog per "global
 // step":
 //     r −= ϵ/2 g → V = M⁻¹R (MFMA) → θ += ϵV → (ℓπ, g) (MFMA for the dense target) → r −= ϵ/2 g
-//     → V = M⁻¹R, ℓκ = −½ r·v (MFMA) → k_d_tree: one NUTS leaf + its merges per chain
-// k_d_tree is the iterative build_tree of ahmc_nuts.hpp turned into a resumable state machine (one
-// wave per chain, state in DChain + vector slots).  Chains run asynchronously through a batch of
+//     → V = M⁻¹R, ℓκ = −½ r·v (MFMA) → k_d_tree2: one NUTS leaf + its merges per chain
+// k_d_tree2 is the iterative build_tree of ahmc_nuts.hpp turned into a resumable state machine (one
+// workgroup per chain, state in DChain2 + a per-chain point pool).  Chains run asynchronously through a batch of
 // transitions: a chain that ends a transition starts its next one in the same call (its fresh
 // momentum r = U⁻¹z and v = M⁻¹r were produced for the whole batch by two GEMMs up front), so the
 // only idle time is at the end of the batch.
@@ -341,32 +341,25 @@ __global__ __launch_bounds__(256) void k_d_freeze(const T* __restrict__ lp, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// Per-chain tree state of the dense engine
+// Per-chain state of the dense engine
 // ------------------------------------------------------------------------------------------------
 constexpr int DN_MAXLEV = 16;  // pending levels = max_depth − 1
 enum { DPH_IDLE = 0, DPH_START = 1, DPH_RUN = 2, DPH_WARM = 3 };  // WARM: one motionless step that computes W = M⁻¹g at the start point
-// vector slots: T[slot][N][D]
+// vector slots of static HMC, its MultinomialTS and find_good_stepsize: T[slot][N][D]
 enum {
-  DS_CUR_V = 0, DS_CUR_W,  // v = M⁻¹r and w = M⁻¹g of the moving edge (w: dense metric only)
+  DS_CUR_V = 0, DS_CUR_W,  // v = M⁻¹r and w = M⁻¹g of the moving point (w: dense / rank-update metric only)
   DS_OTH_W,
-  DS_OTH_TH, DS_OTH_R, DS_OTH_G, DS_OTH_V,
-  DS_TREE_RHO,
-  DS_CAND_TH, DS_CAND_R, DS_CAND_G,
-  DS_SUB_RHO,
-  DS_START_TH, DS_START_R, DS_START_G,  // static HMC: the start point (for rejected proposals)
-  DS_FIXED,
-  DS_PER_LEVEL = 5  // ρ, v_first, candidate θ, r, g
+  DS_OTH_TH, DS_OTH_R, DS_OTH_G, DS_OTH_V,  // find_good_stepsize: z0
+  DS_START_TH, DS_START_R, DS_START_G,      // the start point (rejected proposals, the multinomial passes, the caller's point)
+  DS_FIXED
 };
 
+// the scalars of a chain for static HMC (k_d_hmc_*, ahmc_dense_mn.hpp) and find_good_stepsize (k_d_fe_*); the NUTS loop has DChain2
 template <class T>
 struct DChain {
-  T H0, eps, w_tree, sa_tree, dh_tree, lu;
-  T cand_lp, cand_lk, sub_lp, sub_lk;  // energies of the tree-level / current-subtree candidates
-  T w_c, sa_c, dh_c;
-  T pw[DN_MAXLEV], psa[DN_MAXLEV], pdh[DN_MAXLEV], plp[DN_MAXLEV], plk[DN_MAXLEV];
-  int32_t pna[DN_MAXLEV];
-  int32_t phase, it, jw, leaf, v, cur_is_left, na_tree, na_c, depth, numerical;
-  uint32_t k;  // sequential draws consumed in this transition
+  T H0, eps, w_tree, sa_tree, lu;
+  T cand_lp, cand_lk, sub_lp, sub_lk;  // energies of the start point / of z0
+  int32_t phase, it, v, na_tree, na_c;
 };
 
 template <class T>
@@ -383,16 +376,6 @@ struct DP {  // dense-engine arguments (beside KP)
   int dense_metric;
 };
 
-// stream compaction of the running chains: out = { c in in[0..n) : phase(c) != idle }
-template <class T>
-__global__ __launch_bounds__(256) void k_d_compact(const DChain<T>* __restrict__ S, const int* __restrict__ in, int64_t n, int* __restrict__ out,
-                                                   int* __restrict__ count) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const int c = in ? in[j] : (int)j;
-  if (S[c].phase != DPH_IDLE) out[atomicAdd(count, 1)] = c;
-}
-
 template <class T>
 __global__ __launch_bounds__(256) void k_d_iota(int* __restrict__ out, int start, int64_t n) {  // out[j] = start + j
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -408,10 +391,6 @@ __device__ __forceinline__ void vcopy(T* __restrict__ dst, const T* __restrict__
   for (int d = lane; d < D; d += 64) dst[d] = src[d];
 }
 
-// One call = for every chain that is running: account for the leapfrog that has just completed
-// (leaf, merges, end of subtree, end of doubling, end of transition, start of the next transition)
-// and publish the signed step of its next leapfrog.  MultinomialTS / SliceTS with
-// GeneralisedNoUTurn; log-domain weights as the reference (src/trajectory.jl:144-206,626-742).
 // Threads per chain in the tree kernel (template parameter DT).  Measured on cfg4 (D = 512): 128 -> 2.21e7, 256 -> 2.25e7,
 // 512 -> 2.14e7 leapfrog/s (one wave per chain: 2.01e7).  Round 2: the thread count follows D — a chain of D <= 128 gets
 // ONE wave (the workgroup barriers become wave-local, no idle waves), D <= 256 two: the step-synchronous engine also
@@ -424,7 +403,7 @@ inline int dt_threads_for(int64_t D) {
   // round 3, cfg4 (D = 512, two pipelines, point-pool kernel), whole loop: 256 threads 2.54e7, 128 threads 2.67e7, 64 threads 2.55e7
   return D <= 128 ? 64 : (D <= 512 ? 128 : DT_THREADS);
 }
-// all-reduce of a pair over the DT_THREADS threads of the workgroup (every decision of d_tree_advance is taken on
+// all-reduce of a pair over the DT_THREADS threads of the workgroup (every decision of d_tree_advance2 is taken on
 // such sums or on per-chain scalars, so all threads follow the same control flow and reach the barriers together)
 template <int DT, class T>
 __device__ __forceinline__ void block_allsum2(T& a, T& b) {
@@ -472,582 +451,12 @@ __device__ __forceinline__ void dn_vec_pass(int lane, const T* const (&src)[NV],
   }
 }
 
-// Returns the signed step of the chain's next leapfrog (0 = motionless step or idle).  lp_in / lk_in: ℓπ, ℓκ of the
-// point the leapfrog that has just completed arrived at (registers, uniform across the wave).
-// CRIT: the termination criterion (AHMC_TC_*).  1 = GeneralisedNoUTurn (:566-570), the default and the only one the
-// kernel k_d_tree is built for; 0 = ClassicNoUTurn (:551-557): the "ρ" slots hold θ of the first-built leaf instead
-// of a momentum sum; 2 = StrictGeneralisedNoUTurn (:579-617): three more vectors per pending level (r of the
-// first-built leaf, r and v of the last-built one) and r, v of the edge the current subtree grows from.
-template <int CRIT>
-struct DLevel {
-  static constexpr int STRIDE = CRIT == 2 ? DS_PER_LEVEL + 3 : DS_PER_LEVEL;  // vector slots per pending level
-};
-template <class T, int CRIT = 1, int DT = DT_THREADS>
-__device__ __forceinline__ T d_tree_advance(const KP<T>& p, const DP<T>& q, int64_t c, int lane /* thread of the chain's workgroup, 0 .. DT-1 */, T lp_in, T lk_in) {
-  constexpr int DT_THREADS = DT;  // (shadows the default: every loop below strides by the workgroup's size)
-  constexpr int LS = DLevel<CRIT>::STRIDE;
-  DChain<T>& S = q.S[c];
-  const int D = p.D;
-  const bool slice = p.sampler == 2;
-  T* th = p.th() + c * D;
-  T* r = p.r() + c * D;
-  T* g = p.g() + c * D;
-  T* V = dslot(q, p, DS_CUR_V, c);
-  Rng rng = make_rng(p, c);
-  DrawStream ds;
-  auto resume_draws = [&](uint32_t it, uint32_t k) {
-    rng.iter = p.iteration + it;
-    ds.resume(rng, k);
-  };
-  // scalars are uniform across the wave: every lane computes them; lane 0 writes them back
-  int phase = S.phase, it = S.it;
-  if (phase == DPH_WARM) {
-    // the motionless step has produced W = M⁻¹g at the start point: remember it for the other edge
-    // too and let the first leapfrog go
-    const T* Wc = dslot(q, p, DS_CUR_W, c);
-    T* o_w = dslot(q, p, DS_OTH_W, c);
-    for (int d = lane; d < D; d += DT_THREADS) o_w[d] = Wc[d];
-    const T e_first = S.v < 0 ? -S.eps : S.eps;
-    __syncthreads();  // (every thread has read the phase before thread 0 changes it)
-    if (lane == 0) S.phase = DPH_RUN;
-    return e_first;
-  }
-  bool start = phase == DPH_START;
-  T lp_start = lp_in;  // ℓπ(θ) of the point the next transition starts from
-  if (!start) {
-    resume_draws((uint32_t)it, S.k);
-    const T H0 = S.H0, eps = S.eps;
-    const int v = S.v, jw = S.jw;
-    int leaf = S.leaf;
-    const uint32_t nleaf = 1u << jw;
-    const T lp = lp_in, lk = lk_in;
-    // ---- leaf (:638-647) ----
-    const T ne = lp + lk;
-    const T dH = -ne - H0;
-    T sa_c = exp(jl_min(T(0), -dH)), dh_c = dH, w_c;
-    int na_c = 1;
-    bool sub_term;
-    if (slice) {
-      w_c = (S.lu <= ne) ? T(1) : T(0);
-      sub_term = !(S.lu < p.delta_max + ne);
-    } else {
-      w_c = H0 + ne;
-      sub_term = !(-H0 < p.delta_max + ne);
-    }
-    bool numerical = S.numerical != 0 || sub_term;
-    const int cur_is_left_in = S.cur_is_left;
-    // every thread has now read the chain's scalars of this call: only from here on may thread 0 update them
-    // (an odd leaf parks without any reduction, i.e. without any other barrier in between)
-    __syncthreads();
-    // The subtree being assembled lives only inside this call, so its vectors are VIEWS: a fresh leaf's
-    // ρ, v_first and candidate are the moving edge itself; after a merge ρ is in the SUB_RHO slot and
-    // v_first / the candidate may point into a pending level.  Data is copied only when it must
-    // outlive the call (park, tree-level candidate).
-    T* s_rho = dslot(q, p, DS_SUB_RHO, c);
-    const T* rho_v = CRIT == 0 ? th : r;  // Classic: θ of the subtree's first-built leaf
-    const T* vf_v = V;
-    const T* rf_v = r;  // Strict: r of the subtree's first-built leaf
-    const T *cth_v = th, *cr_v = r, *cg_v = g;
-    T sub_lp = lp, sub_lk = lk;
-    // ---- merges: one per trailing zero bit of `leaf` (:649-673) ----
-    const int nm = __builtin_ctz((uint32_t)leaf);
-    int merged = 0;
-    for (int lvl = 0; lvl < nm && !sub_term; ++lvl) {
-      T* p_rho = dslot(q, p, DS_FIXED + LS * lvl + 0, c);
-      T* p_vf = dslot(q, p, DS_FIXED + LS * lvl + 1, c);
-      const T w_p = S.pw[lvl];
-      bool keep_first;
-      T w_new;
-      if (slice) {
-        w_new = w_p + w_c;
-        keep_first = w_new * (T)ds.uniform() < w_p;
-      } else {
-        w_new = logaddexp(w_p, w_c);
-        keep_first = w_new < w_p + (T)ds.randexp();
-      }
-      if (keep_first) {
-        cth_v = dslot(q, p, DS_FIXED + LS * lvl + 2, c);
-        cr_v = dslot(q, p, DS_FIXED + LS * lvl + 3, c);
-        cg_v = dslot(q, p, DS_FIXED + LS * lvl + 4, c);
-        sub_lp = S.plp[lvl];
-        sub_lk = S.plk[lvl];
-      }
-      w_c = w_new;
-      sa_c = S.psa[lvl] + sa_c;
-      na_c = S.pna[lvl] + na_c;
-      const T dh_p = S.pdh[lvl];
-      dh_c = v > 0 ? maxabs(dh_p, dh_c) : maxabs(dh_c, dh_p);
-      if constexpr (CRIT == 1) {
-        // ρ = ρ_first + ρ_second; generalised_uturn_criterion with v = M⁻¹r at the two ends (:566-570,619-621)
-        T dots[2] = {0, 0};
-        for (int d = lane; d < D; d += DT_THREADS) {
-          const T rho = p_rho[d] + rho_v[d];
-          dots[0] += rho * p_vf[d];
-          dots[1] += rho * V[d];
-          s_rho[d] = rho;
-        }
-        rho_v = s_rho;
-        vf_v = p_vf;
-        block_allsum2<DT>(dots[0], dots[1]);
-        sub_term = (dots[0] <= 0) || (dots[1] <= 0);
-      } else if constexpr (CRIT == 0) {
-        // ClassicNoUTurn (:551-557): ends = the pending half's first-built leaf (θ in the ρ slot, v_first) and the
-        // current leaf; Δθ = θ_right − θ_left; terminated if Δθ·M⁻¹(−r_left) >= 0 or −Δθ·M⁻¹r_right >= 0
-        T dots[2] = {0, 0};
-        for (int d = lane; d < D; d += DT_THREADS) {
-          const T thl = v > 0 ? p_rho[d] : th[d], thr = v > 0 ? th[d] : p_rho[d];
-          const T vl = v > 0 ? p_vf[d] : V[d], vr = v > 0 ? V[d] : p_vf[d];
-          const T dth = thr - thl;
-          dots[0] += dth * (-vl);
-          dots[1] += (-dth) * vr;
-        }
-        rho_v = p_rho;  // the merged subtree's first-built leaf is the pending half's
-        vf_v = p_vf;
-        block_allsum2<DT>(dots[0], dots[1]);
-        sub_term = (dots[0] >= 0) || (dots[1] >= 0);
-      } else {
-        // StrictGeneralisedNoUTurn (:579-617).  F = the pending (first-built) half, S = the half just completed:
-        //   (ρ_F + ρ_S ; ends F.first, S.last)   (ρ_F + r_S.first ; ends F.first, S.first)   (r_F.last + ρ_S ; ends F.last, S.last)
-        const T* p_rf = dslot(q, p, DS_FIXED + LS * lvl + 5, c);
-        const T* p_rl = dslot(q, p, DS_FIXED + LS * lvl + 6, c);
-        const T* p_vl = dslot(q, p, DS_FIXED + LS * lvl + 7, c);
-        T dots[6] = {0, 0, 0, 0, 0, 0};
-        for (int d = lane; d < D; d += DT_THREADS) {
-          const T rho = p_rho[d] + rho_v[d];
-          const T rho2 = p_rho[d] + rf_v[d];
-          const T rho3 = p_rl[d] + rho_v[d];
-          dots[0] += rho * p_vf[d];
-          dots[1] += rho * V[d];
-          dots[2] += rho2 * p_vf[d];
-          dots[3] += rho2 * vf_v[d];
-          dots[4] += rho3 * p_vl[d];
-          dots[5] += rho3 * V[d];
-          s_rho[d] = rho;
-        }
-        rho_v = s_rho;
-        vf_v = p_vf;
-        rf_v = p_rf;
-        block_allsum2<DT>(dots[0], dots[1]);
-        block_allsum2<DT>(dots[2], dots[3]);
-        block_allsum2<DT>(dots[4], dots[5]);
-        sub_term = (dots[0] <= 0) || (dots[1] <= 0) || (dots[2] <= 0) || (dots[3] <= 0) || (dots[4] <= 0) || (dots[5] <= 0);
-      }
-      merged = lvl + 1;
-    }
-    bool subtree_over = true;
-    if (sub_term) {
-      // enclosing unfinished subtrees still absorb the statistics of their first halves (:666)
-      const uint32_t pend = (((uint32_t)leaf - 1u) >> merged) << merged;
-      for (int qq = merged; (pend >> qq) != 0u; ++qq) {
-        if ((pend >> qq) & 1u) {
-          sa_c = S.psa[qq] + sa_c;
-          na_c = S.pna[qq] + na_c;
-          const T dh_p = S.pdh[qq];
-          dh_c = v > 0 ? maxabs(dh_p, dh_c) : maxabs(dh_c, dh_p);
-        }
-      }
-    } else if ((uint32_t)leaf < nleaf) {
-      // park the finished level-nm subtree until its sibling is built
-      T* p_rho = dslot(q, p, DS_FIXED + LS * nm + 0, c);
-      T* p_vf = dslot(q, p, DS_FIXED + LS * nm + 1, c);
-      T* p_cth = dslot(q, p, DS_FIXED + LS * nm + 2, c);
-      T* p_cr = dslot(q, p, DS_FIXED + LS * nm + 3, c);
-      T* p_cg = dslot(q, p, DS_FIXED + LS * nm + 4, c);
-      for (int d = lane; d < D; d += DT_THREADS) {
-        p_rho[d] = rho_v[d];
-        p_vf[d] = vf_v[d];
-        p_cth[d] = cth_v[d];
-        p_cr[d] = cr_v[d];
-        p_cg[d] = cg_v[d];
-      }
-      if constexpr (CRIT == 2) {  // r of the first-built leaf, r and v of the last-built one (the current leaf)
-        T* p_rf = dslot(q, p, DS_FIXED + LS * nm + 5, c);
-        T* p_rl = dslot(q, p, DS_FIXED + LS * nm + 6, c);
-        T* p_vl = dslot(q, p, DS_FIXED + LS * nm + 7, c);
-        for (int d = lane; d < D; d += DT_THREADS) {
-          p_rf[d] = rf_v[d];
-          p_rl[d] = r[d];
-          p_vl[d] = V[d];
-        }
-      }
-      if (lane == 0) {
-        S.pw[nm] = w_c;
-        S.psa[nm] = sa_c;
-        S.pdh[nm] = dh_c;
-        S.pna[nm] = na_c;
-        S.plp[nm] = sub_lp;
-        S.plk[nm] = sub_lk;
-        S.leaf = leaf + 1;
-        S.numerical = numerical ? 1 : 0;
-        S.k = ds.k;
-      }
-      subtree_over = false;  // next leapfrog: same edge, same direction (es unchanged)
-    }
-    if (!subtree_over) return v > 0 ? eps : -eps;
-
-    // ---- top level of the doubling loop (:708-722) ----
-    T w_tree = S.w_tree, sa_tree = S.sa_tree, dh_tree = S.dh_tree;
-    int na_tree = S.na_tree, depth = S.depth;
-    T cand_lp = S.cand_lp, cand_lk = S.cand_lk;
-    if (!sub_term) {
-      ++depth;
-      bool acc;  // mh_accept(rng, sampler, sampler′): biased progressive sampling (:202-206)
-      if (slice) acc = w_tree * (T)ds.uniform() < w_c;
-      else acc = w_tree < w_c + (T)ds.randexp();
-      if (acc) {
-        T* c_th = dslot(q, p, DS_CAND_TH, c);
-        T* c_r = dslot(q, p, DS_CAND_R, c);
-        T* c_g = dslot(q, p, DS_CAND_G, c);
-        for (int d = lane; d < D; d += DT_THREADS) {
-          c_th[d] = cth_v[d];
-          c_r[d] = cr_v[d];
-          c_g[d] = cg_v[d];
-        }
-        cand_lp = sub_lp;
-        cand_lk = sub_lk;
-      }
-    }
-    sa_tree = sa_tree + sa_c;
-    na_tree = na_tree + na_c;
-    dh_tree = v < 0 ? maxabs(dh_c, dh_tree) : maxabs(dh_tree, dh_c);
-    w_tree = slice ? w_tree + w_c : logaddexp(w_tree, w_c);
-    // isterminated on the whole tree; its edges are `cur` and the dormant one
-    bool turn;
-    if constexpr (CRIT == 1) {
-      T* t_rho = dslot(q, p, DS_TREE_RHO, c);
-      const T* o_v = dslot(q, p, DS_OTH_V, c);
-      T dots[2] = {0, 0};
-      for (int d = lane; d < D; d += DT_THREADS) {
-        const T rho = t_rho[d] + rho_v[d];
-        dots[0] += rho * V[d];
-        dots[1] += rho * o_v[d];
-        t_rho[d] = rho;
-      }
-      block_allsum2<DT>(dots[0], dots[1]);
-      turn = (dots[0] <= 0) || (dots[1] <= 0);
-    } else if constexpr (CRIT == 0) {
-      const T* o_th = dslot(q, p, DS_OTH_TH, c);
-      const T* o_v = dslot(q, p, DS_OTH_V, c);
-      const bool cl = cur_is_left_in != 0;
-      T dots[2] = {0, 0};
-      for (int d = lane; d < D; d += DT_THREADS) {
-        const T thl = cl ? th[d] : o_th[d], thr = cl ? o_th[d] : th[d];
-        const T vl = cl ? V[d] : o_v[d], vr = cl ? o_v[d] : V[d];
-        const T dth = thr - thl;
-        dots[0] += dth * (-vl);
-        dots[1] += (-dth) * vr;
-      }
-      block_allsum2<DT>(dots[0], dots[1]);
-      turn = (dots[0] >= 0) || (dots[1] >= 0);
-    } else {
-      // strict at the top: (ρ_tree + ρ_sub ; ends current edge, other edge), (ρ_tree + r_sub.first ; ends other edge,
-      // sub.first) and (r_start + ρ_sub ; ends start edge, current edge); start edge = the one the subtree grew from
-      T* t_rho = dslot(q, p, DS_TREE_RHO, c);
-      const T* o_v = dslot(q, p, DS_OTH_V, c);
-      const T* rs = dslot(q, p, DS_START_R, c);
-      const T* vs = dslot(q, p, DS_START_G, c);
-      T dots[6] = {0, 0, 0, 0, 0, 0};
-      for (int d = lane; d < D; d += DT_THREADS) {
-        const T rho = t_rho[d] + rho_v[d];
-        const T rho2 = t_rho[d] + rf_v[d];
-        const T rho3 = rs[d] + rho_v[d];
-        dots[0] += rho * V[d];
-        dots[1] += rho * o_v[d];
-        dots[2] += rho2 * o_v[d];
-        dots[3] += rho2 * vf_v[d];
-        dots[4] += rho3 * vs[d];
-        dots[5] += rho3 * V[d];
-        t_rho[d] = rho;
-      }
-      block_allsum2<DT>(dots[0], dots[1]);
-      block_allsum2<DT>(dots[2], dots[3]);
-      block_allsum2<DT>(dots[4], dots[5]);
-      turn = (dots[0] <= 0) || (dots[1] <= 0) || (dots[2] <= 0) || (dots[3] <= 0) || (dots[4] <= 0) || (dots[5] <= 0);
-    }
-    const bool done = sub_term || turn || (jw + 1 >= p.max_depth);
-    if (!done) {
-      // ---- next doubling: direction (:693), edge selection ----
-      const bool vleft = ds.boolean();
-      const bool cur_is_left = cur_is_left_in != 0;
-      if (vleft != cur_is_left) {  // continue from the other edge: swap the two edge points
-        T* o_th = dslot(q, p, DS_OTH_TH, c);
-        T* o_r = dslot(q, p, DS_OTH_R, c);
-        T* o_g = dslot(q, p, DS_OTH_G, c);
-        T* o_v = dslot(q, p, DS_OTH_V, c);
-        T* o_w = dslot(q, p, DS_OTH_W, c);
-        T* Wc = dslot(q, p, DS_CUR_W, c);
-        for (int d = lane; d < D; d += DT_THREADS) {
-          T t;
-          t = o_th[d]; o_th[d] = th[d]; th[d] = t;
-          t = o_r[d]; o_r[d] = r[d]; r[d] = t;
-          t = o_g[d]; o_g[d] = g[d]; g[d] = t;
-          t = o_v[d]; o_v[d] = V[d]; V[d] = t;
-          if (q.dense_metric) { t = o_w[d]; o_w[d] = Wc[d]; Wc[d] = t; }
-        }
-      }
-      if constexpr (CRIT == 2) {  // r, v of the edge the next subtree grows from (each thread re-reads its own elements)
-        T* rs = dslot(q, p, DS_START_R, c);
-        T* vs = dslot(q, p, DS_START_G, c);
-        for (int d = lane; d < D; d += DT_THREADS) {
-          rs[d] = r[d];
-          vs[d] = V[d];
-        }
-      }
-      if (lane == 0) {
-        S.w_tree = w_tree; S.sa_tree = sa_tree; S.dh_tree = dh_tree; S.na_tree = na_tree; S.depth = depth;
-        S.cand_lp = cand_lp; S.cand_lk = cand_lk;
-        S.numerical = numerical ? 1 : 0;
-        S.cur_is_left = vleft ? 1 : 0;
-        S.v = vleft ? -1 : 1;
-        S.jw = jw + 1;
-        S.leaf = 1;
-        S.k = ds.k;
-      }
-      return vleft ? -eps : eps;
-    }
-    // ---- Transition(zcand, stats) (:725-741) ----
-    {
-      const T* c_th = dslot(q, p, DS_CAND_TH, c);
-      const T* c_r = dslot(q, p, DS_CAND_R, c);
-      const T* c_g = dslot(q, p, DS_CAND_G, c);
-      T* s1 = p.acc_sum() + c * D;
-      T* s2 = p.acc_sumsq() + c * D;
-      T* so = p.samples_out ? p.samples_out + ((int64_t)it * p.N + c) * D : nullptr;
-      for (int d = lane; d < D; d += DT_THREADS) {
-        const T t = c_th[d];
-        th[d] = t;
-        r[d] = c_r[d];
-        g[d] = c_g[d];
-        if (p.accum) { s1[d] += t; s2[d] += t * t; }
-        if (so) so[d] = t;
-      }
-      if (lane == 0) {
-        const T H = -(cand_lp + cand_lk);
-        p.lp()[c] = cand_lp;
-        p.lk()[c] = cand_lk;
-        p.eps_cur()[c] = eps;
-        p.st_nsteps()[c] = na_tree;
-        p.st_accept()[c] = 1;
-        p.st_accrate()[c] = sa_tree / (T)na_tree;
-        p.st_logdens()[c] = cand_lp;
-        p.st_H()[c] = H;
-        p.st_Herr()[c] = H - H0;
-        p.st_maxHerr()[c] = dh_tree;
-        p.st_depth()[c] = depth;
-        p.st_numerr()[c] = numerical ? 1 : 0;
-        if (p.accum) {
-          p.acc_nsteps()[c] += na_tree;
-          p.acc_ndiv()[c] += numerical ? 1 : 0;
-          accumulate_energy(p, c, H);
-        }
-      }
-      ++it;
-      if (it >= q.n_trans) {
-        if (lane == 0) {
-          S.phase = DPH_IDLE;
-          S.it = it;
-          atomicSub(q.n_active, 1);
-        }
-        return T(0);
-      }
-      start = true;
-      lp_start = cand_lp;  // (lane 0 has just stored it; the other lanes must not re-read it)
-    }
-  }
-  // ---- start of transition `it` (src/sampler.jl:54-57, src/trajectory.jl:677-690): the state is the
-  // previous candidate (θ, g, ℓπ already in place); fresh momentum and v = M⁻¹r from the batch ----
-  {
-    resume_draws((uint32_t)it, 0u);
-    const T eps = chain_eps(p, rng, c);
-    const T* rb = q.RB + ((int64_t)it * p.N + c) * D;
-    const T* vb = q.VB + ((int64_t)it * p.N + c) * D;
-    T* o_th = dslot(q, p, DS_OTH_TH, c);
-    T* o_r = dslot(q, p, DS_OTH_R, c);
-    T* o_g = dslot(q, p, DS_OTH_G, c);
-    T* o_v = dslot(q, p, DS_OTH_V, c);
-    T* t_rho = dslot(q, p, DS_TREE_RHO, c);
-    T* c_th = dslot(q, p, DS_CAND_TH, c);
-    T* c_r = dslot(q, p, DS_CAND_R, c);
-    T* c_g = dslot(q, p, DS_CAND_G, c);
-    T dots[2] = {0, 0};
-    for (int d = lane; d < D; d += DT_THREADS) {
-      const T rd = rb[d], vd = vb[d], td = th[d], gd = g[d];
-      dots[0] += rd * vd;
-      r[d] = rd;
-      V[d] = vd;
-      o_th[d] = td; o_r[d] = rd; o_g[d] = gd; o_v[d] = vd;
-      t_rho[d] = rd;
-      c_th[d] = td; c_r[d] = rd; c_g[d] = gd;
-      if constexpr (CRIT == 2) {
-        dslot(q, p, DS_START_R, c)[d] = rd;
-        dslot(q, p, DS_START_G, c)[d] = vd;
-      }
-    }
-    block_allsum2<DT>(dots[0], dots[1]);
-    const T lp = lp_start;
-    const T lk = sanitize(-dots[0] / 2);
-    const T H0 = -(lp + lk);
-    T lu = 0, w_tree;
-    if (slice) {
-      lu = -H0 - (T)ds.randexp();  // SliceTS(rng, z0) (:144-145)
-      w_tree = 1;
-    } else {
-      w_tree = 0;  // MultinomialTS(rng, z0): ℓw = 0 (:155)
-    }
-    const bool vleft = ds.boolean();
-    if (lane == 0) {
-      p.lk()[c] = lk;
-      S.H0 = H0; S.eps = eps; S.lu = lu; S.w_tree = w_tree; S.sa_tree = 0; S.dh_tree = 0; S.na_tree = 0;
-      S.cand_lp = lp; S.cand_lk = lk;
-      S.depth = 0; S.numerical = 0; S.jw = 0; S.leaf = 1;
-      S.cur_is_left = vleft ? 1 : 0;
-      S.v = vleft ? -1 : 1;
-      S.k = ds.k;
-      S.it = it;
-      S.phase = q.dense_metric ? DPH_WARM : DPH_RUN;
-    }
-    return q.dense_metric ? T(0) : (vleft ? -eps : eps);
-  }
-}
-
-// One global step of the NUTS batch for every listed chain, fused (one wave per chain):
-//   second half of the leapfrog that the GEMMs have just served (k_d_post) → d_tree_advance → first half of the
-//   next leapfrog (k_d_pre).  `do_post` = 0 for the very first call of a batch (no leapfrog in flight yet).
-// One chain per workgroup of 256 threads (2 elements per thread at D = 512): the kernel is a chain of dependent
-// memory round trips, so more threads per chain = fewer trips (one wave per chain: 75 µs per call, this: see DESIGN).
-template <class T, int DT = DT_THREADS>
-__global__ __launch_bounds__(DT) void k_d_tree(KP<T> p, DP<T> q, const T* __restrict__ minv, int per_chain, int dense_target, int do_post) {
-  constexpr int DT_THREADS = DT;
-  const int lane = threadIdx.x;  // one chain per workgroup of DT threads
-  const int64_t j = blockIdx.x;
-  if (j >= q.n_list) return;
-  const int64_t c = q.list ? q.list[j] : j;
-  if (q.S[c].phase == DPH_IDLE) return;
-  const int D = p.D;
-  T* th = p.th() + c * D;
-  T* r = p.r() + c * D;
-  T* g = p.g() + c * D;
-  T* V = dslot(q, p, DS_CUR_V, c);
-  T* W = q.dense_metric ? dslot(q, p, DS_CUR_W, c) : nullptr;
-  T lp = p.lp()[c], lk = p.lk()[c];
-  if (do_post) {
-    const T e = q.es[c];
-    T s[2] = {0, 0};
-    for (int d = lane; d < D; d += DT_THREADS) {
-      const T gd = g[d];
-      T rn = r[d], vn;
-      if (e != T(0)) rn = rn - e / 2 * gd;
-      if (W) vn = e != T(0) ? V[d] - e / 2 * W[d] : V[d];
-      else vn = minv ? minv[per_chain ? c * D + d : d] * rn : rn;
-      if (e != T(0) || !W) { r[d] = rn; V[d] = vn; }
-      s[0] += rn * vn;
-      s[1] += th[d] * gd;
-    }
-    block_allsum2<DT>(s[0], s[1]);
-    lk = sanitize(-s[0] / 2);
-    if (dense_target) lp = sanitize(-s[1] / 2);
-    if (lane == 0) {
-      p.lk()[c] = lk;
-      if (dense_target) p.lp()[c] = lp;
-    }
-  }
-  const T e = d_tree_advance<T, 1, DT>(p, q, c, lane, lp, lk);
-  if (lane == 0) q.es[c] = e;
-  if (e != T(0)) {  // first half of the next leapfrog (src/integrator.jl:231-237)
-    for (int d = lane; d < D; d += DT_THREADS) {
-      const T rh = r[d] - e / 2 * g[d];
-      const T vh = W ? V[d] - e / 2 * W[d] : (minv ? minv[per_chain ? c * D + d : d] * rh : rh);
-      r[d] = rh;
-      V[d] = vh;
-      th[d] = th[d] + e * vh;
-    }
-  }
-}
-
-// the same global step with ClassicNoUTurn (CRIT = 0) / StrictGeneralisedNoUTurn (CRIT = 2) and / or TemperedLeapfrog
-// (TEMPER): k_d_tree's body around d_tree_advance<T, CRIT> (kept as a second kernel so that the code of the default
-// one does not move).  A NUTS leaf is step(lf, h, z, 1): temper multiplies r by √α before the first half-step and
-// divides it by √α after the second (src/integrator.jl:198-209 with n_steps = 1); v = M⁻¹r goes with it.
-template <class T, int CRIT, bool TEMPER, int DT = DT_THREADS>
-__global__ __launch_bounds__(DT) void k_d_tree_crit(KP<T> p, DP<T> q, const T* __restrict__ minv, int per_chain, int dense_target, int do_post) {
-  constexpr int DT_THREADS = DT;
-  const int lane = threadIdx.x;  // one chain per workgroup of DT threads
-  const int64_t j = blockIdx.x;
-  if (j >= q.n_list) return;
-  const int64_t c = q.list ? q.list[j] : j;
-  if (q.S[c].phase == DPH_IDLE) return;
-  const int D = p.D;
-  T* th = p.th() + c * D;
-  T* r = p.r() + c * D;
-  T* g = p.g() + c * D;
-  T* V = dslot(q, p, DS_CUR_V, c);
-  T* W = q.dense_metric ? dslot(q, p, DS_CUR_W, c) : nullptr;
-  T lp = p.lp()[c], lk = p.lk()[c];
-  if (do_post) {
-    const T e = q.es[c];
-    T s[2] = {0, 0};
-    for (int d = lane; d < D; d += DT_THREADS) {
-      const T gd = g[d];
-      T rn = r[d], vn;
-      if (e != T(0)) rn = rn - e / 2 * gd;
-      if constexpr (TEMPER) {
-        if (e != T(0)) rn = rn / p.lf.sqrt_alpha;
-      }
-      if (W) {
-        vn = e != T(0) ? V[d] - e / 2 * W[d] : V[d];
-        if constexpr (TEMPER) {
-          if (e != T(0)) vn = vn / p.lf.sqrt_alpha;
-        }
-      } else {
-        vn = minv ? minv[per_chain ? c * D + d : d] * rn : rn;
-      }
-      if (e != T(0) || !W) { r[d] = rn; V[d] = vn; }
-      s[0] += rn * vn;
-      s[1] += th[d] * gd;
-    }
-    block_allsum2<DT>(s[0], s[1]);
-    lk = sanitize(-s[0] / 2);
-    if (dense_target) lp = sanitize(-s[1] / 2);
-    if (lane == 0) {
-      p.lk()[c] = lk;
-      if (dense_target) p.lp()[c] = lp;
-    }
-  }
-  const T e = d_tree_advance<T, CRIT, DT>(p, q, c, lane, lp, lk);
-  if (lane == 0) q.es[c] = e;
-  if (e != T(0)) {  // first half of the next leapfrog (src/integrator.jl:231-237)
-    for (int d = lane; d < D; d += DT_THREADS) {
-      T r0 = r[d], v0 = W ? V[d] : T(0);
-      if constexpr (TEMPER) {
-        r0 = r0 * p.lf.sqrt_alpha;
-        v0 = v0 * p.lf.sqrt_alpha;
-      }
-      const T rh = r0 - e / 2 * g[d];
-      const T vh = W ? v0 - e / 2 * W[d] : (minv ? minv[per_chain ? c * D + d : d] * rh : rh);
-      r[d] = rh;
-      V[d] = vh;
-      th[d] = th[d] + e * vh;
-    }
-  }
-}
-
-// reset the chain states for a batch of n_trans transitions
-template <class T>
-__global__ __launch_bounds__(256) void k_d_tree_reset(DChain<T>* S, T* es, int* n_active, int64_t N) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0) *n_active = (int)N;
-  if (c >= N) return;
-  S[c].phase = DPH_START;
-  S[c].it = 0;
-  es[c] = T(0);
-}
-
 // ================================================================================================
 // The NUTS loop on a POINT POOL (round 3): k_d_tree2.
 //
-// k_d_tree keeps "the current point" in fixed (D,N) arrays and COPIES whatever must outlive a leapfrog: every leaf that does
-// not end its subtree parks five vectors (ρ, v_first, candidate θ / r / g), an accepted subtree copies its candidate, a
-// change of direction swaps five vectors, a new transition copies the state into eight slots — ≈ 20 D-vectors of HBM traffic
+// Round 2's tree kernel kept "the current point" in fixed (D,N) arrays and COPIED whatever had to outlive a leapfrog: every leaf
+// that did not end its subtree parked five vectors (ρ, v_first, candidate θ / r / g), an accepted subtree copied its candidate, a
+// change of direction swapped five vectors, a new transition copied the state into eight slots — ≈ 20 D-vectors of HBM traffic
 // per chain-step where the two half-steps need 8, and at cfg4 that kernel was as long as the GEMM it alternates with
 // (profiles/r2_cfg4_top_kernels.txt: 40 % of device time).
 //
@@ -1059,12 +468,12 @@ __global__ __launch_bounds__(256) void k_d_tree_reset(DChain<T>* S, T* es, int* 
 // Parking, accepting and changing direction move no vector at all; only the ρ of merged subtrees (sums, not points) are
 // vectors of their own, written straight into the slot of the level they will be parked at.  A new transition starts on
 // the candidate's own point (fresh r, v written over it; its g and w = M⁻¹g are still valid, so the motionless warm-up step
-// of k_d_tree is needed for the first transition of a batch only).  A free point is any index no holder names
+// is needed for the first transition of a batch only).  A free point is any index no holder names
 // (≤ 2·max_depth + 2 live at once; found from a bit mask, no reference counts).
 //
-// GeneralisedNoUTurn, untempered leapfrogs, MultinomialTS / SliceTS — the default NUTS; the other criteria and the
-// TemperedLeapfrog keep k_d_tree_crit, ask / tell (ahmc_ext_*) keeps k_d_tree (its positions must sit in ctx->th).
-// Same draws in the same order, same arithmetic per element as k_d_tree: chains are bit-identical to it.
+// The engine's one NUTS tree kernel: every termination criterion, Leapfrog and TemperedLeapfrog, MultinomialTS / SliceTS, the
+// in-kernel StepSizeAdaptor; built-in targets, user kernels and ask / tell (ahmc_ext_*: "staged", its positions also in ctx->th).
+// Same draws in the same order, same arithmetic per element as the copying kernel it replaced: chains are bit-identical to it.
 // ================================================================================================
 enum { PV_TH = 0, PV_R = 1, PV_G = 2, PV_V = 3, PV_W = 4, PV_COUNT = 5 };
 enum { PR_TREE = 0, PR_SUB0 = 1, PR_SUB1 = 2, PR_LEVEL0 = 2 };  // ρ vectors: whole tree, two scratch, level l >= 1 at PR_LEVEL0 + l
@@ -1177,7 +586,7 @@ __device__ __forceinline__ void dn_chain_barrier() {
 // test needs θ and v at the two ends of a (sub)tree, which are pool points already; 2 StrictGeneralisedNoUTurn (:579-617): two more
 // index holders — per pending level its LAST-built leaf (p_last), per doubling the edge it grew from (S.edge) — and at every merge the two
 // extra checks (ρ_F + r_S.first ; ends F.first, S.first) and (r_F.last + ρ_S ; ends F.last, S.last) for F = the first-built half, S = the
-// second.  Before round 6 these two criteria ran on the copying kernel k_d_tree_crit only.
+// second.  Before round 6 these two criteria ran on round 2's copying tree kernel only (since retired).
 template <class T, int DT, bool WV = false, int DC = 0, int VCH = 8, int CRIT = 1>
 __device__ __forceinline__ T d_tree_advance2(const KP<T>& p, const DP2<T>& q, int64_t c, int lane, T lp_in, T lk_in, const DHot<T>& hot, int& src,
                                              uint64_t& used, bool& rewritten /* the point `src` was given a fresh momentum in this call */) {

@@ -149,17 +149,14 @@ int dn_refresh_fused(Ctx<T>* c) {
   return AHMC_OK;
 }
 
-// workspace for trees of up to max_depth doublings
+// workspace of the engine: the vector slots of static HMC and find_good_stepsize (DS_*), their per-chain state, the signed
+// steps, the running-chain lists and counters
 template <class T>
-int dn_ensure(Ctx<T>* c, int max_depth, int criterion = AHMC_TC_GENERALISED) {
-  const int nlev = max_depth > 1 ? max_depth - 1 : 1;
-  const size_t per_level = criterion == AHMC_TC_STRICT ? DLevel<2>::STRIDE : DLevel<1>::STRIDE;
-  const size_t slots = (size_t)DS_FIXED + per_level * nlev;
-  if (slots > c->dn_slots) {
-    if (c->dn_W) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->dn_W)); c->dn_W = nullptr; }
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->dn_W), slots * (size_t)c->D * (size_t)c->N * sizeof(T)));
-    HIPCHK(hipMemsetAsync(c->dn_W, 0, slots * (size_t)c->D * (size_t)c->N * sizeof(T), c->stream));
-    c->dn_slots = slots;
+int dn_ensure(Ctx<T>* c) {
+  if (!c->dn_W) {
+    const size_t n = (size_t)DS_FIXED * (size_t)c->D * (size_t)c->N;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->dn_W), n * sizeof(T)));
+    HIPCHK(hipMemsetAsync(c->dn_W, 0, n * sizeof(T), c->stream));
   }
   if (!c->dn_S) {
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->dn_S), (size_t)c->N * sizeof(DChain<T>)));
@@ -172,7 +169,7 @@ int dn_ensure(Ctx<T>* c, int max_depth, int criterion = AHMC_TC_GENERALISED) {
   return AHMC_OK;
 }
 
-// the point pool of k_d_tree2 / k_dense_epoch for trees of up to max_depth doublings: 2·max_depth + 2 points of 5 vectors per chain
+// the point pool of k_d_tree2 / k_dense_epoch (NUTS, ask / tell included) for trees of up to max_depth doublings: 2·max_depth + 2 points of 5 vectors per chain
 // (+ 1: the speculative half-step of k_dense_epoch), and max_depth + 2 ρ vectors (cfg4's shard, D = 512, 8 192 chains, max_depth 10:
 // 3.9 GB + 0.4 GB of the 288)
 template <class T>
@@ -242,7 +239,7 @@ int dn_target(Ctx<T>* c, const int* list = nullptr, int64_t n = -1) {
 
 template <class T>
 int dn_fill_caches(Ctx<T>* c) {
-  int rc = dn_ensure(c, 2);
+  int rc = dn_ensure(c);
   if (rc) return rc;
   rc = dn_target(c);
   if (rc) return rc;
@@ -422,7 +419,7 @@ template <class T>
 int dn_refresh(Ctx<T>* c, double alpha) {
   int rc = dn_check(c, "refresh_momentum", alpha);
   if (rc) return rc;
-  rc = dn_ensure(c, 2);
+  rc = dn_ensure(c);
   if (rc) return rc;
   rc = dn_fresh_momentum(c, alpha, c->r);
   if (rc) return rc;
@@ -435,7 +432,7 @@ template <class T>
 int dn_leapfrog(Ctx<T>* c, int64_t n_steps) {
   int rc = dn_check(c, "leapfrog", 0);
   if (rc) return rc;
-  rc = dn_ensure(c, 2);
+  rc = dn_ensure(c);
   if (rc) return rc;
   const int64_t n = n_steps < 0 ? -n_steps : n_steps;
   rc = dn_velocity(c);  // v = M⁻¹r of the point as it is now (the slot may hold another edge's)
@@ -464,7 +461,7 @@ template <class T>
 int dn_hmc_transition(Ctx<T>* c, int64_t L, int sampler, double refresh_alpha, bool accum) {
   int rc = dn_check(c, "hmc_transition", refresh_alpha);
   if (rc) return rc;
-  rc = dn_ensure(c, 2);
+  rc = dn_ensure(c);
   if (rc) return rc;
   rc = dn_fresh_momentum(c, refresh_alpha, c->r);  // refresh (src/sampler.jl:54-57)
   if (rc) return rc;
@@ -515,32 +512,67 @@ int dn_nuts_batch_momenta(Ctx<T>* c, int n_trans, double refresh_alpha) {
   return AHMC_OK;
 }
 
-// one global step of the tree state machine with the kernel built for the criterion and the integrator (the default
-// — GeneralisedNoUTurn, no tempering — is k_d_tree, the measured kernel)
+// DP2 arguments of a NUTS batch of n_trans transitions on the point pool (after dn_ensure_pool), every chain listed.  `staged`:
+// the target reads θ′ from / leaves (ℓπ, g′) in the context's arrays (every target but the dense Gaussian and a wide context's
+// built-in family — ask / tell on every context)
 template <class T>
-void launch_d_tree(Ctx<T>* c, int criterion, unsigned grid, const KP<T>& p, const DP<T>& q, const T* minv_d, int per_chain, int dense_target, int do_post) {
-  const bool temper = c->integ_kind == AHMC_INTEGRATOR_TEMPERED;
-  const int dt = dt_threads_for(c->D);
-#define AHMC_LAUNCH_TREE(K) hipLaunchKernelGGL(K, dim3(grid), dim3(dt), 0, c->stream, p, q, minv_d, per_chain, dense_target, do_post)
-#define AHMC_TREE_BY_DT(CR, TP)                                                        \
-  do {                                                                                 \
-    if (dt == 64) AHMC_LAUNCH_TREE((k_d_tree_crit<T, CR, TP, 64>));                    \
-    else if (dt == 128) AHMC_LAUNCH_TREE((k_d_tree_crit<T, CR, TP, 128>));             \
-    else AHMC_LAUNCH_TREE((k_d_tree_crit<T, CR, TP, 256>));                            \
+DP2<T> make_dp2(Ctx<T>* c, int n_trans, bool staged) {
+  DP2<T> q2;
+  memset(&q2, 0, sizeof(q2));
+  q2.P = c->dn_P; q2.R = c->dn_R; q2.S = c->dn_S2; q2.ptcur = c->dn_ptcur; q2.es = c->dn_es; q2.RB = c->dn_RB; q2.VB = c->dn_VB;
+  q2.n_trans = n_trans; q2.n_pt = c->dn_npt; q2.n_rho = c->dn_nrho; q2.n_active = c->dn_active; q2.list = nullptr; q2.n_list = c->N;
+  q2.dense_metric = dn_recurrent(c) ? 1 : 0;
+  q2.staged = staged ? 1 : 0;
+  return q2;
+}
+
+// one global step of k_d_tree2 for the q2.n_list listed chains, the kernel built for the criterion and for the threads per chain
+// D asks for.  do_post = 0: the start of a batch (no leapfrog in flight yet)
+template <class T>
+void launch_tree2(Ctx<T>* c, int criterion, const KP<T>& p, const DP2<T>& q2, int dense_target, int do_post) {
+  const T* minv_d = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
+  const int pc = c->minv_per_chain ? 1 : 0;
+  const unsigned grid = (unsigned)q2.n_list;
+  const int dtt = dt_threads_for(c->D);
+#define AHMC_TREE2(CR)                                                                                                                          \
+  do {                                                                                                                                          \
+    if (dtt == 64) hipLaunchKernelGGL((k_d_tree2<T, 64, CR>), dim3(grid), dim3(64), 0, c->stream, p, q2, minv_d, pc, dense_target, do_post);     \
+    else if (dtt == 128) hipLaunchKernelGGL((k_d_tree2<T, 128, CR>), dim3(grid), dim3(128), 0, c->stream, p, q2, minv_d, pc, dense_target, do_post); \
+    else hipLaunchKernelGGL((k_d_tree2<T, 256, CR>), dim3(grid), dim3(256), 0, c->stream, p, q2, minv_d, pc, dense_target, do_post);             \
   } while (0)
-  if (criterion == AHMC_TC_CLASSIC) {
-    if (temper) AHMC_TREE_BY_DT(0, true); else AHMC_TREE_BY_DT(0, false);
-  } else if (criterion == AHMC_TC_STRICT) {
-    if (temper) AHMC_TREE_BY_DT(2, true); else AHMC_TREE_BY_DT(2, false);
-  } else if (temper) {
-    AHMC_TREE_BY_DT(1, true);
-  } else {  // the default and the measured kernel
-    if (dt == 64) AHMC_LAUNCH_TREE((k_d_tree<T, 64>));
-    else if (dt == 128) AHMC_LAUNCH_TREE((k_d_tree<T, 128>));
-    else AHMC_LAUNCH_TREE((k_d_tree<T, 256>));
-  }
-#undef AHMC_TREE_BY_DT
-#undef AHMC_LAUNCH_TREE
+  if (criterion == AHMC_TC_CLASSIC) AHMC_TREE2(0);
+  else if (criterion == AHMC_TC_STRICT) AHMC_TREE2(2);
+  else AHMC_TREE2(1);
+#undef AHMC_TREE2
+}
+
+// start of a NUTS batch on the pool: every chain reset, then the start of its transition 0 (Unit / Diag metric: and the first
+// half of its first leapfrog)
+template <class T>
+int dn_tree2_begin(Ctx<T>* c, int criterion, const KP<T>& p, const DP2<T>& q2, int dense_target) {
+  hipLaunchKernelGGL((k_d_tree2_reset<T>), dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, c->dn_S2, c->dn_es, c->dn_ptcur, c->dn_active, c->N);
+  launch_tree2(c, criterion, p, q2, dense_target, 0);
+  HIPCHK(hipGetLastError());
+  c->dn_last_pool = 1;
+  return AHMC_OK;
+}
+
+// staged step, non-diagonal metric: w′ = M⁻¹g′ from the context's g into the pool point of each listed chain's leapfrog
+template <class T>
+int dn_staged_w(Ctx<T>* c, const int* list, int64_t n) {
+  const int64_t PS = (int64_t)PV_COUNT * c->D, CS = (int64_t)c->dn_npt * PS;  // pool strides: between the points of a chain, between chains
+  return dn_minv_apply(c, (const T*)c->g, c->dn_P + (size_t)PV_W * c->D, n, list, c->dn_ptcur, (int64_t)0, PS, (int64_t)0, CS);
+}
+
+// the chains of list[0..n) still running into `out`, their number into *cnt (device) and *active (host: once the context's
+// stream has synchronised)
+template <class T>
+int dn_compact(Ctx<T>* c, const int* list, int64_t n, int* out, int* cnt, int* active) {
+  HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL((k_d_compact2<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->dn_S2, list, n, out, cnt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(active, cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  return AHMC_OK;
 }
 
 // n_trans NUTS transitions of every chain (asynchronous chains, see ahmc_dense.hpp)
@@ -621,8 +653,6 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   if (max_depth > DN_MAXLEV + 1) return fail(c, AHMC_ERR_UNSUPPORTED, "nuts_transition: the dense engine supports max_depth <= 17");
   if (adapt_i0 >= 0 && refresh_alpha != 0)
     return fail(c, AHMC_ERR_UNSUPPORTED, "dense engine: the in-kernel StepSizeAdaptor needs full momentum refreshment (the momenta of a batch are drawn up front)");
-  if (adapt_i0 >= 0 && getenv("AHMC_DENSE_POOL") && atoi(getenv("AHMC_DENSE_POOL")) == 0)  // (the caller decides from the same variable; checked again here
-    return fail(c, AHMC_ERR_UNSUPPORTED, "dense engine: AHMC_DENSE_POOL=0 selects the copying tree kernel, which has no in-kernel StepSizeAdaptor");  // because a silent unadapted warm-up is the alternative)
   if (refresh_alpha != 0 && n_trans > 1) {
     // a partially refreshed momentum depends on the momentum the previous transition ended with, so the batch's
     // momenta cannot be drawn up front: one transition per batch
@@ -632,9 +662,11 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
     }
     return AHMC_OK;
   }
-  rc = dn_ensure(c, max_depth, criterion);
+  rc = dn_ensure(c);
   if (rc) return rc;
   rc = dn_nuts_batch_momenta(c, n_trans, refresh_alpha);
+  if (rc) return rc;
+  rc = dn_ensure_pool(c, max_depth, criterion);
   if (rc) return rc;
   KP<T> p = make_kp(c);
   p.max_depth = max_depth;
@@ -643,63 +675,23 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   p.sampler = sampler;
   p.accum = accum ? 1 : 0;
   p.samples_out = samples_dev;
-  DP<T> q = make_dp(c);
-  q.n_trans = n_trans;
   const bool dm = dn_recurrent(c), dt = c->target_kind == AHMC_TARGET_DENSE_GAUSS;
   const bool wt = c->wide && c->target_kind != AHMC_TARGET_KERNEL;  // wide built-in family: k_w_target reads θ′ from / writes g′ to the pool point itself
-  const T* minv_d = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
-  const int pc = c->minv_per_chain ? 1 : 0;
-  T* Wcur = dm ? c->dn_W + (size_t)DS_CUR_W * c->D * c->N : nullptr;
-  // The default NUTS (GeneralisedNoUTurn, untempered) runs on the point pool (k_d_tree2: no park / candidate / edge copies);
-  // the other criteria and the TemperedLeapfrog on the copying kernel.  AHMC_DENSE_POOL=0 forces the latter (A/B, tests).
-  const int pool_env = getenv("AHMC_DENSE_POOL") ? atoi(getenv("AHMC_DENSE_POOL")) : 1;
-  const bool pool = pool_env != 0;   // (round 6: every criterion and the TemperedLeapfrog on the pool kernels; AHMC_DENSE_POOL=0: the copying kernels)
-  c->dn_last_pool = pool ? 1 : 0;
-  DP2<T> q2;
-  memset(&q2, 0, sizeof(q2));
-  const int64_t PS = (int64_t)PV_COUNT * c->D;  // pool stride between the points of a chain; between chains: CS (set below)
-  int64_t CS = 0;
-  T *Pth = nullptr, *Pg = nullptr, *Pw = nullptr;
-  const int dtt = dt_threads_for(c->D);
-  auto launch_tree2 = [&](unsigned grid, int do_post) {
-#define AHMC_TREE2(CR)                                                                                                                        \
-  do {                                                                                                                                        \
-    if (dtt == 64) hipLaunchKernelGGL((k_d_tree2<T, 64, CR>), dim3(grid), dim3(64), 0, c->stream, p, q2, minv_d, pc, dt ? 1 : 0, do_post);     \
-    else if (dtt == 128) hipLaunchKernelGGL((k_d_tree2<T, 128, CR>), dim3(grid), dim3(128), 0, c->stream, p, q2, minv_d, pc, dt ? 1 : 0, do_post); \
-    else hipLaunchKernelGGL((k_d_tree2<T, 256, CR>), dim3(grid), dim3(256), 0, c->stream, p, q2, minv_d, pc, dt ? 1 : 0, do_post);             \
-  } while (0)
-    if (criterion == AHMC_TC_CLASSIC) AHMC_TREE2(0);
-    else if (criterion == AHMC_TC_STRICT) AHMC_TREE2(2);
-    else AHMC_TREE2(1);
-#undef AHMC_TREE2
-  };
-  if (pool) {
-    rc = dn_ensure_pool(c, max_depth, criterion);
-    if (rc) return rc;
-    q2.P = c->dn_P; q2.R = c->dn_R; q2.S = c->dn_S2; q2.ptcur = c->dn_ptcur; q2.es = c->dn_es; q2.RB = c->dn_RB; q2.VB = c->dn_VB;
-    q2.n_trans = n_trans; q2.n_pt = c->dn_npt; q2.n_rho = c->dn_nrho; q2.n_active = c->dn_active; q2.list = nullptr; q2.n_list = c->N;
-    CS = (int64_t)c->dn_npt * PS;
-    q2.dense_metric = dm ? 1 : 0;
-    q2.staged = (dt || wt) ? 0 : 1;
-    if (adapt_i0 >= 0) {
-      q2.adapt_ss = 1;
-      q2.i0 = adapt_i0;
-      q2.n_adapts = adapt_n;
-      q2.delta = (T)c->da_delta; q2.gamma = T(DA_GAMMA); q2.t0 = T(DA_T0); q2.kappa = T(DA_KAPPA);  // stepsize.jl:168-172
-      q2.da_m = c->da_m; q2.da_eps = c->da_eps; q2.da_mu = c->da_mu; q2.da_xbar = c->da_xbar; q2.da_Hbar = c->da_Hbar;
-      q2.da_tab = c->da_tab;
-    }
-    Pth = c->dn_P + (size_t)PV_TH * c->D;
-    Pg = c->dn_P + (size_t)PV_G * c->D;
-    Pw = c->dn_P + (size_t)PV_W * c->D;
-    hipLaunchKernelGGL((k_d_tree2_reset<T>), dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, c->dn_S2, c->dn_es, c->dn_ptcur, c->dn_active, c->N);
-    launch_tree2((unsigned)c->N, 0);  // start of transition 0 (and, for Unit/Diag metrics, the first half of its first leapfrog)
-  } else {
-    hipLaunchKernelGGL((k_d_tree_reset<T>), dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, c->dn_S, c->dn_es, c->dn_active, c->N);
-    // start of transition 0 (and, for Unit/Diag metrics, the first half of its first leapfrog)
-    launch_d_tree(c, criterion, (unsigned)c->N, p, q, minv_d, pc, dt ? 1 : 0, 0);
+  DP2<T> q2 = make_dp2(c, n_trans, !(dt || wt));
+  if (adapt_i0 >= 0) {
+    q2.adapt_ss = 1;
+    q2.i0 = adapt_i0;
+    q2.n_adapts = adapt_n;
+    q2.delta = (T)c->da_delta; q2.gamma = T(DA_GAMMA); q2.t0 = T(DA_T0); q2.kappa = T(DA_KAPPA);  // stepsize.jl:168-172
+    q2.da_m = c->da_m; q2.da_eps = c->da_eps; q2.da_mu = c->da_mu; q2.da_xbar = c->da_xbar; q2.da_Hbar = c->da_Hbar;
+    q2.da_tab = c->da_tab;
   }
-  HIPCHK(hipGetLastError());
+  const int64_t PS = (int64_t)PV_COUNT * c->D, CS = (int64_t)c->dn_npt * PS;  // pool strides: between the points of a chain, between chains
+  T* Pth = c->dn_P + (size_t)PV_TH * c->D;
+  T* Pg = c->dn_P + (size_t)PV_G * c->D;
+  T* Pw = c->dn_P + (size_t)PV_W * c->D;
+  rc = dn_tree2_begin(c, criterion, p, q2, dt ? 1 : 0);
+  if (rc) return rc;
   // global steps until every chain has finished the batch.  Every CHUNK steps the list of chains
   // still running is compacted and its length read back, so the tail of the batch (few chains with
   // long trees left) costs GEMMs over those chains only.
@@ -710,14 +702,10 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   // own stream with its own running-chain list, and the hardware overlaps one half's tree kernel with the other
   // half's GEMM.  (Dense target only: the built-in families' cache kernel has no chain list.)
   //
-  // AHMC_DENSE_SPLIT=1 (default) gives each half its own stream.  Nothing then keeps the halves out of phase: both GEMMs
-  // are enqueued together and share the matrix pipe, then both tree kernels share HBM — which is what the measured
-  // +2.5 % says happened.  AHMC_DENSE_SPLIT=2 orders the work by KIND instead: every GEMM on the context's stream (A0 B0
-  // A1 B1 …), every tree kernel on the second stream (A0 B0 A1 …), with an event per half in each direction (tree k
-  // waits for GEMM k; the next GEMM of that half waits for its tree kernel).  Stream order then forces the phase shift:
-  // GEMM B(s) can only run beside tree A(s), GEMM A(s+1) beside tree B(s).  Same kernels on the same data: bit-identical
-  // results.  Measured in round 2 (profiles/r2_cfg4_timeline_split*.json): the phase shift happens as designed and both
-  // kernels slow down by the factor they now share the chip — 18.5–19.6 TFLOP/s against 24.0 for =1 and 22.2 for =0.  Kept as a switch.
+  // Each half has its own stream.  Nothing then keeps the halves out of phase: both GEMMs are enqueued together and share the
+  // matrix pipe, then both tree kernels share HBM — which is what the measured +2.5 % says happened.  (Measured and retired: a
+  // schedule by kernel KIND with event hand-over, 18.5–19.6 TFLOP/s against 24.0; three or four smaller pipelines.)
+  // AHMC_DENSE_SPLIT=0: one pipeline — the reference the two must reproduce bit for bit.
   const int chunk_env = getenv("AHMC_DENSE_CHUNK") ? atoi(getenv("AHMC_DENSE_CHUNK")) : 0;  // (experiments: global steps between two compactions)
   const int CHUNK_STEP = chunk_env >= 4 && chunk_env <= 256 ? chunk_env : 16;   // step-synchronous kernels
   const int CHUNK_EPOCH = chunk_env >= 4 && chunk_env <= 256 ? chunk_env : 64;  // k_dense_epoch: one launch per chunk (cfg4: 16 / 32 / 64 steps 35.7 / 36.4 / 36.8 TFLOP/s)
@@ -738,9 +726,9 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   const bool epoch2_ok = epoch_v >= 2 && epoch2_shape<T>((int)c->D, getenv("AHMC_DENSE_EPOCH_NCT") ? atoi(getenv("AHMC_DENSE_EPOCH_NCT")) : 0, e2_nct, e2_wpe,
                                                                  getenv("AHMC_DENSE_EPOCH_WPE") ? atoi(getenv("AHMC_DENSE_EPOCH_WPE")) : 0, criterion);
   const bool epoch1_ok = !epoch2_ok && v1_has;
-  const bool epoch_ok = epoch_env != 0 && pool && dt && dm && c->dn_fused_ok && (epoch2_ok || epoch1_ok);   // (epoch2_shape knows the criteria it has kernels for)
+  const bool epoch_ok = epoch_env != 0 && dt && dm && c->dn_fused_ok && (epoch2_ok || epoch1_ok);   // (epoch2_shape knows the criteria it has kernels for)
   const int epoch_chains = epoch2_ok ? 16 * e2_nct : DE_CHAINS;
-  q2.lazy_gw = (epoch_ok && (getenv("AHMC_DENSE_LAZY_GW") ? atoi(getenv("AHMC_DENSE_LAZY_GW")) : 1)) ? 1 : 0;  // (for the whole batch: the step-synchronous kernels of its tail must not trust a record the epoch kernel skipped)
+  q2.lazy_gw = epoch_ok ? 1 : 0;  // (for the whole batch: the step-synchronous kernels of its tail must not trust a record the epoch kernel skipped)
   if (epoch_ok) {
     if (!c->dn_Asw) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->dn_Asw), 2 * sizeof(T) * (size_t)c->D * (size_t)c->D));
     const int64_t tot = 2 * c->D * c->D;
@@ -770,34 +758,19 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
     }
   };
   const int split_env = getenv("AHMC_DENSE_SPLIT") ? atoi(getenv("AHMC_DENSE_SPLIT")) : 1;  // (read per call: the tests toggle it)
-  // AHMC_DENSE_PIPES=3|4 (with AHMC_DENSE_SPLIT=1): more, smaller pipelines — more chances for one pipeline's memory-bound tree
-  // kernel to run beside another's GEMM, smaller GEMM launches
-  const int pipes_env = getenv("AHMC_DENSE_PIPES") ? atoi(getenv("AHMC_DENSE_PIPES")) : 2;
-  const int NP = (split_env != 0 && dt && c->N >= 2048) ? ((split_env == 1 && pipes_env >= 2 && pipes_env <= 4 && c->N >= 512 * pipes_env) ? pipes_env : 2) : 1;
+  const int NP = (split_env != 0 && dt && c->N >= 2048) ? 2 : 1;
   c->dn_last_pipelines = NP;
   struct Pipe { hipStream_t s; const int* list; int64_t n_list; int pp; int* lists; int* cnt; int active; };
-  Pipe pipes[4];
+  Pipe pipes[2];
   const int64_t per = (c->N + NP - 1) / NP;  // capacity of one running-chain list of a pipeline (two per pipeline: 2·NP·per <= 4·N ints)
-  if (NP >= 2 && !c->stream2) {
+  if (NP == 2 && !c->stream2) {
     HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&c->ev_split, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   }
-  for (int k = 2; k < NP; ++k)
-    if (!c->stream_x[k - 2]) {
-      HIPCHK(hipStreamCreateWithFlags(&c->stream_x[k - 2], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_join_x[k - 2], hipEventDisableTiming));
-    }
-  const bool by_kind = NP == 2 && split_env == 2 && dm && c->dn_fused_ok;  // (one GEMM launch per half and step)
-  if (by_kind && !c->ev_gemm[0]) {
-    for (int k = 0; k < 2; ++k) {
-      HIPCHK(hipEventCreateWithFlags(&c->ev_gemm[k], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_tree[k], hipEventDisableTiming));
-    }
-  }
   for (int k = 0; k < NP; ++k) {
     Pipe& h = pipes[k];
-    h.s = k >= 2 ? c->stream_x[k - 2] : ((k == 0 && !by_kind) ? c->stream : c->stream2);  // (by kind: the stream of the half's tree kernel, compaction and read-back)
+    h.s = k == 0 ? c->stream : c->stream2;
     h.lists = c->dn_list + (size_t)k * 2 * per;
     h.cnt = c->dn_active + 1 + k;
     h.pp = 0;
@@ -814,13 +787,11 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   }
   HIPCHK(hipGetLastError());
   hipStream_t main_stream = c->stream;
-  if (NP >= 2) {  // everything enqueued so far (momenta, start of transition 0, the lists) precedes the other pipelines
+  if (NP == 2) {  // everything enqueued so far (momenta, start of transition 0, the lists) precedes the other pipeline
     HIPCHK(hipEventRecord(c->ev_split, main_stream));
     HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_split, 0));
-    for (int k = 2; k < NP; ++k) HIPCHK(hipStreamWaitEvent(c->stream_x[k - 2], c->ev_split, 0));
   }
   auto bail = [&](int code) { c->stream = main_stream; return code; };
-  bool tree_recorded[2] = {false, false};
   auto any_running = [&]() {
     for (int k = 0; k < NP; ++k)
       if (pipes[k].n_list > 0) return true;
@@ -844,51 +815,25 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
           }
           continue;
         }
-        q.list = h.list;
-        q.n_list = h.n_list;
-        // one global step = g′ = Pθ′ (or the built-in family's kernel), w′ = M⁻¹g′, then the fused
-        // second-half / tree / first-half kernel
+        // one global step = g′ = Pθ′ (or the target's kernel), w′ = M⁻¹g′, then the fused second-half / tree / first-half kernel
         q2.list = h.list;
         q2.n_list = h.n_list;
-        const int* pti = pool ? c->dn_ptcur : nullptr;
-        const T* gX = pool ? Pth : c->th;   // θ′ of the leapfrogs in flight
-        T* gY = pool ? Pg : c->g;           // g′
-        T* gW = pool ? Pw : Wcur;           // w′
-        const int64_t ps = pool ? PS : 0, cs = pool ? CS : 0;
-        if (by_kind) {
-          c->stream = main_stream;
-          if (tree_recorded[k] && hipStreamWaitEvent(main_stream, c->ev_tree[k], 0) != hipSuccess) return bail(fail(c, AHMC_ERR_RUNTIME, "hipStreamWaitEvent failed"));
-          rc = dn_gemm(c, c->tparams, gX, gY, h.n_list, h.list, c->dn_C, gW, pti, ps, ps, cs, cs);
-          if (rc) return bail(rc);
-          if (hipEventRecord(c->ev_gemm[k], main_stream) != hipSuccess || hipStreamWaitEvent(h.s, c->ev_gemm[k], 0) != hipSuccess)
-            return bail(fail(c, AHMC_ERR_RUNTIME, "hipEventRecord / hipStreamWaitEvent failed"));
-          c->stream = h.s;
-        } else if (dt && dm && c->dn_fused_ok) {
-          rc = dn_gemm(c, c->tparams, gX, gY, h.n_list, h.list, c->dn_C, gW, pti, ps, ps, cs, cs);  // g′ = Pθ′ and w′ = (M⁻¹P)θ′, one launch
-          if (rc) return bail(rc);
+        const int* pti = c->dn_ptcur;
+        if (dt && dm && c->dn_fused_ok) {
+          rc = dn_gemm(c, c->tparams, Pth, Pg, h.n_list, h.list, c->dn_C, Pw, pti, PS, PS, CS, CS);  // g′ = Pθ′ and w′ = (M⁻¹P)θ′, one launch
         } else if (wt) {
-          rc = dn_wide_target(c, h.list, h.n_list, gX, gY, pti, ps, cs);  // (ℓπ sanitised in the kernel)
-          if (rc) return bail(rc);
-          if (dm) {  // (the rank-update metric: a wide context has no dense one)
-            rc = dn_minv_apply(c, (const T*)gY, gW, h.n_list, h.list, pti, ps, ps, cs, cs);
-            if (rc) return bail(rc);
-          }
+          rc = dn_wide_target(c, h.list, h.n_list, Pth, Pg, pti, PS, CS);  // (ℓπ sanitised in the kernel)
+          if (!rc && dm) rc = dn_minv_apply(c, (const T*)Pg, Pw, h.n_list, h.list, pti, PS, PS, CS, CS);  // (the rank-update metric: a wide context has no dense one)
+        } else if (dt) {
+          rc = dn_gemm(c, c->tparams, Pth, Pg, h.n_list, h.list, (const T*)nullptr, (T*)nullptr, pti, PS, PS, CS, CS);
+          if (!rc && dm) rc = dn_minv_apply(c, (const T*)Pg, Pw, h.n_list, h.list, pti, PS, PS, CS, CS);
         } else {
-          // (a target that is not the dense Gaussian reads θ′ from / leaves g′ in the context's arrays: the pool is "staged")
-          rc = dt ? dn_gemm(c, c->tparams, gX, gY, h.n_list, h.list, (const T*)nullptr, (T*)nullptr, pti, ps, ps, cs, cs) : dn_other_target(c, h.list, h.n_list, /*sanitize_lp=*/!pool);  // (the pool kernel sanitises ℓπ itself: one launch fewer per global step)
-          if (rc) return bail(rc);
-          if (dm) {
-            rc = dt ? dn_minv_apply(c, (const T*)gY, gW, h.n_list, h.list, pti, ps, ps, cs, cs)
-                    : dn_minv_apply(c, (const T*)c->g, gW, h.n_list, h.list, pti, (int64_t)0, ps, (int64_t)0, cs);
-            if (rc) return bail(rc);
-          }
+          // staged: the target reads θ′ from / leaves g′ in the context's arrays (the tree kernel sanitises ℓπ itself: one launch fewer per step)
+          rc = dn_other_target(c, h.list, h.n_list, /*sanitize_lp=*/false);
+          if (!rc && dm) rc = dn_staged_w(c, h.list, h.n_list);
         }
-        if (pool) launch_tree2((unsigned)h.n_list, 1);
-        else launch_d_tree(c, criterion, (unsigned)h.n_list, p, q, minv_d, pc, dt ? 1 : 0, 1);
-        if (by_kind) {
-          if (hipEventRecord(c->ev_tree[k], h.s) != hipSuccess) return bail(fail(c, AHMC_ERR_RUNTIME, "hipEventRecord failed"));
-          tree_recorded[k] = true;
-        }
+        if (rc) return bail(rc);
+        launch_tree2(c, criterion, p, q2, dt ? 1 : 0, 1);
       }
     }
     done_steps += CHUNK;
@@ -897,11 +842,8 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
       Pipe& h = pipes[k];
       if (h.n_list <= 0) continue;
       c->stream = h.s;
-      int* out = h.lists + (size_t)h.pp * (NP == 1 ? c->N : per);
-      if (hipMemsetAsync(h.cnt, 0, sizeof(int), h.s) != hipSuccess) return bail(fail(c, AHMC_ERR_RUNTIME, "hipMemsetAsync failed"));
-      if (pool) hipLaunchKernelGGL((k_d_compact2<T>), dim3((unsigned)((h.n_list + 255) / 256)), dim3(256), 0, h.s, c->dn_S2, h.list, h.n_list, out, h.cnt);
-      else hipLaunchKernelGGL((k_d_compact<T>), dim3((unsigned)((h.n_list + 255) / 256)), dim3(256), 0, h.s, c->dn_S, h.list, h.n_list, out, h.cnt);
-      if (hipMemcpyAsync(&h.active, h.cnt, sizeof(int), hipMemcpyDeviceToHost, h.s) != hipSuccess) return bail(fail(c, AHMC_ERR_RUNTIME, "hipMemcpyAsync failed"));
+      rc = dn_compact(c, h.list, h.n_list, h.lists + (size_t)h.pp * (NP == 1 ? c->N : per), h.cnt, &h.active);
+      if (rc) return bail(rc);
     }
     for (int k = 0; k < NP; ++k) {
       Pipe& h = pipes[k];
@@ -914,13 +856,9 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
     }
   }
   c->stream = main_stream;
-  if (NP >= 2) {  // whatever is enqueued on the context's stream next comes after the other pipelines
+  if (NP == 2) {  // whatever is enqueued on the context's stream next comes after the other pipeline
     HIPCHK(hipEventRecord(c->ev_join, c->stream2));
     HIPCHK(hipStreamWaitEvent(main_stream, c->ev_join, 0));
-    for (int k = 2; k < NP; ++k) {
-      HIPCHK(hipEventRecord(c->ev_join_x[k - 2], c->stream_x[k - 2]));
-      HIPCHK(hipStreamWaitEvent(main_stream, c->ev_join_x[k - 2], 0));
-    }
   }
 #ifdef AHMC_EPOCH_PROF
   if (epoch_ok) {
@@ -944,7 +882,7 @@ template <class T>
 int dn_find_eps(Ctx<T>* c, double init_eps, int max_iters) {
   int rc = dn_check(c, "find_good_stepsize", 0);
   if (rc) return rc;
-  rc = dn_ensure(c, 2);
+  rc = dn_ensure(c);
   if (rc) return rc;
   KP<T> p = make_kp(c);
   p.init_eps = (T)init_eps;

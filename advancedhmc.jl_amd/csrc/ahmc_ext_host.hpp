@@ -5,13 +5,14 @@
 // cannot be one fused kernel.  It does not have to be: the step-synchronous engine of ahmc_dense.hpp already
 // advances every chain by ONE leapfrog per "global step" with the gradient coming from outside the tree kernel
 // (there: a GEMM).  Here the outside is the caller.  One ahmc_ext_advance =
-//     ingest (ℓπ, -∇ℓπ) of the pending chains  →  [dense metric: w′ = M⁻¹g′ on MFMA]  →
-//     k_d_tree: second half of the leapfrog, one NUTS leaf + its merges (+ end / start of a transition),
-//               first half of the next leapfrog  →  compaction of the running chains
+//     ingest (ℓπ, -∇ℓπ) of the pending chains  →  [dense / rank-update metric: w′ = M⁻¹g′ into the pool point]  →
+//     k_d_tree2: second half of the leapfrog, one NUTS leaf + its merges (+ end / start of a transition),
+//                first half of the next leapfrog  →  compaction of the running chains
 // and the positions the next leapfrog needs are in c->th when it returns.  The kernels are those of the dense
-// engine, unchanged (dense_target = 0: ℓπ is taken from the context, where ingest put it); Unit / Diag / Dense
-// metric.  Static HMC (EndPointTS; MultinomialTS through the state machine of ahmc_dense_mn_host.hpp) and
-// find_good_stepsize drive k_d_pre / k_d_post the same way.
+// engine's NUTS loop for a user kernel, unchanged: the point pool "staged" (θ′ also to c->th, g′ and ℓπ read back from
+// the context, where ingest put them; dense_target = 0) on every context, wide ones included.  Static HMC (EndPointTS;
+// MultinomialTS through the state machine of ahmc_dense_mn_host.hpp) and find_good_stepsize drive k_d_pre / k_d_post
+// the same way.
 #pragma once
 
 // lp[c] ← sanitize(lp_in[c]) (PhasePoint: non-finite ℓπ → -Inf, src/hamiltonian.jl:95-104), g[:, c] ← g_in[:, c]
@@ -57,6 +58,15 @@ KP<T> ext_kp(Ctx<T>* c) {
   p.accum = 0;
   p.samples_out = nullptr;
   return p;
+}
+
+// the NUTS batch in progress on the point pool: staged on every context (the caller evaluates at c->th)
+template <class T>
+DP2<T> ext_dp2(Ctx<T>* c) {
+  DP2<T> q2 = make_dp2(c, c->ext.n_trans, true);
+  q2.list = c->ext.list;
+  q2.n_list = c->ext.n_list;
+  return q2;
 }
 
 template <class T>
@@ -105,7 +115,9 @@ int ext_begin(Ctx<T>* c, const ahmc_kernel_cfg* cfg, int n_trans) {
     if (cfg->criterion < AHMC_TC_CLASSIC || cfg->criterion > AHMC_TC_STRICT) return fail(c, AHMC_ERR_ARGUMENT, "unknown termination criterion");
     if (cfg->max_depth < 1) return fail(c, AHMC_ERR_ARGUMENT, "ext_begin: max_depth must be >= 1");
     if (cfg->max_depth > DN_MAXLEV + 1) return fail(c, AHMC_ERR_UNSUPPORTED, "ext_begin: the step-synchronous engine supports max_depth <= 17");
-    rc = dn_ensure(c, cfg->max_depth, cfg->criterion);
+    rc = dn_ensure(c);
+    if (rc) return rc;
+    rc = dn_ensure_pool(c, cfg->max_depth, cfg->criterion);
     if (rc) return rc;
     rc = dn_nuts_batch_momenta(c, n_trans, cfg->refresh_alpha);
     if (rc) return rc;
@@ -118,14 +130,9 @@ int ext_begin(Ctx<T>* c, const ahmc_kernel_cfg* cfg, int n_trans) {
     x.steps = 0;
     // a transition is at most 2^max_depth − 1 leapfrogs (+ the motionless first step of the dense metric)
     x.max_steps = (int64_t)n_trans * ((1ll << cfg->max_depth) + 1) + 16;
-    KP<T> p = ext_kp(c);
-    DP<T> q = ext_dp(c);
-    hipLaunchKernelGGL((k_d_tree_reset<T>), dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, c->dn_S, c->dn_es, c->dn_active, c->N);
-    const T* minv_d = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
-    // start of transition 0 of every chain (Unit / Diag metric: and the first half of its first leapfrog)
-    launch_d_tree(c, cfg->criterion, (unsigned)c->N, p, q, minv_d, c->minv_per_chain ? 1 : 0, 0, 0);
-    HIPCHK(hipGetLastError());
-    return AHMC_OK;
+    rc = dn_tree2_begin(c, cfg->criterion, ext_kp(c), ext_dp2(c), 0);
+    if (rc) x.mode = EXT_IDLE;
+    return rc;
   }
   // static HMC
   if (cfg->sampler != AHMC_TS_ENDPOINT && cfg->sampler != AHMC_TS_MULTINOMIAL)
@@ -137,7 +144,7 @@ int ext_begin(Ctx<T>* c, const ahmc_kernel_cfg* cfg, int n_trans) {
   }
   if (L < 0) L = -L;
   if (L < 1) return fail(c, AHMC_ERR_ARGUMENT, "ext_begin: static HMC needs at least one leapfrog step");
-  rc = dn_ensure(c, 2);
+  rc = dn_ensure(c);
   if (rc) return rc;
   x.mode = EXT_HMC;
   x.cfg = *cfg;
@@ -155,7 +162,7 @@ template <class T>
 int ext_find_eps_begin(Ctx<T>* c, double init_eps, int max_iters) {
   int rc = ext_common_checks(c, "ext_find_good_stepsize_begin");
   if (rc) return rc;
-  rc = dn_ensure(c, 2);
+  rc = dn_ensure(c);
   if (rc) return rc;
   ExtRun& x = c->ext;
   x.mode = EXT_FINDEPS;
@@ -240,24 +247,16 @@ int ext_advance(Ctx<T>* c, const void* lp_in, const void* g_in) {
   };
   int rc = AHMC_OK;
   if (x.mode == EXT_NUTS) {
-    const bool dm = dn_recurrent(c);
-    const T* minv_d = c->metric_kind == AHMC_METRIC_DIAG ? c->minv : nullptr;
-    T* Wcur = dm ? c->dn_W + (size_t)DS_CUR_W * c->D * c->N : nullptr;
-    if (dm) {
-      rc = dn_minv_apply(c, c->g, Wcur, x.n_list, x.list);  // w′ = M⁻¹g′
+    if (dn_recurrent(c)) {
+      rc = dn_staged_w(c, x.list, x.n_list);  // w′ = M⁻¹g′
       if (rc) { finish(); return rc; }
     }
-    KP<T> p = ext_kp(c);
-    DP<T> q = ext_dp(c);
-    launch_d_tree(c, x.cfg.criterion, (unsigned)x.n_list, p, q, minv_d, c->minv_per_chain ? 1 : 0, 0, 1);
+    launch_tree2(c, x.cfg.criterion, ext_kp(c), ext_dp2(c), 0, 1);
     // the chains still running: the next request
     int* out = c->dn_list + (size_t)x.pp * c->N;
-    int* cnt = c->dn_active + 1;
-    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL((k_d_compact<T>), dim3((unsigned)((x.n_list + 255) / 256)), dim3(256), 0, c->stream, c->dn_S, x.list, x.n_list, out, cnt);
-    HIPCHK(hipGetLastError());
     int active = 0;
-    HIPCHK(hipMemcpyAsync(&active, cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    rc = dn_compact(c, x.list, x.n_list, out, c->dn_active + 1, &active);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     c->dn_global_steps += 1;
     c->dn_chain_steps += x.n_list;

@@ -8,7 +8,8 @@ place at ahmc_theta_ptr and handing device pointers back (default), or by numpy 
 of the protocol (--host: the PCIe-inclusive figure).  Reports chain-leapfrogs/s, requests, µs per request, and the
 fused engine's figure for the same chains and step sizes as the yardstick.  One untimed transition first: the first
 ahmc_ext_begin allocates the step-synchronous engine's buffers (round 2 measurement, 16 384 x 128: 0.22 ms per
-request in steady state — 0.16 ms of it ahmc_ext_advance = ingest + k_d_tree + compaction + the 4-byte read-back —
+request in steady state — 0.16 ms of it ahmc_ext_advance = ingest + the tree kernel + compaction + the 4-byte read-back —
+today the point pool's k_d_tree2, staged —
 against 2.0 ms when the allocations are averaged in; scripts/ext_trace.py splits a request into its calls)."""
 import argparse
 import ctypes as C

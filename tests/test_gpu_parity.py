@@ -472,25 +472,21 @@ def test_dense_fused_stepsize_warmup_equals_stepwise(hip, rng, target):
 
 
 def test_dense_two_pipelines_equal_one(hip, rng, monkeypatch):
-    """the dense NUTS loop cut into two chain halves — a stream per half (AHMC_DENSE_SPLIT=1, the default) or a stream per
-    kernel kind with event hand-over (=2) — must give exactly the chains of the single pipeline (=0): chains are
-    independent and a column's arithmetic does not depend on which other columns share its GEMM launch"""
+    """the dense NUTS loop cut into two chain halves, a stream per half (AHMC_DENSE_SPLIT=1, the default), must give exactly
+    the chains of the single pipeline (=0): chains are independent and a column's arithmetic does not depend on which other
+    columns share its GEMM launch"""
     D, N = 48, 2304
     h = _dense_hamiltonian(D, N, rng, "dense", "dense")
     lf = A.Leapfrog(np.full(N, 0.15) * (0.6 + 0.8 * rng.random(N)))
     k = A.HMCKernel(A.Trajectory(A.MultinomialTS, lf, A.GeneralisedNoUTurn(max_depth=7)))
     th0 = 0.5 * rng.normal(size=(D, N))
     res = []
-    for split in ("0", "1", "2", "1nopool", "1pipes3", "1pipes4"):
-        monkeypatch.setenv("AHMC_DENSE_SPLIT", split[0])
-        monkeypatch.setenv("AHMC_DENSE_POOL", "0" if split.endswith("nopool") else "1")  # (the point-pool kernel == the copying kernel, bit for bit)
-        monkeypatch.setenv("AHMC_DENSE_PIPES", split[-1] if "pipes" in split else "2")
+    for split in ("0", "1"):
+        monkeypatch.setenv("AHMC_DENSE_SPLIT", split)
         e = A.Engine(h, N, rng=31, lib=hip)
         e.set_integrator(lf)
         e.set_position(th0)
         e.run(k, 5)
-        if "pipes" in split:
-            assert e.info("dense_pipelines") == int(split[-1])
         res.append((e.phasepoint(), e.stats(), e.accum()))
         e.close()
     z0, s0, a0 = res[0]

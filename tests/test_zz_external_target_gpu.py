@@ -56,7 +56,7 @@ def assert_close_state(e_ext, e_ref, what="external target"):
 @pytest.mark.parametrize("metric,target", [("dense", "dense"), ("dense", "funnel"), ("diag", "dense"), ("unit", "dense")])
 def test_dense_engine_classic_and_strict_uturn(hip, oracle, rng, metric, target, TS, TC):
     """ClassicNoUTurn (src/trajectory.jl:551-557) and StrictGeneralisedNoUTurn (:579-617) in the step-synchronous tree
-    kernel (k_d_tree_crit) against the oracle's recursion"""
+    kernel (k_d_tree2<…, CRIT>) against the oracle's recursion"""
     D, N = 16, 160
     B = rng.normal(size=(D, D))
     tgt = A.DenseGaussian(B @ B.T / D + np.eye(D)) if target == "dense" else A.Funnel(D)
