@@ -422,6 +422,41 @@ __device__ __forceinline__ void wave_allsum2(T& a, T& b) {
   b = dpp_mov<0x151>(x);  // row_newbcast:1
 }
 
+// Σa <= 0 || Σb <= 0 for a chain that owns one whole wave, as ONE wave-uniform (scalar) predicate — the generalised U-turn test, which
+// needs two signs and no sums.  Σa and Σb go through exactly the additions of wave_allsum2<64> (same transposed first stage, same
+// stages, same order), but the two row_newbcast that would hand lanes 0 / 1 of the row to all 64 lanes are not made: after the xor-32
+// stage lane 0 already holds the final bits of Σa and lane 1 those of Σb, so one compare of that register and bits 0 / 1 of its lane
+// mask are the two decisions.  ONLY those two lanes: the in-row rotations associate the four quads' sums in a rotated order from quad
+// to quad ((Q0 + Q1) + (Q2 + Q3) in quad 0, (Q1 + Q2) + (Q3 + Q0) in quad 1), so another even lane may hold Σa rounded differently —
+// wave_allsum2 returns lane 0's and lane 1's bits, and so must this.  Rows need no care: xor16 / xor32 add {lower, upper} in the
+// same order on both sides.  NaN: `<=` is false, as in the two compares this replaces.
+// 0: wave_allsum2 + two compares, the form of rounds 1–6, for A/B runs.
+// (Who reaches the first arm below: k_nuts calls this function only when AHMC_UTURN_ANY != 0, so in the engine it is the arm of the
+// experimental reductions alone — -DAHMC_MFMA_REDUCE=1, or -DAHMC_DS_REDUCE with bit 0 or 1, whose additions differ from the DPP
+// butterfly's and which therefore go through their own wave_allsum2.  AHMC_DS_REDUCE=4 moves only the final broadcast to the LDS pipe,
+// which this predicate does not make: it takes the second arm.  A direct caller built with -DAHMC_UTURN_ANY=0, such as the device
+// probe, gets the old form.)
+#ifndef AHMC_UTURN_ANY
+#define AHMC_UTURN_ANY 1
+#endif
+template <class T>
+__device__ __forceinline__ bool wave64_any_le0_pair(T a, T b) {
+  if constexpr (!AHMC_UTURN_ANY || AHMC_MFMA_REDUCE || (AHMC_DS_REDUCE & 3) != 0) {
+    wave_allsum2<64>(a, b);
+    return (__builtin_amdgcn_ballot_w64(a <= T(0)) != 0) || (__builtin_amdgcn_ballot_w64(b <= T(0)) != 0);
+  } else {
+    const bool odd = (threadIdx.x & 1u) != 0;
+    const T keep = odd ? b : a, send = odd ? a : b;
+    T x = keep + dpp_mov<0xB1>(send);  // quad_perm [1,0,3,2]
+    x += dpp_mov<0x4E>(x);             // quad_perm [2,3,0,1]
+    x += dpp_mov<0x124>(x);            // row_ror:4
+    x += dpp_mov<0x128>(x);            // row_ror:8
+    x = xor16_sum(x);
+    x = xor32_sum(x);
+    return (__builtin_amdgcn_ballot_w64(x <= T(0)) & 3ull) != 0ull;  // lane 0: Σa, lane 1: Σb
+  }
+}
+
 // the same for FOUR values: two transposed exchanges (lane & 1, then lane & 2) leave one value per lane, lanes 0..3 of
 // the row are broadcast back.  14 + 7 + 3 + 3 (+5 +5) + 8 = 45 VALU for G = 64 against 2 x 30, and the additions each
 // value goes through are those of wave_allsum2 (a, b as there; c, d as a second pair), so the results are bit-identical.

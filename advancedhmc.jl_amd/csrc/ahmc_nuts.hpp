@@ -185,35 +185,63 @@ __device__ __forceinline__ void leapfrog_core(Point<T, E>& z, const T (&minv)[E]
 // draw k = 32-bit word k & 3 of Philox block k >> 2; uniform = (w + ½)·2⁻³² ∈ (0,1), boolean = top bit.
 // One Philox block (≈75 VALU) serves four draws; 32 bits of resolution are ample for tree sampling
 // (the momentum normals, jitter and the static-HMC draws keep 53-bit uniforms).
-// WIDE (a chain owns whole wavefronts, G >= 64): the four 16-lane rows of the wave run Philox on four consecutive
-// blocks at once, so one Philox evaluation (≈75 VALU) serves SIXTEEN draws; a draw is then one v_readlane from the
-// row that holds its block.  Same blocks, same words, same draw order as the narrow form — only who computes what.
+// WIDE (a chain owns whole wavefronts, G >= 64): the lanes of the wave run Philox on consecutive blocks at once and a draw is one
+// v_readlane from a lane that holds its block.  Same blocks, same words, same draw order as the narrow form — only who computes what.
+//   AHMC_DRAWS_PER_LANE 1 (round 7): lane ℓ computes block base + ℓ, so one Philox evaluation (≈ 85 VALU) serves 256 draws — one
+//     evaluation for every tree below 255 draws, where the row form below made one per 16 draws with the 16 lanes of a row all
+//     computing the SAME block.  Draw k reads word k & 3 of lane (k >> 2) & 63; refill when k & 255 == 0.
+//   AHMC_DRAWS_PER_LANE 0 (rounds 3–6, for A/B runs): the four 16-lane rows compute four consecutive blocks, refill when k & 15 == 0.
+//   AHMC_DRAW_SCALAR_WORD 0 (default): the draw's word is selected per lane first (three v_cndmask), then read.  1 (round 7, measured
+//     and NOT taken): k is wave-uniform, so which of the block's four registers a draw reads can be a scalar branch around the
+//     v_readlane — three VALU fewer per draw, and slower: cfg2 2.966e9 against 3.004e9 leapfrog/s with the selects.  The selects are
+//     issue slots the other waves fill; the branch (readfirstlane -> s_cmp -> s_cbranch -> v_readlane) is latency on the chain of
+//     dependent stages every draw sits on (profiles/r7_experiments.md r7d).
+#ifndef AHMC_DRAWS_PER_LANE
+#define AHMC_DRAWS_PER_LANE 1
+#endif
+#ifndef AHMC_DRAW_SCALAR_WORD
+#define AHMC_DRAW_SCALAR_WORD 0
+#endif
 template <bool WIDE>
 struct DrawStreamT {
+  static constexpr uint32_t PERIOD = !WIDE ? 4u : (AHMC_DRAWS_PER_LANE ? 256u : 16u);  // draws per refill
   Rng rng;
   uint32_t k;
   Philox4 blk;
+  __device__ __forceinline__ uint32_t lane_block() const {  // which of the refill's blocks this lane computes
+    if constexpr (!WIDE) return 0u;
+    else if constexpr (AHMC_DRAWS_PER_LANE) return threadIdx.x & 63u;
+    else return (threadIdx.x & 63u) >> 4;
+  }
   __device__ __forceinline__ void init(const Rng& r) { rng = r; k = 0; }
   __device__ __forceinline__ void resume(const Rng& r, uint32_t k0) {  // continue a stream at draw k0
     rng = r;
     k = k0;
-    if constexpr (WIDE) {
-      if (k & 15u) blk = rng.raw(RNG_TRANSITION, ((k >> 4) << 2) + ((threadIdx.x & 63u) >> 4));
-    } else {
-      if (k & 3u) blk = rng.raw(RNG_TRANSITION, k >> 2);
-    }
+    if (k & (PERIOD - 1u)) blk = rng.raw(RNG_TRANSITION, ((k & ~(PERIOD - 1u)) >> 2) + lane_block());
   }
   __device__ __forceinline__ uint32_t word() {
-    if constexpr (WIDE) {
-      if ((k & 15u) == 0u) blk = rng.raw(RNG_TRANSITION, (k >> 2) + ((threadIdx.x & 63u) >> 4));
+    if ((k & (PERIOD - 1u)) == 0u) blk = rng.raw(RNG_TRANSITION, (k >> 2) + lane_block());
+    uint32_t w;
+    if constexpr (WIDE && AHMC_DRAW_SCALAR_WORD) {
+      w = 0;
     } else {
-      if ((k & 3u) == 0u) blk = rng.raw(RNG_TRANSITION, k >> 2);
+      const uint32_t lo = (k & 1u) ? blk.v[1] : blk.v[0], hi = (k & 1u) ? blk.v[3] : blk.v[2];
+      w = (k & 2u) ? hi : lo;
     }
-    const uint32_t lo = (k & 1u) ? blk.v[1] : blk.v[0], hi = (k & 1u) ? blk.v[3] : blk.v[2];
-    uint32_t w = (k & 2u) ? hi : lo;
     if constexpr (WIDE) {
-      const int row = __builtin_amdgcn_readfirstlane((int)((k >> 2) & 3u));  // k is the same in every lane of the chain
-      w = (uint32_t)__builtin_amdgcn_readlane((int)w, row * 16);
+      const uint32_t ks = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);  // k is the same in every lane of the chain
+      const int src = AHMC_DRAWS_PER_LANE ? (int)((ks >> 2) & 63u) : (int)(((ks >> 2) & 3u) * 16u);
+      if constexpr (AHMC_DRAW_SCALAR_WORD) {
+        // (the empty asm keeps the four arms a scalar branch: merged, they are four v_readlane and a scalar select)
+        switch (ks & 3u) {
+          case 0u: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[0], src); asm volatile(""); break;
+          case 1u: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[1], src); asm volatile(""); break;
+          case 2u: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[2], src); asm volatile(""); break;
+          default: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[3], src); asm volatile(""); break;
+        }
+      } else {
+        w = (uint32_t)__builtin_amdgcn_readlane((int)w, src);
+      }
     }
     ++k;
     return w;
@@ -271,6 +299,9 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   // 1.87e9 although 216 -> 212 VALU per leapfrog), so G <= 64 keeps two reductions.
   constexpr bool FUSE_M0 = !GENERAL && G > 64;
   constexpr bool ADAPT = MODE >= 3;  // MODE 0 / 1 + adapt!(…) after every transition, inside the kernel (AdaptK)
+  // Round 7: a chain that owns ONE wave takes the generalised U-turn decision as a scalar predicate straight from the reduction
+  // (ahmc_device.hpp: wave64_any_le0_pair).  G < 64 needs it per lane, G > 64 needs the sums themselves for the cross-wave exchange.
+  constexpr bool UTURN_ANY = G == 64 && AHMC_UTURN_ANY != 0;
   const bool strict = GENERAL && p.criterion == 2;
   const int NV = strict ? 3 : 2;  // vectors per pending level: A, RF (, RL)
   const int n_slots = NV * NLEV + NUTS_DORMANT + NUTS_CKPT;
@@ -724,9 +755,12 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
                 // the double reduction only inside an error band of 2⁻¹⁹ Σ(|p₀| + |p₁|): decisions identical, every GPU test green,
                 // and not faster: cfg2 draws 3.228e9 against 3.243e9 in-kernel, cfg3 2.41e9 against 2.54e9 whole loop.  The chain of
                 // dependent stages is as long as before and the DPP hazards leave wait states where the double version has work.)
-                group_allsum<G>(dots);
+                if constexpr (!UTURN_ANY) group_allsum<G>(dots);
               }
-              sub_term = AHMC_UNI(dots[0] <= 0) || AHMC_UNI(dots[1] <= 0);  // generalised_uturn_criterion (:619-621)
+              // generalised_uturn_criterion (:619-621).  One chain per wave: the two signs straight from the reduction's transposed
+              // register, without broadcasting the sums they belong to (wave64_any_le0_pair)
+              if constexpr (UTURN_ANY && !pre.value) sub_term = wave64_any_le0_pair(dots[0], dots[1]);
+              else sub_term = AHMC_UNI(dots[0] <= 0) || AHMC_UNI(dots[1] <= 0);
             } else {
               // StrictGeneralisedNoUTurn (:579-617).  F = the pending (first-built) half, S = the half
               // just completed; in built order the two extra checks are symmetric in the direction:
@@ -875,8 +909,12 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
               dots[0] += A_tree[e] * (minv[e] * cur.r[e]);
               dots[1] += A_tree[e] * (minv[e] * oth_r[e]);
             }
-            group_allsum<G>(dots);
-            turn = AHMC_UNI(dots[0] <= 0) || AHMC_UNI(dots[1] <= 0);
+            if constexpr (UTURN_ANY) {
+              turn = wave64_any_le0_pair(dots[0], dots[1]);
+            } else {
+              group_allsum<G>(dots);
+              turn = AHMC_UNI(dots[0] <= 0) || AHMC_UNI(dots[1] <= 0);
+            }
           } else {
             // strict at the top: (ρ_tree + r_sub.first ; ends other edge, sub.first) and
             //                    (r_start + ρ_sub ; ends start edge, current edge)
