@@ -176,6 +176,29 @@ RU_SIGNATURES = {
     "ahmc_get_metric_rank_update": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
 }
 
+# include/ahmc_lowrank_adapt.h: the optional mass-matrix adaptor of that metric (likewise: the HIP engine only)
+AHMC_LOWRANK_ADAPT_VERSION = 1
+AHMC_LOWRANK_MAX_ELL = 40
+
+
+class LowRankState(C.Structure):
+    """ahmc_lowrank_state"""
+    _fields_ = [
+        ("k", C.c_int64),
+        ("ell", C.c_int64),
+        ("seed", C.c_uint64),
+        ("n", C.c_int64),
+        ("n_fits", C.c_int64),
+    ]
+
+
+LR_SIGNATURES = {
+    "ahmc_lowrank_adapt_version": (_i32, []),
+    "ahmc_lowrank_adaptor_init": (_i32, [_vp, _i32, _f64, _i32, _i32, _i32, _i64, _i64, _u64]),
+    "ahmc_lowrank_get_state": (_i32, [_vp, C.POINTER(LowRankState), _vp, _vp, _vp, _vp, _vp]),
+    "ahmc_lowrank_set_state": (_i32, [_vp, C.POINTER(LowRankState), _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -220,6 +243,16 @@ class CLib:
             v = self.dll.ahmc_rank_update_version()
             if v != AHMC_RANK_UPDATE_VERSION:
                 raise ImportError(f"{self.path}: ahmc_rank_update version {v}, expected {AHMC_RANK_UPDATE_VERSION}")
+        # ahmc_lowrank_adapt.h: likewise
+        lr = [getattr(self.dll, name, None) for name in LR_SIGNATURES]
+        self.has_lowrank_adapt = all(fn is not None for fn in lr)
+        if self.has_lowrank_adapt:
+            for fn, (res, args) in zip(lr, LR_SIGNATURES.values()):
+                fn.restype = res
+                fn.argtypes = args
+            v = self.dll.ahmc_lowrank_adapt_version()
+            if v != AHMC_LOWRANK_ADAPT_VERSION:
+                raise ImportError(f"{self.path}: ahmc_lowrank_adapt version {v}, expected {AHMC_LOWRANK_ADAPT_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

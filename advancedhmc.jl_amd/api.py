@@ -477,6 +477,21 @@ class NutpieVar(MassMatrixAdaptor):
     estimator = 1  # AHMC_VAR_NUTPIE
 
 
+class LowRankVar(MassMatrixAdaptor):
+    """LowRankVar(D | metric, rank, oversample=8, seed=0): the estimator of RankUpdateEuclideanMetric — M⁻¹ = Diagonal(A) + B·Dm·Bᵀ
+    of rank `rank`, one for all chains, fitted to the draws of all of them (include/ahmc_lowrank_adapt.h; the arithmetic:
+    rank_update.lowrank_*).  The reference has no adaptor for this metric.  Usable alone or as the `pc` of NaiveHMCAdaptor /
+    StanHMCAdaptor; the engine's metric may be Unit, a shared (D,) Diag or a rank update of rank <= `rank`, and becomes a rank
+    update of rank `rank` when the adaptor is set up."""
+    lowrank = True
+
+    def __init__(self, metric, rank, oversample=8, seed=0):
+        if not isinstance(metric, AbstractMetric):
+            metric = RankUpdateEuclideanMetric(int(metric))
+        super().__init__(metric)
+        self.rank, self.oversample, self.seed = int(rank), int(oversample), int(seed)
+
+
 @dataclass
 class NaiveHMCAdaptor:
     """src/adaptation/Adaptation.jl:41-64"""
@@ -823,7 +838,37 @@ class Engine:
                       getattr(adaptor, "window_size", 25))
         pc = adaptor if isinstance(adaptor, MassMatrixAdaptor) else getattr(adaptor, "pc", None)
         self._call("ahmc_set_var_estimator", int(getattr(pc, "estimator", 0)))
+        if getattr(pc, "lowrank", False):
+            self._need_lowrank_adapt("LowRankVar")
+            self._call("ahmc_lowrank_adaptor_init", adaptor.code, float(adaptor.delta), ib, tb, ws, pc.rank, pc.oversample, pc.seed)
+            self.metric_kind = capi.METRIC_RANK_UPDATE
+            return
         self._call("ahmc_adaptor_init", adaptor.code, float(adaptor.delta), ib, tb, ws)
+
+    def _need_lowrank_adapt(self, what):
+        if not getattr(self.lib, "has_lowrank_adapt", False):
+            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_lowrank_adapt.h")
+
+    def lowrank_state(self):
+        """the low-rank adaptor's state (ahmc_lowrank_get_state) as a dict of the header fields and the float64 arrays mu, m2 (D,),
+        Z, Omega (D, ell), s0 (D,); None when the context has no such adaptor"""
+        if not getattr(self.lib, "has_lowrank_adapt", False):
+            return None
+        st = capi.LowRankState()
+        if self.lib.dll.ahmc_lowrank_get_state(self._ctx, C.byref(st), None, None, None, None, None) != capi.OK:
+            return None
+        D, L = self.D, int(st.ell)
+        out = {"mu": np.empty(D), "m2": np.empty(D), "Z": np.empty((D, L), order="F"), "s0": np.empty(D), "Omega": np.empty((D, L), order="F")}
+        self._call("ahmc_lowrank_get_state", C.byref(st), *(capi.as_ptr(out[k]) for k in ("mu", "m2", "Z", "s0", "Omega")))
+        out.update({k: getattr(st, k) for k, _ in capi.LowRankState._fields_})
+        return out
+
+    def set_lowrank_state(self, state: dict):
+        """ahmc_lowrank_set_state: the adaptor must have been set up with the same rank and oversampling"""
+        self._need_lowrank_adapt("set_lowrank_state")
+        st = capi.LowRankState(**{k: int(state[k]) for k, _ in capi.LowRankState._fields_})
+        arrs = [np.asfortranarray(state[k], dtype=np.float64) for k in ("mu", "m2", "Z", "s0", "Omega")]
+        self._call("ahmc_lowrank_set_state", C.byref(st), *(capi.as_ptr(a) for a in arrs))
 
     def adapt(self, i, n_adapts, theta=None, alpha=None, grad=None):
         """adapt!(h, κ, adaptor, i, n_adapts, z_or_θ, α) (src/sampler.jl:72-90); θ/α default to the
@@ -880,9 +925,16 @@ class Engine:
         return {"adaptor": {k: getattr(st, k) for k, _ in capi.AdaptorState._fields_}, "da": da, "welford": wv,
                 "theta": z.theta, "r": z.r, "lp": z.lp.value, "grad": z.lp.gradient,
                 "metric": self.get_metric(), "metric_kind": self.metric_kind, "stepsize": self.get_stepsize(),
-                "stepsize_scalar": bool(self.info("stepsize_scalar")), "accum": acc}
+                "stepsize_scalar": bool(self.info("stepsize_scalar")), "accum": acc, "lowrank": self.lowrank_state()}
 
     def set_state(self, state: dict):
+        lr = state.get("lowrank")
+        if lr is not None and state["adaptor"]["kind"] in (capi.ADAPT_MASSMATRIX, capi.ADAPT_NAIVE, capi.ADAPT_STAN):  # the low-rank adaptor first: it shapes the metric and the estimator, the saved values then overwrite both
+            ad = state["adaptor"]
+            self._need_lowrank_adapt("set_state")
+            self._call("ahmc_lowrank_adaptor_init", int(ad["kind"]), float(ad["delta"]), int(ad["init_buffer"]), int(ad["term_buffer"]),
+                       int(ad["window_size"]), int(lr["k"]), int(lr["ell"]) - int(lr["k"]), int(lr["seed"]))
+            self.set_lowrank_state(lr)
         if state.get("metric_kind") == capi.METRIC_RANK_UPDATE:  # (A, B, D)
             self._set_rank_update(*state["metric"])
         elif state["metric"] is not None:

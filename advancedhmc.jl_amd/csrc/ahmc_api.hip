@@ -5,12 +5,14 @@
 #include "ahmc_hip.h"
 #include "ahmc_diag.h"
 #include "ahmc_rank_update.h"
+#include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
 #include "ahmc_dense_mn.hpp"
 #include "ahmc_wide.hpp"
 #include "ahmc_diag.hpp"
 #include "ahmc_rank_update.hpp"
+#include "ahmc_lowrank_adapt.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: the entry points are resolved at run time (ahmc_multi_host.hpp)
@@ -238,6 +240,17 @@ struct Ctx : CtxBase {
   size_t ru_cap = 0;
   int64_t ru_off[7] = {0, 0, 0, 0, 0, 0, 0};
   int ru_k = 0;
+  // the low-rank mass-matrix adaptor of that metric (ahmc_lowrank_adapt_host.hpp): parameters, counters, one slab of doubles
+  struct LowRank {
+    bool on = false;
+    int k = 0, ell = 0;
+    uint64_t seed = 0;
+    int64_t n = 0, n_fits = 0;
+    double* buf = nullptr;
+    size_t cap = 0;
+    bool have_V = false;      // V holds the eigenvectors of a fit the next window has not started from yet
+    std::vector<double> V;
+  } lr;
   T* dn_C = nullptr;   // M⁻¹·P (dense metric + dense target), see dn_refresh_fused
   T* dn_Asw = nullptr; // P and M⁻¹·P in MFMA-fragment order (k_dense_swizzle), refreshed at the start of every batch
   int64_t dn_epoch_launches = 0;
@@ -275,7 +288,7 @@ struct Ctx : CtxBase {
     void* bufs[] = {vbase, tbase, ibase, lbase, tparams, minv, sqrt_minv, scratch, order, order_hist, adaptk_dev, hmc_H, da_m, da_eps, da_mu, da_xbar,
                     da_Hbar, wv_mu, wv_M, wv_var, ext_th, ext_alpha, redo, znorm, dn_minv, dn_uinv, dn_W, dn_es, dn_RB, dn_VB,
                     dn_S, dn_active, dn_list, wg_mu, wg_M, ext_g, wc_mu, wc_M, wc_S, wc_cov, stage[0], stage[1], dn_C, ext_gstage, ext_lpstage,
-                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp, ru_buf};
+                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp, ru_buf, lr.buf};
     for (void* b : bufs)
       if (b) (void)hipFree(b);
     for (auto* v : {&ev_pool, &ev_pending, &ev_pending_warm})
@@ -411,6 +424,7 @@ int launch_fill_caches_builtin(Ctx<T>* c) {
 }
 
 #include "ahmc_rank_update_host.hpp"
+#include "ahmc_lowrank_adapt_host.hpp"
 #include "ahmc_dense_host.hpp"
 #include "ahmc_dense_mn_host.hpp"
 #include "ahmc_ext_host.hpp"
@@ -1033,7 +1047,7 @@ int adaptor_init(Ctx<T>* c, int kind, double delta, int ib, int tb, int ws) {
   c->stan_i = 0;
   c->windows_n_adapts = 0;
   if (kind == AHMC_ADAPT_NONE) return AHMC_OK;
-  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && kind != AHMC_ADAPT_STEPSIZE) {  // (the reference has no MassMatrixAdaptor for it)
+  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && kind != AHMC_ADAPT_STEPSIZE && !c->lr.on) {  // (the reference has no MassMatrixAdaptor for it; ours: ahmc_lowrank_adaptor_init)
     c->adapt_kind = AHMC_ADAPT_NONE;
     c->adapting = false;
     return fail(c, AHMC_ERR_UNSUPPORTED, "adaptor_init: RankUpdateEuclideanMetric has no mass-matrix adaptor (MassMatrixAdaptor / NaiveHMCAdaptor / "
@@ -1108,12 +1122,16 @@ int adaptor_init(Ctx<T>* c, int kind, double delta, int ib, int tb, int ws) {
 template <class T>
 int adapt(Ctx<T>* c, int64_t i, int64_t n_adapts, const T* th_ext = nullptr, const T* alpha_ext = nullptr, const T* g_ext = nullptr) {
   if (c->adapt_kind == AHMC_ADAPT_NONE || i > n_adapts) return AHMC_OK;
-  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && c->adapt_kind != AHMC_ADAPT_STEPSIZE)  // (an adaptor set up for an earlier metric)
+  if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && c->adapt_kind != AHMC_ADAPT_STEPSIZE && !c->lr.on)  // (an adaptor set up for an earlier metric)
     return fail(c, AHMC_ERR_UNSUPPORTED, "adapt: RankUpdateEuclideanMetric has no mass-matrix adaptor (the adaptor was set up for another metric)");
+  if (c->lr.on && c->adapt_kind != AHMC_ADAPT_STEPSIZE && c->metric_kind != AHMC_METRIC_RANK_UPDATE_CTX)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "adapt: the low-rank adaptor fits a RankUpdateEuclideanMetric and the context's metric was replaced by another kind: "
+                                         "set up an adaptor again");
   if (i == n_adapts) c->adapting = false;
   const bool has_ss = c->adapt_kind != AHMC_ADAPT_MASSMATRIX;
   const bool has_mm = c->adapt_kind != AHMC_ADAPT_STEPSIZE && c->metric_kind == AHMC_METRIC_DIAG;
   const bool has_cov = c->adapt_kind != AHMC_ADAPT_STEPSIZE && c->metric_kind == AHMC_METRIC_DENSE;  // WelfordCov
+  const bool has_lr = c->adapt_kind != AHMC_ADAPT_STEPSIZE && c->lr.on;                               // the low-rank estimator
   bool do_push = false, do_update = false, wv_reset = false, da_reset = false;
   if (c->adapt_kind == AHMC_ADAPT_STAN) {
     if (i == 1 || c->windows_n_adapts != n_adapts) {  // initialize! (also after a resume that did not carry the schedule)
@@ -1123,15 +1141,15 @@ int adapt(Ctx<T>* c, int64_t i, int64_t n_adapts, const T* th_ext = nullptr, con
     c->stan_i += 1;  // adapt!(tp::StanHMCAdaptor, ...) (stan_adaptor.jl:137-159)
     const bool in_window = c->stan_i >= c->windows.window_start && c->stan_i <= c->windows.window_end;
     const bool window_end = std::find(c->windows.splits.begin(), c->windows.splits.end(), c->stan_i) != c->windows.splits.end();
-    if (in_window && (has_mm || has_cov)) {
+    if (in_window && (has_mm || has_cov || has_lr)) {
       do_push = true;
       do_update = window_end;
     }
     if (window_end) {
       da_reset = true;
-      wv_reset = has_mm || has_cov;
+      wv_reset = has_mm || has_cov || has_lr;
     }
-  } else if (has_mm || has_cov) {
+  } else if (has_mm || has_cov || has_lr) {
     do_push = true;
     do_update = true;
   }
@@ -1169,6 +1187,19 @@ int adapt(Ctx<T>* c, int64_t i, int64_t n_adapts, const T* th_ext = nullptr, con
     if (do_push) rc2 = dn_cov_push(c, th);
     if (!rc2 && do_update) rc2 = dn_cov_update(c);
     if (!rc2 && wv_reset) rc2 = dn_cov_init(c);
+    if (rc2) return rc2;
+  }
+  if (has_lr && (do_push || wv_reset)) {
+    const T* th = c->th;
+    if (th_ext) {  // caller-supplied θ
+      if (!c->ext_th) { int rc2 = dev_alloc(c, &c->ext_th, (size_t)a.DN); if (rc2) return rc2; }
+      HIPCHK(hipMemcpyAsync(c->ext_th, th_ext, sizeof(T) * a.DN, hipMemcpyDefault, c->stream));
+      th = c->ext_th;
+    }
+    int rc2 = AHMC_OK;
+    if (do_push) rc2 = lr_push(c, th);
+    if (!rc2 && do_update) rc2 = lr_fit(c);
+    if (!rc2 && wv_reset) rc2 = lr_restart(c);
     if (rc2) return rc2;
   }
   if (has_mm && (do_push || wv_reset)) {
@@ -1837,6 +1868,7 @@ int32_t ahmc_find_good_stepsize(ahmc_ctx* ctx, double initial_step_size, int32_t
 int32_t ahmc_adaptor_init(ahmc_ctx* ctx, int32_t kind, double delta, int32_t init_buffer, int32_t term_buffer, int32_t window_size) {
   FOR_CTX_MUT(ctx, {
     if (kind < AHMC_ADAPT_NONE || kind > AHMC_ADAPT_STAN) return fail(c, AHMC_ERR_ARGUMENT, "adaptor_init: unknown adaptor kind");
+    c->lr.on = false;  // (a low-rank adaptor ends here: include/ahmc_lowrank_adapt.h)
     int rc = adaptor_init(c, kind, delta, init_buffer, term_buffer, window_size);
     if (rc) return rc;
     return AHMC_OK;
@@ -1908,7 +1940,10 @@ static int32_t sample_from_impl(ahmc_ctx* ctx, const ahmc_kernel_cfg* cfg, int64
     if (!c->have_point) return fail(c, AHMC_ERR_STATE, "sample before set_position");
     if (drop_warmup && c->adapt_kind == AHMC_ADAPT_NONE)
       return fail(c, AHMC_ERR_ARGUMENT, "Cannot drop warmup samples if there is no adaptation phase.");  // src/sampler.jl:172
-    if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && c->adapt_kind != AHMC_ADAPT_NONE && c->adapt_kind != AHMC_ADAPT_STEPSIZE)
+    if (c->lr.on && c->adapt_kind != AHMC_ADAPT_NONE && c->adapt_kind != AHMC_ADAPT_STEPSIZE && c->metric_kind != AHMC_METRIC_RANK_UPDATE_CTX)
+      return fail(c, AHMC_ERR_UNSUPPORTED, "sample: the low-rank adaptor fits a RankUpdateEuclideanMetric and the context's metric was replaced by another kind: "
+                                           "set up an adaptor again");
+    if (c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX && c->adapt_kind != AHMC_ADAPT_NONE && c->adapt_kind != AHMC_ADAPT_STEPSIZE && !c->lr.on)
       return fail(c, AHMC_ERR_UNSUPPORTED, "sample: RankUpdateEuclideanMetric has no mass-matrix adaptor (the adaptor was set up for another metric)");
     // a resumed run must continue where the restored state stopped: a Stan adaptor counts its own calls (state.i,
     // stan_adaptor.jl:137-159), so while it is adapting the absolute iteration is known and a mismatch is an error rather
@@ -2431,6 +2466,23 @@ int32_t ahmc_set_metric_rank_update(ahmc_ctx* ctx, const void* A, const void* B,
 
 int32_t ahmc_get_metric_rank_update(ahmc_ctx* ctx, void* A, void* B, void* Dm, int64_t* k) {
   FOR_CTX(ctx, { return ru_get_metric(c, A, B, Dm, k); });
+}
+
+// ---- include/ahmc_lowrank_adapt.h: the mass-matrix adaptor of that metric (ahmc_lowrank_adapt.hpp, ahmc_lowrank_adapt_host.hpp) -------
+int32_t ahmc_lowrank_adapt_version(void) { return AHMC_LOWRANK_ADAPT_VERSION; }
+
+int32_t ahmc_lowrank_adaptor_init(ahmc_ctx* ctx, int32_t kind, double delta, int32_t init_buffer, int32_t term_buffer, int32_t window_size,
+                                  int64_t k, int64_t oversample, uint64_t seed) {
+  FOR_CTX_MUT(ctx, { return lr_adaptor_init(c, kind, delta, init_buffer, term_buffer, window_size, k, oversample, seed); });
+}
+
+int32_t ahmc_lowrank_get_state(ahmc_ctx* ctx, ahmc_lowrank_state* state, double* mu, double* m2, double* Z, double* s0, double* Omega) {
+  FOR_CTX(ctx, { return lr_get_state(c, state, mu, m2, Z, s0, Omega); });
+}
+
+int32_t ahmc_lowrank_set_state(ahmc_ctx* ctx, const ahmc_lowrank_state* state, const double* mu, const double* m2, const double* Z,
+                               const double* s0, const double* Omega) {
+  FOR_CTX_MUT(ctx, { return lr_set_state(c, state, mu, m2, Z, s0, Omega); });
 }
 
 }  // extern "C"

@@ -511,5 +511,6 @@ end
 
 include("AdvancedHMCMI355XDiag.jl")  # summarystats_device: include/ahmc_diag.h
 include("AdvancedHMCMI355XRankUpdate.jl")  # set_metric!(z, ::RankUpdateEuclideanMetric): include/ahmc_rank_update.h
+include("AdvancedHMCMI355XLowRankAdapt.jl")  # lowrank_adaptor_init!: include/ahmc_lowrank_adapt.h
 
 end # module
