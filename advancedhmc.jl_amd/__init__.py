@@ -13,6 +13,7 @@ from .build import build_hip_library  # noqa: E402
 from . import shard  # noqa: E402,F401
 from . import diagnostics  # noqa: E402,F401
 from . import rank_update  # noqa: E402,F401
+from . import glm  # noqa: E402,F401
 from .diagnostics import ess, bundle_samples, summarystats  # noqa: E402,F401
 
 __version__ = "0.1.0"

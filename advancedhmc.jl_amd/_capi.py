@@ -199,6 +199,16 @@ LR_SIGNATURES = {
     "ahmc_lowrank_set_state": (_i32, [_vp, C.POINTER(LowRankState), _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/ahmc_glm.h: the optional generalised-linear-model target (likewise: the HIP engine only)
+AHMC_GLM_VERSION = 1
+TARGET_GLM = 8
+GLM_BERNOULLI_LOGIT, GLM_POISSON_LOG, GLM_GAUSSIAN_IDENTITY = 0, 1, 2
+GLM_SIGNATURES = {
+    "ahmc_glm_version": (_i32, []),
+    "ahmc_set_target_glm": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _f64]),
+    "ahmc_get_target_glm": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_f64)]),
+    "ahmc_glm_pointwise": (_i32, [_vp, _vp, _vp]),
+}
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -253,6 +263,16 @@ class CLib:
             v = self.dll.ahmc_lowrank_adapt_version()
             if v != AHMC_LOWRANK_ADAPT_VERSION:
                 raise ImportError(f"{self.path}: ahmc_lowrank_adapt version {v}, expected {AHMC_LOWRANK_ADAPT_VERSION}")
+        # ahmc_glm.h: likewise
+        glm = [getattr(self.dll, name, None) for name in GLM_SIGNATURES]
+        self.has_glm = all(fn is not None for fn in glm)
+        if self.has_glm:
+            for fn, (res, args) in zip(glm, GLM_SIGNATURES.values()):
+                fn.restype = res
+                fn.argtypes = args
+            v = self.dll.ahmc_glm_version()
+            if v != AHMC_GLM_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm version {v}, expected {AHMC_GLM_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _capi as capi
 from . import rank_update as _ru
+from . import glm as _glm
 from ._capi import ArgumentError
 
 
@@ -298,6 +299,47 @@ class KernelTarget:
     user: object = None
     kind: int = capi.TARGET_KERNEL
     params: Optional[np.ndarray] = None
+
+
+class GLMTarget:
+    """A generalised linear model as the target (include/ahmc_glm.h; arithmetic: advancedhmc.jl_amd/glm.py):
+        ℓπ(θ) = Σ_i ℓ(y_i, (Xθ + offset)_i) − ½ Σ_d p_d θ_d²,    X (n_obs, D), D = X.shape[1]
+    with `family` "bernoulli_logit" (0 <= y <= 1), "poisson_log" (y >= 0) or "gaussian_identity" (scale = 1/σ²).  The prior is
+    N(0, prior_scale²) per coefficient — `prior_scale` a scalar or (D,) — or given as its precision `prior_prec`; neither: flat.
+    The engine evaluates all chains at once, X·Θ and Xᵀ·U on the MFMA units.  HIP engine only (the CPU checker takes the same
+    density as `ExternalTarget(D, lambda th: glm.logdensity(...))` or a host KernelTarget)."""
+    kind = capi.TARGET_GLM
+    params = None
+
+    def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0):
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64).ravel()
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.size != X.shape[0]:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: X {X.shape}, y {y.shape}")
+        try:
+            self.family = _glm.family_code(family)
+        except ValueError as e:
+            raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+        if prior_scale is not None and prior_prec is not None:
+            raise ArgumentError(capi.ERR_ARGUMENT, "GLMTarget: give prior_scale or prior_prec, not both")
+        self.X = np.asfortranarray(X)
+        self.y = y
+        self.D = X.shape[1]
+        self.n_obs = X.shape[0]
+        if prior_scale is not None:
+            prior_prec = 1.0 / np.square(np.asarray(prior_scale, dtype=np.float64))
+        self.prior_prec = None if prior_prec is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prior_prec, dtype=np.float64), (self.D,)))
+        self.offset = None if offset is None else np.asarray(offset, dtype=np.float64).ravel()
+        if self.offset is not None and self.offset.size != self.n_obs:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: offset {self.offset.shape}, n_obs {self.n_obs}")
+        self.scale = float(scale)
+
+    def logdensity(self, theta):
+        """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
+        return _glm.logdensity(self.family, self.X, self.y, theta, self.offset, self.prior_prec, self.scale)
+
+    def __repr__(self):
+        return f"GLMTarget(n_obs={self.n_obs}, D={self.D}, family={self.family})"
 
 
 @dataclass
@@ -632,6 +674,9 @@ class Engine:
                                                  n_params=-1 if p is None else p.size)
             self._call("ahmc_set_target_plugin", so.encode(), capi.as_ptr(p), 0 if p is None else p.size)
             return
+        if isinstance(target, GLMTarget):
+            self._set_glm(target)
+            return
         if isinstance(target, KernelTarget):
             h = target.handle
             self._kernel_keepalive = (h, target.user)  # (a ctypes callback must outlive the context's use of it)
@@ -640,6 +685,30 @@ class Engine:
             self._call("ahmc_set_target_kernel", int(target.handle_kind), hp, int(target.block_threads), int(target.chains_per_block), up)
             return
         self._call("ahmc_set_target", target.kind, capi.as_ptr(p), 0 if p is None else p.size)
+
+    def _need_glm(self, what):
+        if not getattr(self.lib, "has_glm", False):
+            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_glm.h")
+
+    def _set_glm(self, t):
+        self._need_glm("GLMTarget")
+        if t.D != self.D:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: X has {t.D} columns, the context has D = {self.D}")
+        X = np.asfortranarray(t.X, dtype=self.dtype)
+        y = np.ascontiguousarray(t.y, dtype=self.dtype)
+        off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
+        p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
+        self._call("ahmc_set_target_glm", int(t.family), int(t.n_obs), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p), float(t.scale))
+
+    def glm_pointwise(self):
+        """(η, ℓ(y_i, η_i)) at the context's current θ, each (n_obs, N): ahmc_glm_pointwise"""
+        self._need_glm("glm_pointwise")
+        n = C.c_int64()
+        self._call("ahmc_get_target_glm", None, C.byref(n), None)
+        eta = np.empty((n.value, self.N), dtype=self.dtype, order="F")
+        ll = np.empty((n.value, self.N), dtype=self.dtype, order="F")
+        self._call("ahmc_glm_pointwise", capi.as_ptr(eta), capi.as_ptr(ll))
+        return eta, ll
 
     def _need_rank_update(self, what):
         if not getattr(self.lib, "has_rank_update", False):

@@ -5,6 +5,7 @@
 #include "ahmc_hip.h"
 #include "ahmc_diag.h"
 #include "ahmc_rank_update.h"
+#include "ahmc_glm.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -12,6 +13,7 @@
 #include "ahmc_wide.hpp"
 #include "ahmc_diag.hpp"
 #include "ahmc_rank_update.hpp"
+#include "ahmc_glm.hpp"
 #include "ahmc_lowrank_adapt.hpp"
 
 #include <dlfcn.h>
@@ -240,6 +242,13 @@ struct Ctx : CtxBase {
   size_t ru_cap = 0;
   int64_t ru_off[7] = {0, 0, 0, 0, 0, 0, 0};
   int ru_k = 0;
+  // AHMC_TARGET_GLM (ahmc_glm_host.hpp): one slab of X, Xᵀ, y, offset, p, U, partial, gs at glm_off[0..7]
+  T* glm_buf = nullptr;
+  int64_t glm_off[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int glm_family = 0;
+  int64_t glm_nobs = 0;
+  bool glm_has_offset = false;
+  double glm_scale = 1;
   // the low-rank mass-matrix adaptor of that metric (ahmc_lowrank_adapt_host.hpp): parameters, counters, one slab of doubles
   struct LowRank {
     bool on = false;
@@ -288,7 +297,7 @@ struct Ctx : CtxBase {
     void* bufs[] = {vbase, tbase, ibase, lbase, tparams, minv, sqrt_minv, scratch, order, order_hist, adaptk_dev, hmc_H, da_m, da_eps, da_mu, da_xbar,
                     da_Hbar, wv_mu, wv_M, wv_var, ext_th, ext_alpha, redo, znorm, dn_minv, dn_uinv, dn_W, dn_es, dn_RB, dn_VB,
                     dn_S, dn_active, dn_list, wg_mu, wg_M, ext_g, wc_mu, wc_M, wc_S, wc_cov, stage[0], stage[1], dn_C, ext_gstage, ext_lpstage,
-                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp, ru_buf, lr.buf};
+                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp, ru_buf, glm_buf, lr.buf};
     for (void* b : bufs)
       if (b) (void)hipFree(b);
     for (auto* v : {&ev_pool, &ev_pending, &ev_pending_warm})
@@ -425,6 +434,7 @@ int launch_fill_caches_builtin(Ctx<T>* c) {
 
 #include "ahmc_rank_update_host.hpp"
 #include "ahmc_lowrank_adapt_host.hpp"
+#include "ahmc_glm_host.hpp"
 #include "ahmc_dense_host.hpp"
 #include "ahmc_dense_mn_host.hpp"
 #include "ahmc_ext_host.hpp"
@@ -1496,6 +1506,7 @@ int32_t ahmc_set_target(ahmc_ctx* ctx, int32_t kind, const void* params, int64_t
     int64_t need = 0;
     if (kind == AHMC_TARGET_PLUGIN || kind == AHMC_TARGET_KERNEL)
       return fail(c, AHMC_ERR_ARGUMENT, "set_target: use ahmc_set_target_plugin / ahmc_set_target_kernel");
+    if (kind == AHMC_TARGET_GLM) return fail(c, AHMC_ERR_ARGUMENT, "set_target: use ahmc_set_target_glm (include/ahmc_glm.h)");
     switch (kind) {
       case AHMC_TARGET_ISO_GAUSS: case AHMC_TARGET_FUNNEL: case AHMC_TARGET_HIER_GAUSS: case AHMC_TARGET_EXTERNAL: need = 0; break;
       case AHMC_TARGET_DIAG_GAUSS: need = 2 * c->D; break;
@@ -1521,6 +1532,7 @@ int32_t ahmc_set_target(ahmc_ctx* ctx, int32_t kind, const void* params, int64_t
     }
     if (c->tparams) (void)hipFree(c->tparams);
     c->tparams = np_dev;
+    if (int rc = glm_release(c)) return rc;
     c->target_kind = kind;
     c->have_point = false;
     c->order_valid = false; c->sched = {};   // (a dispatch order and a launch length measured on another density say nothing about this one)
@@ -1584,6 +1596,7 @@ int32_t ahmc_set_target_plugin(ahmc_ctx* ctx, const char* plugin_so, const void*
     if (c->plugin_dl) dlclose(c->plugin_dl);  // (the stream is idle: nothing of the previous plugin's code is running)
     c->plugin_dl = dl;
     c->plugin_ops = static_cast<const TargetOps<T>*>(d->ops);
+    if (int rc = glm_release(c)) return rc;
     c->target_kind = AHMC_TARGET_PLUGIN;
     c->have_point = false;
     c->order_valid = false; c->sched = {};
@@ -1603,6 +1616,7 @@ int32_t ahmc_set_target_kernel(ahmc_ctx* ctx, int32_t handle_kind, void* handle,
     c->uk_block = block_threads;
     c->uk_cpb = chains_per_block;
     c->uk_user = user;
+    if (int rc = glm_release(c)) return rc;
     c->target_kind = AHMC_TARGET_KERNEL;
     c->have_point = false;
     c->order_valid = false; c->sched = {};
@@ -2483,6 +2497,32 @@ int32_t ahmc_lowrank_get_state(ahmc_ctx* ctx, ahmc_lowrank_state* state, double*
 int32_t ahmc_lowrank_set_state(ahmc_ctx* ctx, const ahmc_lowrank_state* state, const double* mu, const double* m2, const double* Z,
                                const double* s0, const double* Omega) {
   FOR_CTX_MUT(ctx, { return lr_set_state(c, state, mu, m2, Z, s0, Omega); });
+}
+
+// ---- include/ahmc_glm.h: the generalised-linear-model target (ahmc_glm.hpp, ahmc_glm_host.hpp) ----------------------------------------
+int32_t ahmc_glm_version(void) { return AHMC_GLM_VERSION; }
+
+int32_t ahmc_set_target_glm(ahmc_ctx* ctx, int32_t family, int64_t n_obs, const void* X, const void* y, const void* offset, const void* prior_prec,
+                            double scale) {
+  FOR_CTX_MUT(ctx, {
+    int rc = glm_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), scale);
+    if (rc) return rc;
+    return dn_refresh_fused(c);
+  });
+}
+
+int32_t ahmc_get_target_glm(ahmc_ctx* ctx, int32_t* family, int64_t* n_obs, double* scale) {
+  FOR_CTX(ctx, {
+    if (c->target_kind != AHMC_TARGET_GLM) return fail(c, AHMC_ERR_ARGUMENT, "get_target_glm: no GLM is bound (ahmc_set_target_glm)");
+    if (family) *family = c->glm_family;
+    if (n_obs) *n_obs = c->glm_nobs;
+    if (scale) *scale = c->glm_scale;
+    return AHMC_OK;
+  });
+}
+
+int32_t ahmc_glm_pointwise(ahmc_ctx* ctx, void* eta_out, void* loglik_out) {
+  FOR_CTX_MUT(ctx, { return glm_pointwise(c, eta_out, loglik_out); });
 }
 
 }  // extern "C"

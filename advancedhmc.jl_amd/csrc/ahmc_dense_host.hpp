@@ -7,7 +7,7 @@
 template <class T>
 bool dense_engine(const Ctx<T>* c) {
   return c->wide || c->metric_kind == AHMC_METRIC_DENSE || c->metric_kind == AHMC_METRIC_RANK_UPDATE_CTX || c->target_kind == AHMC_TARGET_DENSE_GAUSS ||
-         c->target_kind == AHMC_TARGET_KERNEL;
+         listed_target(c);
 }
 
 // the velocity v = M⁻¹r is carried by the recurrence v ← v − ϵ/2·w, w = M⁻¹g (a non-diagonal M⁻¹: dense or rank-update).  Whether
@@ -75,6 +75,7 @@ int dn_wide_target(Ctx<T>* c, const int* list, int64_t n, const T* X, T* Y, cons
 template <class T>
 int dn_other_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   if (c->target_kind == AHMC_TARGET_KERNEL) return dn_user_target(c, list, n, sanitize_lp);
+  if (c->target_kind == AHMC_TARGET_GLM) return glm_target(c, list, n, sanitize_lp);
   if (c->wide) return dn_wide_target(c, list, n, (const T*)c->th, c->g);
   return launch_fill_caches_builtin(c);
 }
@@ -676,7 +677,7 @@ int dn_nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion
   p.accum = accum ? 1 : 0;
   p.samples_out = samples_dev;
   const bool dm = dn_recurrent(c), dt = c->target_kind == AHMC_TARGET_DENSE_GAUSS;
-  const bool wt = c->wide && c->target_kind != AHMC_TARGET_KERNEL;  // wide built-in family: k_w_target reads θ′ from / writes g′ to the pool point itself
+  const bool wt = c->wide && !listed_target(c);  // wide built-in family: k_w_target reads θ′ from / writes g′ to the pool point itself
   DP2<T> q2 = make_dp2(c, n_trans, !(dt || wt));
   if (adapt_i0 >= 0) {
     q2.adapt_ss = 1;

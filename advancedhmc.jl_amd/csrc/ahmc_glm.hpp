@@ -1,0 +1,302 @@
+// ahmc_glm.hpp — device side of the generalised-linear-model target (include/ahmc_glm.h; host side: ahmc_glm_host.hpp; the
+// arithmetic is defined by advancedhmc.jl_amd/glm.py).
+//
+// With the design matrix X (n_obs, D) and all chains' positions Θ (D, N) the linear predictor is ONE product X·Θ and the gradient
+// ONE product Xᵀ·U — every chain shares X, as every chain shares M⁻¹ in k_dgemm, whose tiling, operand layout and k order these
+// kernels take over (64×64 output tile per workgroup, or 64×16 when few chains are running; K stepped by GB_K through LDS, k
+// ascending into one accumulator per element, zero padding past the end).  An accumulator therefore holds the k-ordered fma chain
+// of its element, whichever tile shape computed it, and a chain's bits depend on (n_obs, D, family, element type) only — not on
+// N, on the chain's column, on the chain list or on the tile shape.  No atomics; no kernel uses scratch.
+#pragma once
+
+#include "ahmc_dense.hpp"
+
+namespace ahmc {
+
+// Xᵀ·U runs over K = n_obs, a serial MFMA chain of n_obs/4 per wave however few chains are left; it is cut into slices of this
+// fixed length (a multiple of GB_K), each a workgroup's own chain, and the slice sums are added in ascending order
+// (k_glm_gsum).  The same constant is glm.K_SLICE of the mirror.
+constexpr int GLM_K_SLICE = 1024;
+static_assert(GLM_K_SLICE % GB_K == 0, "a slice is whole k tiles");
+
+// tile shapes: BN = 64 (four waves as 2×2, each 32×32 = 2×2 MFMA tiles) or BN = 16 (four waves stacked, each one 16×16 MFMA tile)
+template <int BN>
+struct GlmShape {
+  static_assert(BN == 64 || BN == 16, "64×64 or 64×16");
+  static constexpr int WR = BN == 64 ? 2 : 4;              // waves along the rows
+  static constexpr int MI = BN == 64 ? 2 : 1;              // MFMA tiles of a wave, each way
+  static constexpr int BE = BN / 16;                       // B elements a thread stages per k tile
+  static constexpr int LDA = GB_M + GB_PAD;
+  static constexpr int LDB = BN + (BN == 64 ? GB_PAD : 4);
+  static constexpr int SMEM = 2 * GB_K * (LDA + LDB);      // elements: the two LDS buffers of A and B; the epilogues reuse them
+  static constexpr int LDE = GB_M + 1;                     // epilogue staging, [column][row] or [row][column]
+  static_assert(BN * LDE <= SMEM && GB_M * (BN + 1) <= SMEM, "the epilogue's staging fits into the tile buffers");
+};
+
+// (row block, column block) of a workgroup.  BN = 64: a 1-D grid of row_blocks × 8·⌈col_blocks/8⌉ in k_dgemm's XCD-aware order (the
+// row blocks of one column block share an L2); BN = 16: grid (row_blocks, col_blocks).
+template <int BN>
+__device__ __forceinline__ void glm_block(int nrb, int& rblk, int64_t& cb) {
+  if constexpr (BN == 64) {
+    const unsigned lin = blockIdx.x;
+    const unsigned xcd = lin & 7u, slot = lin >> 3;
+    cb = (int64_t)(slot / nrb) * 8 + xcd;
+    rblk = (int)(slot % nrb);
+  } else {
+    rblk = blockIdx.x;
+    cb = blockIdx.y;
+  }
+}
+
+// acc += A[m0 .. m0+63, k0 .. k1) · B[k0 .. k1), this workgroup's BN columns].  A is column-major with leading dimension lda and M
+// rows; Bcol is the column this THREAD stages (nullptr: a column past the list, zeros), indexed by k.  k_dgemm_small's pipeline:
+// tile t in LDS buffer t & 1, tile t+1 in registers, the loads of tile t+2 issued before tile t is multiplied; one barrier per tile.
+// On return all waves have passed the last barrier: smem is free.
+template <class T, int BN>
+__device__ __forceinline__ void glm_tile_product(const T* __restrict__ A, int64_t lda, int M, int m0, const T* __restrict__ Bcol, int k0, int k1,
+                                                 T* __restrict__ smem, typename Mfma<T>::acc_t (&acc)[GlmShape<BN>::MI][GlmShape<BN>::MI]) {
+  using S = GlmShape<BN>;
+  using Mf = Mfma<T>;
+  T* As = smem;                       // [2][GB_K][LDA]
+  T* Bs = smem + 2 * GB_K * S::LDA;   // [2][GB_K][LDB]
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wm = (w % S::WR) * 16 * S::MI, wn = (w / S::WR) * 16 * S::MI;
+  const int ai = (tid & 31) * 2, ak = tid >> 5;                       // A tile: rows ai, ai+1 of k-rows ak and ak+8
+  constexpr int KT = GB_K / S::BE;                                    // threads that share a B column
+  const int bn = tid / KT, bk = (tid % KT) * S::BE;                   // B tile: column bn, k-rows bk .. bk+BE-1
+  const bool arow0 = m0 + ai < M, arow1 = m0 + ai + 1 < M;
+  const T* Ap = A + (m0 + ai);
+  T ra[2][4], rb[2][S::BE];
+  auto load_tile = [&](int kb, T (&a)[4], T (&b)[S::BE]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int k = kb + ak + 8 * q;
+      a[2 * q + 0] = (k < k1 && arow0) ? Ap[(int64_t)k * lda] : T(0);
+      a[2 * q + 1] = (k < k1 && arow1) ? Ap[(int64_t)k * lda + 1] : T(0);
+    }
+#pragma unroll
+    for (int e = 0; e < S::BE; ++e) {
+      const int k = kb + bk + e;
+      b[e] = (Bcol && k < k1) ? Bcol[k] : T(0);
+    }
+  };
+  auto store_tile = [&](int buf, const T (&a)[4], const T (&b)[S::BE]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) As[(buf * GB_K + ak + 8 * q) * S::LDA + ai + e] = a[2 * q + e];
+#pragma unroll
+    for (int e = 0; e < S::BE; ++e) Bs[(buf * GB_K + bk + e) * S::LDB + bn] = b[e];
+  };
+  const int nk = (k1 - k0 + GB_K - 1) / GB_K;
+  const int nk_round = (nk + 1) / 2 * 2;  // tiles past k1 are all zero: harmless to multiply
+  load_tile(k0, ra[0], rb[0]);
+  load_tile(k0 + GB_K, ra[1], rb[1]);
+  store_tile(0, ra[0], rb[0]);
+  __syncthreads();
+  for (int kt = 0; kt < nk_round; kt += 2) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      load_tile(k0 + (kt + s + 2) * GB_K, ra[s], rb[s]);
+#pragma unroll
+      for (int ks = 0; ks < GB_K / 4; ++ks) {
+        const int kq = ks * 4 + (lane >> 4), l16 = lane & 15;
+        T a[S::MI], b[S::MI];
+#pragma unroll
+        for (int i = 0; i < S::MI; ++i) {
+          a[i] = As[(s * GB_K + kq) * S::LDA + wm + 16 * i + l16];
+          b[i] = Bs[(s * GB_K + kq) * S::LDB + wn + 16 * i + l16];
+        }
+#pragma unroll
+        for (int i = 0; i < S::MI; ++i)
+#pragma unroll
+          for (int j = 0; j < S::MI; ++j) acc[i][j] = Mf::mma(a[i], b[j], acc[i][j]);
+      }
+      store_tile(s ^ 1, ra[s ^ 1], rb[s ^ 1]);
+      __syncthreads();
+    }
+  }
+}
+
+// (ℓ(y, η), u = ∂ℓ/∂η) of one observation.  Every multiply-add is an explicit fma, so the two tile shapes compile to the same
+// arithmetic.  FAM: AHMC_GLM_BERNOULLI_LOGIT (0), AHMC_GLM_POISSON_LOG (1), AHMC_GLM_GAUSSIAN_IDENTITY (2).
+template <class T, int FAM>
+__device__ __forceinline__ void glm_link(T y, T eta, T scale, T& ll, T& u) {
+  if constexpr (FAM == 0) {
+    const T e = exp(-fabs(eta));
+    const T sp = (eta > T(0) ? eta : T(0)) + log1p(e);   // softplus(η): finite for any finite η
+    const T d = T(1) + e;
+    const T sig = eta >= T(0) ? T(1) / d : e / d;        // σ(η) from the same exp(−|η|)
+    ll = fma(y, eta, -sp);
+    u = y - sig;
+  } else if constexpr (FAM == 1) {
+    const T ex = exp(eta);
+    ll = fma(y, eta, -ex);
+    u = y - ex;
+  } else {
+    const T r = y - eta;
+    u = scale * r;
+    ll = (T(-0.5) * u) * r;
+  }
+}
+
+// η = X·Θ + offset for the listed chains, and from it in registers u → U (n_obs, N) and the tile's Σ_rows ℓ → partial[row block][chain].
+// Tile rows are observations, tile columns chains, K = D.  η itself is stored only on request (ahmc_glm_pointwise: eta_out / ll_out,
+// (n_obs, N) arrays).  U leaves through LDS so that a wave writes 64 consecutive observations of one chain; ℓ is summed over the
+// tile's 64 rows in ascending row order by one thread per column (rows past n_obs contribute +0).
+template <class T, int FAM, int BN>
+__global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const T* __restrict__ y, const T* __restrict__ off, T scale, const T* __restrict__ th,
+                                                 T* __restrict__ U, T* __restrict__ partial, int n_obs, int D, int64_t ncols, int64_t N,
+                                                 const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out) {
+  using S = GlmShape<BN>;
+  using Mf = Mfma<T>;
+  __shared__ T smem[S::SMEM];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nrb = (n_obs + GB_M - 1) / GB_M;
+  int rblk;
+  int64_t cb;
+  glm_block<BN>(nrb, rblk, cb);
+  const int m0 = rblk * GB_M;
+  const int64_t n0 = cb * BN;
+  if (n0 >= ncols) return;
+  typename Mf::acc_t acc[S::MI][S::MI];
+#pragma unroll
+  for (int i = 0; i < S::MI; ++i)
+#pragma unroll
+    for (int j = 0; j < S::MI; ++j) acc[i][j] = typename Mf::acc_t{0, 0, 0, 0};
+  {
+    const int bn = tid / (GB_K / S::BE);
+    const int64_t bcol = n0 + bn < ncols ? (idx ? (int64_t)idx[n0 + bn] : n0 + bn) : -1;
+    glm_tile_product<T, BN>(X, (int64_t)n_obs, n_obs, m0, bcol >= 0 ? th + bcol * D : nullptr, 0, D, smem, acc);
+  }
+  const int wm = (w % S::WR) * 16 * S::MI, wn = (w / S::WR) * 16 * S::MI;
+  T ll[S::MI][S::MI][4];
+  // u → smem[column][row]
+#pragma unroll
+  for (int ti = 0; ti < S::MI; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < S::MI; ++tj) {
+      const int cl = wn + tj * 16 + (lane & 15);
+      const int64_t j = n0 + cl;
+      const int64_t col = j < ncols ? (idx ? (int64_t)idx[j] : j) : -1;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int rl = wm + ti * 16 + Mf::row(lane, v);
+        const int row = m0 + rl;
+        T l = T(0), u = T(0);
+        if (row < n_obs && col >= 0) {
+          const T eta = off ? acc[ti][tj][v] + off[row] : acc[ti][tj][v];
+          glm_link<T, FAM>(y[row], eta, scale, l, u);
+          if (eta_out) eta_out[row + col * n_obs] = eta;
+          if (ll_out) ll_out[row + col * n_obs] = l;
+        }
+        ll[ti][tj][v] = l;
+        smem[cl * S::LDE + rl] = u;
+      }
+    }
+  __syncthreads();
+  for (int cl = w; cl < BN; cl += 4) {  // a wave per column: 64 consecutive observations
+    const int64_t j = n0 + cl;
+    if (j < ncols && m0 + lane < n_obs) {
+      const int64_t col = idx ? (int64_t)idx[j] : j;
+      U[(m0 + lane) + col * n_obs] = smem[cl * S::LDE + lane];
+    }
+  }
+  __syncthreads();
+  // ℓ → smem[row][column], then the column sums
+#pragma unroll
+  for (int ti = 0; ti < S::MI; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < S::MI; ++tj)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) smem[(wm + ti * 16 + Mf::row(lane, v)) * (BN + 1) + wn + tj * 16 + (lane & 15)] = ll[ti][tj][v];
+  __syncthreads();
+  if (tid < BN && n0 + tid < ncols) {
+    const int64_t col = idx ? (int64_t)idx[n0 + tid] : n0 + tid;
+    T s = T(0);
+    for (int r = 0; r < GB_M; ++r) s += smem[r * (BN + 1) + tid];
+    partial[(int64_t)rblk * N + col] = s;
+  }
+}
+
+// Xᵀ·U for the listed chains.  Tile rows are coefficients, tile columns chains, K = the workgroup's slice of the observations; the
+// A operand is the transposed copy Xt (D, n_obs) made when the target was set.  One slice (n_obs <= GLM_K_SLICE): the epilogue
+// writes g = −acc + p∘θ to the chain's column of g.  More: the slice's sum goes to gs[slice][chain][d] and k_glm_gsum finishes.
+template <class T, int BN>
+__global__ __launch_bounds__(256) void k_glm_grad(const T* __restrict__ Xt, const T* __restrict__ U, const T* __restrict__ prec, const T* __restrict__ th,
+                                                  T* __restrict__ g, T* __restrict__ gs, int n_obs, int D, int64_t ncols, int64_t N,
+                                                  const int* __restrict__ idx, int n_slices) {
+  using S = GlmShape<BN>;
+  using Mf = Mfma<T>;
+  __shared__ T smem[S::SMEM];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nrb1 = (D + GB_M - 1) / GB_M;
+  int rs;
+  int64_t cb;
+  glm_block<BN>(nrb1 * n_slices, rs, cb);
+  const int slice = rs / nrb1, m0 = (rs % nrb1) * GB_M;
+  const int64_t n0 = cb * BN;
+  if (n0 >= ncols) return;
+  typename Mf::acc_t acc[S::MI][S::MI];
+#pragma unroll
+  for (int i = 0; i < S::MI; ++i)
+#pragma unroll
+    for (int j = 0; j < S::MI; ++j) acc[i][j] = typename Mf::acc_t{0, 0, 0, 0};
+  {
+    const int bn = tid / (GB_K / S::BE);
+    const int64_t bcol = n0 + bn < ncols ? (idx ? (int64_t)idx[n0 + bn] : n0 + bn) : -1;
+    const int k0 = slice * GLM_K_SLICE, k1 = k0 + GLM_K_SLICE < n_obs ? k0 + GLM_K_SLICE : n_obs;
+    glm_tile_product<T, BN>(Xt, (int64_t)D, D, m0, bcol >= 0 ? U + bcol * n_obs : nullptr, k0, k1, smem, acc);
+  }
+  const int wm = (w % S::WR) * 16 * S::MI, wn = (w / S::WR) * 16 * S::MI;
+#pragma unroll
+  for (int ti = 0; ti < S::MI; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < S::MI; ++tj) {
+      const int64_t j = n0 + wn + tj * 16 + (lane & 15);
+      const int64_t col = j < ncols ? (idx ? (int64_t)idx[j] : j) : -1;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int row = m0 + wm + ti * 16 + Mf::row(lane, v);
+        if (row < D && col >= 0) {
+          if (n_slices == 1) g[row + col * D] = fma(prec[row], th[row + col * D], -acc[ti][tj][v]);
+          else gs[((int64_t)slice * N + col) * D + row] = acc[ti][tj][v];
+        }
+      }
+    }
+}
+
+// g = −(Σ_slices gs, ascending) + p∘θ for the listed chains (n_slices > 1)
+template <class T>
+__global__ __launch_bounds__(256) void k_glm_gsum(const T* __restrict__ gs, const T* __restrict__ prec, const T* __restrict__ th, T* __restrict__ g, int D,
+                                                  int64_t ncols, int64_t N, const int* __restrict__ idx, int n_slices) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ncols * D) return;
+  const int64_t j = i / D, col = idx ? (int64_t)idx[j] : j;
+  const int d = (int)(i % D);
+  T s = gs[col * D + d];
+  for (int sl = 1; sl < n_slices; ++sl) s += gs[((int64_t)sl * N + col) * D + d];
+  g[d + col * D] = fma(prec[d], th[d + col * D], -s);
+}
+
+// ℓπ = Σ_row blocks partial − ½ Σ_d p_d θ_d², one wave per chain (as k_d_coldot): lane l sums the row blocks and the coefficients
+// l, l+64, … in ascending order, then wave_allsum2.  sanitize_lp = 0: the caller's next kernel sanitises ℓπ as it reads it.
+template <class T>
+__global__ __launch_bounds__(256) void k_glm_lp(const T* __restrict__ partial, const T* __restrict__ prec, const T* __restrict__ th, T* __restrict__ lp, int nrb,
+                                                int D, int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= ncols) return;
+  const int64_t c = idx ? (int64_t)idx[j] : j;
+  T s[2] = {0, 0};
+  for (int rb = lane; rb < nrb; rb += 64) s[0] += partial[(int64_t)rb * N + c];
+  for (int d = lane; d < D; d += 64) {
+    const T t = th[c * D + d];
+    s[1] = fma(prec[d] * t, t, s[1]);
+  }
+  wave_allsum2<64>(s[0], s[1]);
+  const T v = fma(T(-0.5), s[1], s[0]);
+  if (lane == 0) lp[c] = sanitize_lp ? sanitize(v) : v;
+}
+
+}  // namespace ahmc

@@ -512,5 +512,6 @@ end
 include("AdvancedHMCMI355XDiag.jl")  # summarystats_device: include/ahmc_diag.h
 include("AdvancedHMCMI355XRankUpdate.jl")  # set_metric!(z, ::RankUpdateEuclideanMetric): include/ahmc_rank_update.h
 include("AdvancedHMCMI355XLowRankAdapt.jl")  # lowrank_adaptor_init!: include/ahmc_lowrank_adapt.h
+include("AdvancedHMCMI355XGLM.jl")  # set_target!(z, ::GLMTarget), glm_pointwise: include/ahmc_glm.h
 
 end # module
