@@ -7,7 +7,9 @@ Translation units (compiled in parallel; objects cached OUTSIDE the repository â
 `$XDG_CACHE_HOME/ahmc_build`, else `~/.cache/ahmc_build` â€” so that nothing but the linked .so and its two digest stamps
 ever lands in the tree that `gpurun` snapshots; each object carries the digest of the files it was compiled from â€” taken from the compiler's own dependency list â€” so that a change to the host
 side or to the dense engine does not recompile the eight log-density instantiations):
-  ahmc_api.hip                      host side of the C ABI + the target-independent kernels
+  ahmc_api.hip                      host side of the C ABI + the target-independent kernels; it includes one ahmc_*_host.hpp per
+                                    subsystem (the sampling loop of ahmc_sample: ahmc_sample_host.hpp, with its launch-length
+                                    controller ahmc_draw_sched.hpp, which the host compiler alone can build: tests/test_draw_sched.py)
   ahmc_inst.hip  Ã— {f32,f64} Ã— {iso,diag,funnel,hier}
                                     the kernels that evaluate a built-in log-density family, which is
                                     a compile-time parameter (see ahmc_inst.hpp)

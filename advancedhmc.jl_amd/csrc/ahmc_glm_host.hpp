@@ -160,7 +160,7 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   c->glm_scale = scale;
   c->target_kind = AHMC_TARGET_GLM;
   c->have_point = false;
-  c->order_valid = false; c->sched = {};
+  invalidate_schedule(c);
   return AHMC_OK;
 }
 

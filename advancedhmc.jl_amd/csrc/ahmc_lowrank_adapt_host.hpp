@@ -115,7 +115,7 @@ int lr_adaptor_init(Ctx<T>* c, int kind, double delta, int ib, int tb, int ws, i
   }
   int rc = ru_set_metric(c, hA.data(), hB.data(), hD.data(), k);
   if (rc) return rc;
-  c->order_valid = false; c->sched = {};
+  invalidate_schedule(c);
   c->lr.on = true;
   c->lr.k = (int)k;
   c->lr.ell = (int)std::min<int64_t>(D, k + oversample);
@@ -372,7 +372,7 @@ int lr_fit(Ctx<T>* c) {
   for (int a = 0; a < k; ++a) hD[a + (size_t)a * k] = (T)(sh * dm[a]);
   c->lr.V.swap(V);
   c->lr.have_V = true;
-  c->order_valid = false; c->sched = {};
+  invalidate_schedule(c);
   return ru_set_metric(c, hA.data(), hB.data(), hD.data(), (int64_t)k);
 }
 

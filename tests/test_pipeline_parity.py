@@ -235,3 +235,34 @@ def test_dispatch_schedules_leave_the_chains_untouched(hip, monkeypatch, D, targ
         np.testing.assert_array_equal(res[4]["sum_theta"], ref[4]["sum_theta"], err_msg=str(env))
         if hip.backend == "hip:gfx950" and ("AHMC_NUTS_DRAW_BATCH" in env or "AHMC_NUTS_BATCH" in env or "AHMC_NUTS_SCHED" in env):
             assert res[5] != ref[5], (env, res[5], ref[5])   # the switch did change the launch plan
+
+
+def test_launch_plan_where_it_is_deterministic(hip, monkeypatch):
+    """Where no clock decides it, the number of sampling launches is the even-split arithmetic of the launch-length controller
+    (csrc/ahmc_draw_sched.hpp: even_split): 300 kept draws with AHMC_NUTS_DRAW_BATCH=7 are ⌈300/7⌉ = 43 launches (of 7 and 6),
+    with AHMC_NUTS_SCHED=0 AHMC_NUTS_BATCH=6 they are 300/6 = 50.  `nuts_launches` counts the launches of the sampling kernel
+    (MODE 0) only: neither the fused warm-up nor the redo passes enter.  The draws (through the host-buffer staging pipe) are the
+    same bit for bit under both plans."""
+    D, N, n_adapts, n = 32, 1024, 40, 340
+    names = ("AHMC_NUTS_NO_ORDER", "AHMC_NUTS_ORDER_REFRESH", "AHMC_NUTS_DRAW_BATCH", "AHMC_NUTS_FIRST_BATCH", "AHMC_NUTS_BATCH", "AHMC_NUTS_SCHED",
+             "AHMC_NORMALS_PREFETCH", "AHMC_NORMALS_PREFETCH_MAX_MB")
+    res = []
+    for env, launches in (({"AHMC_NUTS_DRAW_BATCH": "7"}, 43), ({"AHMC_NUTS_SCHED": "0", "AHMC_NUTS_BATCH": "6"}, 50)):
+        for v in names:
+            monkeypatch.delenv(v, raising=False)
+        for kk, vv in env.items():
+            monkeypatch.setenv(kk, vv)
+        e, k, ad = _setup(hip, D, N, "funnel", 77)
+        e.find_good_stepsize()
+        e.adaptor_init(ad)
+        out = np.zeros((D, N, n - n_adapts), order="F")
+        l0 = e.info("nuts_launches")
+        e.run(k, n, n_adapts, drop_warmup=True, samples_out=out)
+        e.sync()
+        got = e.info("nuts_launches") - l0
+        print(f"{env}: {got} sampling launches (expected {launches})")
+        res.append((out, e.get_stepsize(), e.stats()["n_steps"]))
+        e.close()
+        assert got == launches, (env, got, launches)
+    for a, b in zip(res[0], res[1]):
+        np.testing.assert_array_equal(a, b)
