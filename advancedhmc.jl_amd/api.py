@@ -1114,10 +1114,12 @@ class Engine:
 
     INFO = {"group_lanes": 0, "elems_per_lane": 1, "nuts_launches": 2, "nuts_batch": 3, "iteration": 4, "nuts_kernel_ns": 5,
             "nuts_warm_launches": 6, "nuts_warm_kernel_ns": 7, "dense_gemm_launches": 8, "dense_gemm_small_launches": 9, "dense_pipelines": 10,
-            "dense_pool": 11, "nuts_draw_batch": 12, "dense_epoch_launches": 13, "stepsize_scalar": 14, "wide": 15}
+            "dense_pool": 11, "nuts_draw_batch": 12, "dense_epoch_launches": 13, "stepsize_scalar": 14, "wide": 15,
+            "norm_tail_hits": 16, "norm_prefetch_hits": 17}
 
     # keys the CPU checker (oracle/) does not answer, and what they mean there: it has no thread geometry, so no wide mode either
-    CHECKER_ONLY_ZERO = ("wide",)
+    # (nor a launch whose normals could be made ahead of time)
+    CHECKER_ONLY_ZERO = ("wide", "norm_tail_hits", "norm_prefetch_hits")
 
     def info(self, key):
         """engine introspection (ahmc_get_info): thread geometry, NUTS launch count / batch, iteration, wide context"""

@@ -171,7 +171,8 @@ struct Ctx : CtxBase {
   hipStream_t stream_norm = nullptr;
   hipEvent_t ev_norm_ready = nullptr, ev_z2_free = nullptr;
   bool z2_has_reader = false;       // ev_z2_free marks the end of the last k_nuts that read what is now znorm2
-  struct NormPre { bool valid = false; uint64_t iter = 0, k0 = 0, k1 = 0, chain_offset = 0, chain_stride = 0; int64_t n = 0; } npre;
+  bool z2_norm_stream_busy = false; // a k_normals on stream_norm writes znorm2 and c->stream has not waited for ev_norm_ready since
+  struct NormPre { bool valid = false, in_tail = false; uint64_t iter = 0, k0 = 0, k1 = 0, chain_offset = 0, chain_stride = 0; int64_t n = 0; } npre;
   // (ABI v6) ahmc_set_ref_compat: the reference's matrix-mode early exit (Q1) for ahmc_leapfrog and static EndPointTS transitions
   bool ref_compat = false;
   T* compat_save = nullptr;         // θ, r, g (3·D·N) + the scalar slab (14·N): the state a dry run must give back
@@ -179,6 +180,9 @@ struct Ctx : CtxBase {
   int64_t norm_hint = 0;            // set by the sampling loop before a launch: transitions of the launch that will follow it (0: unknown)
   int norm_prefetch = -1;           // -1 undecided, 0 off (AHMC_NORMALS_PREFETCH=0 or no memory for the second buffer), 1 on
   int64_t norm_prefetch_hits = 0;
+  // Round 8: … or by waves appended to the k_nuts launch before (G = 64; tail_normals_plan, AHMC_NORMALS_TAIL): on c->stream itself
+  int norm_tail = -1;               // -1 undecided, 0 off for this context (no memory for the second buffer), 1 on
+  int64_t norm_tail_hits = 0;       // launches whose normals were made in the tail of the launch before
   int32_t* redo = nullptr;  // per-chain "redo in the log domain" flags of the NUTS fast pass
   int nuts_blocks = 0;
   // static multinomial
@@ -589,6 +593,10 @@ int launch_nuts(Ctx<T>* c, KP<T> p, int max_depth) {
     p.hmc_H = reinterpret_cast<T*>(tl_buf);
   }
 #endif
+  // (the waves that make the next launch's normals: behind the last chain's, in workgroups of the same size)
+#if AHMC_TAIL_NORMALS
+  if (p.tail_waves) blocks = (int)(((int64_t)p.n_chunks + p.tail_waves + wpb - 1) / wpb);
+#endif
   if (const TargetOps<T>* o = ops_for(c)) o->nuts(c->G, c->E, MODE, (unsigned)blocks, wpb, smem, c->stream, p);
   HIPCHK(hipGetLastError());
 #if AHMC_WAVE_TIMELINE
@@ -663,6 +671,14 @@ int nuts_event_begin(Ctx<T>* c, std::pair<hipEvent_t, hipEvent_t>& ev) {
 #include "ahmc_sample_host.hpp"
 
 template <class T>
+void set_tail(KP<T>& p, const KP<T>& from) {  // the tail job of a k_nuts launch (KP::tail_*), or none
+#if AHMC_TAIL_NORMALS
+  p.tail_out = from.tail_out; p.tail_n_trans = from.tail_n_trans; p.tail_iteration = from.tail_iteration;
+  p.tail_rows = from.tail_rows; p.tail_waves = from.tail_waves;
+#endif
+}
+
+template <class T>
 int nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion, int sampler, double refresh_alpha,
                     bool accum, int n_trans = 1, T* samples_dev = nullptr, const AdaptK<T>* adapt_host = nullptr) {
   if (!c->have_point) return fail(c, AHMC_ERR_STATE, "transition before set_position");
@@ -691,13 +707,21 @@ int nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion, i
   p.n_chunks = (unsigned int)((c->N + CPW - 1) / CPW);
   p.redo = c->redo;
   static const bool no_linw = getenv("AHMC_NUTS_LOGW") != nullptr;
-  const int64_t hint = c->norm_hint;  // (the launch that follows this one: prefetch_next_normals)
+  const int64_t hint = c->norm_hint;  // (the launch that follows this one: tail_normals_plan / prefetch_next_normals)
   c->norm_hint = 0;
+  // its normals from the tail of this launch's MODE 0 / MODE 3 pass?
+  const bool fast_pass = !no_linw && (adapt_host || (sampler == AHMC_TS_MULTINOMIAL && criterion == AHMC_TC_GENERALISED && c->integ_kind != AHMC_INTEGRATOR_TEMPERED));
+  const bool in_tail = fast_pass && tail_normals_applies(c, hint, refresh_alpha);
   rc = normals_for_launch(c, p, n_trans);
   if (rc) return rc;
   p.n_trans = n_trans;
   p.znorm = c->znorm;
   p.samples_out = samples_dev;
+  KP<T> p_tail = p;  // (the fields alone are taken from it, below)
+  if (in_tail) {
+    rc = tail_normals_plan(c, p_tail, hint, n_trans);
+    if (rc) return rc;
+  }
   const bool no_order = getenv("AHMC_NUTS_NO_ORDER") != nullptr;  // (read per call: the tests toggle it)
   static const bool order_adapt = getenv("AHMC_NUTS_ORDER_ADAPT") ? atoi(getenv("AHMC_NUTS_ORDER_ADAPT")) != 0 : false;  // measured: no gain (a per-transition launch lasts as long as its longest tree)
   if ((n_trans > 1 || order_adapt) && !c->eps_scalar && !no_order) {
@@ -729,11 +753,13 @@ int nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion, i
       std::pair<hipEvent_t, hipEvent_t> ev;
       rc = nuts_event_begin(c, ev);
       if (rc) return rc;
+      set_tail(p, p_tail);
       rc = launch_nuts<T, 3>(c, p, max_depth);
       HIPCHK(hipEventRecord(ev.second, c->stream));
       c->ev_pending_warm.push_back(ev);
       if (rc) return rc;
       c->nuts_warm_launches += 1;
+      set_tail(p, KP<T>{});  // (the redo pass has no tail)
       p.redo_only = 1;
       rc = launch_nuts<T, 4>(c, p, max_depth);
     } else {
@@ -748,11 +774,13 @@ int nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion, i
       std::pair<hipEvent_t, hipEvent_t> ev;
       rc = nuts_event_begin(c, ev);
       if (rc) return rc;
+      set_tail(p, p_tail);
       rc = launch_nuts<T, 0>(c, p, max_depth);
       HIPCHK(hipEventRecord(ev.second, c->stream));
       c->ev_pending.push_back(ev);
       if (rc) return rc;
       c->nuts_launches += 1;
+      set_tail(p, KP<T>{});  // (the redo pass has no tail)
       p.redo_only = 1;
       rc = launch_nuts<T, 1>(c, p, max_depth);
     } else {
@@ -765,6 +793,7 @@ int nuts_transition(Ctx<T>* c, int max_depth, double delta_max, int criterion, i
   }
   if (rc) return rc;
   c->iteration += (uint64_t)n_trans;
+  if (in_tail && tail_normals_planned(p_tail)) return tail_normals_done(c, p_tail);
   return prefetch_next_normals(c, p, hint, refresh_alpha);
 }
 
@@ -1836,7 +1865,16 @@ int32_t ahmc_sample_reserve(ahmc_ctx* ctx, const ahmc_kernel_cfg* cfg, int64_t n
   FOR_CTX_MUT(ctx, {
     if (!cfg) return fail(c, AHMC_ERR_ARGUMENT, "sample_reserve: cfg is NULL");
     if (n_samples < 1 || !cfg->nuts || dense_engine(c) || c->target_kind == AHMC_TARGET_EXTERNAL) return AHMC_OK;  // nothing to reserve ahead of time
-    return reserve_normals(c, std::min<int64_t>(nuts_batch(c), n_samples));
+    int64_t k = std::min<int64_t>(nuts_batch(c), n_samples);
+    int rc = reserve_normals(c, k);
+    if (rc) return rc;
+    if (c->znorm_cap_trans > 0) k = std::min<int64_t>(k, c->znorm_cap_trans);
+    // a run of several launches that make each other's normals in their tails (tail_normals_plan) writes a second buffer of the same size
+    if (n_samples > k && tail_normals_applies(c, k, cfg->refresh_alpha)) {
+      if (c->norm_tail < 0) c->norm_tail = 1;
+      rc = second_normals_buffer(c, (size_t)k * (size_t)c->D * (size_t)c->N, c->norm_tail);
+    }
+    return rc;
   });
 }
 
@@ -1924,6 +1962,8 @@ int32_t ahmc_get_info(ahmc_ctx* ctx, int32_t what, int64_t* out) {
       case AHMC_INFO_DENSE_EPOCH_LAUNCHES: *out = c->dn_epoch_launches; break;
       case AHMC_INFO_NUTS_DRAW_BATCH: *out = c->sched.phase == DrawSched::SETTLED ? c->sched.best_len : 0; break;
       case AHMC_INFO_STEPSIZE_SCALAR: *out = c->eps_scalar ? 1 : 0; break;
+      case AHMC_INFO_NORM_TAIL_HITS: *out = c->norm_tail_hits; break;
+      case AHMC_INFO_NORM_PREFETCH_HITS: *out = c->norm_prefetch_hits; break;
       default: return fail(c, AHMC_ERR_ARGUMENT, "get_info: unknown key");
     }
     return AHMC_OK;

@@ -7,6 +7,14 @@
 
 namespace ahmc {
 
+#ifndef AHMC_TAIL_NORMALS
+// 1: the sampling and warm-up kernels of a chain that owns one wave (G = 64, MODE 0 / 3) accept waves BEHIND their chain waves that make
+// the momentum normals of the launch that follows (KP::tail_*, k_nuts in ahmc_nuts.hpp; the host side: tail_normals_plan).  Workgroups are dealt in block order, so
+// those waves start when no chain is left to start: they run in the slots the launch's tail leaves empty, beside its oldest waves.
+// 0: the kernels of round 7, instruction for instruction.
+#define AHMC_TAIL_NORMALS 1
+#endif
+
 // Everything a kernel needs, passed by value.  Arrays are (D,N) column-major / (N,).
 // The context keeps its per-chain arrays in four slabs so that the kernel arguments stay small
 // (a fat kernarg struct exhausts the 102 SGPRs and pushes every uniform value into VGPRs):
@@ -79,6 +87,16 @@ struct KP {
   int64_t n_steps;  // k_leapfrog
   T init_eps;
   int max_iters;
+  // k_nuts, G = 64, MODE 0 / 3: the standard normals of the launch that FOLLOWS this one, made by extra waves behind the chain waves
+  // (normals_rows, ahmc_nuts.hpp).  All zero: no such waves.  At the END of the struct: the offsets of everything above are round 7's
+  // (and with AHMC_TAIL_NORMALS = 0 so is its size, which places the kernels' hidden arguments).
+#if AHMC_TAIL_NORMALS
+  T* tail_out;              // (tail_n_trans, N, D): the context's second normals buffer, which no wave of this launch reads
+  int tail_n_trans;         // transitions of the following launch
+  uint32_t tail_iteration;  // its first Philox iteration
+  int tail_rows;            // rows (one transition of one chain) per tail wave
+  unsigned int tail_waves;  // waves appended to the grid
+#endif
 };
 // LDS / scratch layout of k_nuts (ahmc_nuts.hpp), needed by the host launch plan as well
 constexpr int NUTS_NSC = 3;      // T scalars per pending level: w, Σα, ΔH_max
@@ -700,9 +718,48 @@ __global__ __launch_bounds__(256) void k_adapt_wv(AdaptP<T> a) {
 
 // standard normals of the momentum draws of `n_trans` consecutive transitions: element d of chain c
 // at transition kt = Box–Muller half (d & 1) of Philox block (chain, iteration+kt, MOMENTUM, d >> 1)
+//
+// By ROWS: a row is one (transition, chain) pair, row = kt·N + c, i.e. (D+1)/2 Box–Muller pairs written to out[row·D ..].  One wave makes the
+// rows [row0, row1) — both wave-uniform — and its lanes stride over the pairs of a row: chain, iteration and key are then scalars (so are the
+// products of the first Philox rounds that depend on them alone), and the index is split into (kt, c) once per wave, not twice per pair.
+// The values are Rng::normal_pair's, whoever calls this: k_normals, or the waves k_nuts appends behind its chains.
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+  return (int64_t)((uint64_t)hi << 32 | lo);
+}
+template <class T>
+__device__ __forceinline__ void normals_rows(const KP<T>& p, T* __restrict__ out, uint32_t iter0, uint32_t purpose, int64_t row0, int64_t row1, int lane64) {
+  const int npairs = (p.D + 1) / 2;
+  uint32_t kt = (uint32_t)(row0 / p.N);
+  int64_t c = row0 - (int64_t)kt * p.N;
+  T* dst_row = out + row0 * p.D;
+  for (int64_t row = row0; row < row1; ++row) {
+    Rng rng = make_rng(p, c);
+    rng.iter = iter0 + kt;
+    for (int pair = lane64; pair < npairs; pair += 64) {
+      double a, b;
+      rng.normal_pair(purpose, (uint32_t)pair, a, b);
+      T* dst = dst_row + 2 * pair;
+      dst[0] = (T)a;
+      if (2 * pair + 1 < p.D) dst[1] = (T)b;
+    }
+    dst_row += p.D;
+    if (++c == p.N) { c = 0; ++kt; }
+  }
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void k_normals(KP<T> p, T* __restrict__ out, int n_trans, uint32_t purpose) {
   const int64_t pairs_per_chain = (p.D + 1) / 2;
+  if (pairs_per_chain > 32) {  // a row fills more than half a wave: the waves share the rows out in equal consecutive runs
+    const int64_t rows = p.N * n_trans, waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const int64_t per_wave = (rows + waves - 1) / waves;
+    const int64_t row0 = wave_uniform(((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * per_wave);
+    const int64_t row1 = row0 + per_wave < rows ? row0 + per_wave : rows;
+    if (row0 < rows) normals_rows(p, out, p.iteration, purpose, row0, row1, (int)(threadIdx.x & 63));
+    return;
+  }
+  // short rows (D <= 64): a thread per pair, whatever row it belongs to
   const int64_t total = pairs_per_chain * p.N * n_trans;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t kt = i / (pairs_per_chain * p.N);

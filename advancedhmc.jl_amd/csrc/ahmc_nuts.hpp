@@ -273,6 +273,20 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   // A chain that owns whole waves makes every per-chain predicate wave-uniform; saying so (a ballot is uniform by
   // construction) turns the exec-mask save/restore of divergent branches into scalar branches and keeps the
   // predicates in SGPRs instead of VGPR 0/1 values.
+#if AHMC_TAIL_NORMALS
+  // Before anything of a chain is live: a wave behind the last chunk makes its rows of the NEXT launch's normals and is done.  It writes a
+  // buffer that no wave of this launch reads, and the launch that reads it is ordered behind this one on the stream: nothing to synchronise.
+  if constexpr (G == 64 && (MODE == 0 || MODE == 3)) {
+    const unsigned int wave_id = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wave_id >= p.n_chunks) {
+      const unsigned int tw = (unsigned int)__builtin_amdgcn_readfirstlane((int)(wave_id - p.n_chunks));
+      const int64_t rows = (int64_t)p.tail_n_trans * p.N, row0 = (int64_t)tw * p.tail_rows;
+      if (tw < p.tail_waves && row0 < rows)
+        normals_rows(p, p.tail_out, p.tail_iteration, (uint32_t)RNG_MOMENTUM, row0, row0 + p.tail_rows < rows ? row0 + p.tail_rows : rows, (int)(threadIdx.x & 63));
+      return;
+    }
+  }
+#endif
 #define AHMC_UNI(b) (CPW == 1 ? (__builtin_amdgcn_ballot_w64(b) != 0) : (b))
   // any lane of the wave?  For a chain that owns the wave the predicate is already wave-uniform (built from AHMC_UNI values):
   // testing it directly is a scalar branch, a ballot of it would re-materialise the lane mask (v_cndmask + v_cmp).

@@ -11,7 +11,7 @@ unsigned normals_grid(const Ctx<T>* c, int64_t n) {
 }
 
 // standard normals of the n_trans momentum refreshes (rand_momentum, src/metric.jl:290-309) in c->znorm: already made beside the
-// launch before (prefetch_next_normals), or made now
+// launch before (prefetch_next_normals), in its tail (tail_normals_plan), or made now
 template <class T>
 int normals_for_launch(Ctx<T>* c, const KP<T>& p, int n_trans) {
   const size_t need = (size_t)n_trans * (size_t)c->D * (size_t)c->N;
@@ -20,12 +20,13 @@ int normals_for_launch(Ctx<T>* c, const KP<T>& p, int n_trans) {
                    np.chain_offset == (uint64_t)p.chain_offset && np.chain_stride == (uint64_t)p.chain_stride && c->znorm2_elems >= need;
   np.valid = false;   // (used or stale: either way the buffer's content is spent)
   if (hit) {
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_norm_ready, 0));
+    // (made by the waves behind the launch before, on c->stream itself: this launch is ordered behind them already)
+    if (!np.in_tail) { HIPCHK(hipStreamWaitEvent(c->stream, c->ev_norm_ready, 0)); c->z2_norm_stream_busy = false; }
     std::swap(c->znorm, c->znorm2);
     std::swap(c->znorm_elems, c->znorm2_elems);
     HIPCHK(hipEventRecord(c->ev_z2_free, c->stream));   // everything that read the buffer that is now znorm2 lies before this point
     c->z2_has_reader = true;
-    c->norm_prefetch_hits += 1;
+    (np.in_tail ? c->norm_tail_hits : c->norm_prefetch_hits) += 1;
   } else {
     if (need > c->znorm_elems) {
       if (c->znorm) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->znorm)); }
@@ -39,44 +40,132 @@ int normals_for_launch(Ctx<T>* c, const KP<T>& p, int n_trans) {
   return AHMC_OK;
 }
 
+// ---- the second normals buffer, at least `need2` elements: both ways of making the next launch's normals ahead of time write it ----
+// Out of memory is not an error: `on` (the caller's switch for this context) goes to 0 and the caller's path is off from then on.
+template <class T>
+int second_normals_buffer(Ctx<T>* c, size_t need2, int& on) {
+  if (!c->ev_z2_free) {
+    HIPCHK(hipEventCreateWithFlags(&c->ev_norm_ready, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_z2_free, hipEventDisableTiming));
+  }
+  if (need2 <= c->znorm2_elems) return AHMC_OK;
+  // a second buffer only where the device has room to spare (the draws of a run, another context): 2x its size must be free
+  size_t free_b = 0, total_b = 0;
+  const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + c->znorm2_elems * sizeof(T) >= 2 * need2 * sizeof(T);
+  (void)hipGetLastError();
+  if (room) {
+    if (c->znorm2) {
+      HIPCHK(hipStreamSynchronize(c->stream));
+      if (c->stream_norm) HIPCHK(hipStreamSynchronize(c->stream_norm));
+      HIPCHK(hipFree(c->znorm2));
+      c->z2_has_reader = false;
+      c->z2_norm_stream_busy = false;
+      c->npre.valid = false;
+    }
+    c->znorm2 = nullptr;
+    c->znorm2_elems = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&c->znorm2), need2 * sizeof(T)) == hipSuccess) c->znorm2_elems = need2;
+    else { (void)hipGetLastError(); c->znorm2 = nullptr; on = 0; }
+  } else if (!c->znorm2) {
+    on = 0;
+  }
+  return AHMC_OK;
+}
+
+#ifndef AHMC_NORMALS_TAIL_DEFAULT
+#define AHMC_NORMALS_TAIL_DEFAULT 1
+#endif
+// AHMC_NORMALS_TAIL (read per call): 0 off; 1 where the second stream is declined for size alone; 2 every launch length (tests, A/B runs)
+inline int normals_tail_mode() {
+  const char* e = getenv("AHMC_NORMALS_TAIL");
+  const int m = e ? atoi(e) : AHMC_NORMALS_TAIL_DEFAULT;
+  return m < 0 ? 0 : (m > 2 ? 2 : m);
+}
+inline size_t normals_prefetch_max_bytes() {
+  return getenv("AHMC_NORMALS_PREFETCH_MAX_MB") ? (size_t)atoll(getenv("AHMC_NORMALS_PREFETCH_MAX_MB")) << 20 : (size_t)2 << 30;
+}
+// does a launch whose successor has `hint` transitions make that successor's normals in its own tail?  (k_nuts, G = 64, MODE 0 / 3:
+// AHMC_TAIL_NORMALS in ahmc_kernels.hpp.)  Mode 1 takes exactly the launches the second stream declines for their size.
+template <class T>
+bool tail_normals_applies(const Ctx<T>* c, int64_t hint, double refresh_alpha) {
+  const int mode = normals_tail_mode();
+  if (!AHMC_TAIL_NORMALS || mode == 0 || c->norm_tail == 0 || c->G != 64 || hint <= 0 || refresh_alpha != 0) return false;
+  if (mode == 2) return true;
+  if (getenv("AHMC_NORMALS_PREFETCH") && atoi(getenv("AHMC_NORMALS_PREFETCH")) == 0) return false;
+  return (size_t)hint * (size_t)c->D * (size_t)c->N * sizeof(T) > normals_prefetch_max_bytes();
+}
+
+// ---- the normals of the launch that follows, in the TAIL of the one about to be enqueued ----
+// Fills p.tail_*: `tail_waves` single-wave workgroups behind the chain workgroups, `AHMC_NORMALS_TAIL_ROWS` rows each (a row = one
+// transition of one chain), writing the second buffer.  The hardware deals workgroups in block order, so they start when the last chain
+// has started and fill the wave slots that empty out while the launch waits for its slowest chains (measured: profiles/r8_experiments.md).
+template <class T>
+int tail_normals_plan(Ctx<T>* c, KP<T>& p, int64_t hint, int n_trans) {
+  const size_t need2 = (size_t)hint * (size_t)c->D * (size_t)c->N;
+  if (c->norm_tail < 0) c->norm_tail = 1;
+  int rc = second_normals_buffer(c, need2, c->norm_tail);
+  if (rc) return rc;
+  if (c->norm_tail != 1 || !c->znorm2 || need2 > c->znorm2_elems) return AHMC_OK;
+  // a k_normals of the second stream may still be writing the buffer (its launch was never consumed): behind it
+  if (c->z2_norm_stream_busy) { HIPCHK(hipStreamWaitEvent(c->stream, c->ev_norm_ready, 0)); c->z2_norm_stream_busy = false; }
+#if AHMC_TAIL_NORMALS
+  const int rows_env = getenv("AHMC_NORMALS_TAIL_ROWS") ? atoi(getenv("AHMC_NORMALS_TAIL_ROWS")) : 0;
+  const int64_t rows = hint * c->N, per_wave = rows_env > 0 ? rows_env : 64;
+  p.tail_out = c->znorm2;
+  p.tail_n_trans = (int)hint;
+  p.tail_iteration = (uint32_t)(c->iteration + (uint64_t)n_trans);
+  p.tail_rows = (int)per_wave;
+  p.tail_waves = (unsigned int)((rows + per_wave - 1) / per_wave);
+#endif
+  return AHMC_OK;
+}
+template <class T>
+bool tail_normals_planned(const KP<T>& p) {
+#if AHMC_TAIL_NORMALS
+  return p.tail_waves != 0;
+#else
+  return false;
+#endif
+}
+// after that launch: what the second buffer will hold, and that the stream is still writing it (a later k_normals of the second stream waits)
+template <class T>
+int tail_normals_done(Ctx<T>* c, const KP<T>& p) {
+  HIPCHK(hipEventRecord(c->ev_z2_free, c->stream));
+  c->z2_has_reader = true;
+  c->npre.valid = true;
+  c->npre.in_tail = true;
+#if AHMC_TAIL_NORMALS
+  c->npre.iter = c->iteration; c->npre.n = p.tail_n_trans;
+#endif
+  c->npre.k0 = (uint64_t)p.k0; c->npre.k1 = (uint64_t)p.k1; c->npre.chain_offset = (uint64_t)p.chain_offset; c->npre.chain_stride = (uint64_t)p.chain_stride;
+  return AHMC_OK;
+}
+
 // ---- the normals of the launch that follows (`hint` transitions, from c->iteration on), beside the one just enqueued ----
 // Measured (profiles/r6_experiments.md r6n): cfg3's 4-transition launches gain 6 % in the sampling phase (3.20 -> 3.40e9: the 0.1 ms of
 // k_normals and its launch gap no longer sit between two 6 ms launches); cfg2's 256-transition launches lose 0.4 % (a 5.7 ms k_normals beside
 // a VALU-bound k_nuts takes what it gives) and cfg5's 32 are unchanged — so only launches whose normals are at most 2 GiB are prefetched.
 template <class T>
 int prefetch_next_normals(Ctx<T>* c, const KP<T>& p, int64_t hint, double refresh_alpha) {
-  const size_t prefetch_max_bytes = getenv("AHMC_NORMALS_PREFETCH_MAX_MB") ? (size_t)atoll(getenv("AHMC_NORMALS_PREFETCH_MAX_MB")) << 20 : (size_t)2 << 30;
+  const size_t prefetch_max_bytes = normals_prefetch_max_bytes();
   if (!(hint > 0 && refresh_alpha == 0 && (size_t)hint * (size_t)c->D * (size_t)c->N * sizeof(T) <= prefetch_max_bytes)) return AHMC_OK;
   if (c->norm_prefetch < 0) c->norm_prefetch = (getenv("AHMC_NORMALS_PREFETCH") && atoi(getenv("AHMC_NORMALS_PREFETCH")) == 0) ? 0 : 1;
   const size_t need2 = (size_t)hint * (size_t)c->D * (size_t)c->N;
-  if (c->norm_prefetch == 1 && need2 > c->znorm2_elems) {
-    // a second buffer only where the device has room to spare (the draws of a run, another context): 2x its size must be free
-    size_t free_b = 0, total_b = 0;
-    const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + c->znorm2_elems * sizeof(T) >= 2 * need2 * sizeof(T);
-    (void)hipGetLastError();
-    if (room) {
-      if (c->znorm2) { HIPCHK(hipStreamSynchronize(c->stream)); if (c->stream_norm) HIPCHK(hipStreamSynchronize(c->stream_norm)); HIPCHK(hipFree(c->znorm2)); c->z2_has_reader = false; }
-      c->znorm2 = nullptr;
-      c->znorm2_elems = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&c->znorm2), need2 * sizeof(T)) == hipSuccess) c->znorm2_elems = need2;
-      else { (void)hipGetLastError(); c->znorm2 = nullptr; c->norm_prefetch = 0; }
-    } else if (!c->znorm2) {
-      c->norm_prefetch = 0;
-    }
+  if (c->norm_prefetch == 1) {
+    int rc = second_normals_buffer(c, need2, c->norm_prefetch);
+    if (rc) return rc;
   }
   if (c->norm_prefetch == 1 && c->znorm2 && need2 <= c->znorm2_elems) {
-    if (!c->stream_norm) {
-      HIPCHK(hipStreamCreateWithFlags(&c->stream_norm, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_norm_ready, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_z2_free, hipEventDisableTiming));
-    }
+    if (!c->stream_norm) HIPCHK(hipStreamCreateWithFlags(&c->stream_norm, hipStreamNonBlocking));
     if (c->z2_has_reader) HIPCHK(hipStreamWaitEvent(c->stream_norm, c->ev_z2_free, 0));
     KP<T> p2 = p;
     p2.iteration = (uint32_t)c->iteration;   // (make_kp's field: the launch that follows starts here)
     hipLaunchKernelGGL((k_normals<T>), dim3(normals_grid(c, hint)), dim3(256), 0, c->stream_norm, p2, c->znorm2, (int)hint, (uint32_t)RNG_MOMENTUM);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_norm_ready, c->stream_norm));
+    c->z2_norm_stream_busy = true;
     c->npre.valid = true;
+    c->npre.in_tail = false;
     c->npre.iter = c->iteration; c->npre.n = hint;
     c->npre.k0 = (uint64_t)p.k0; c->npre.k1 = (uint64_t)p.k1; c->npre.chain_offset = (uint64_t)p.chain_offset; c->npre.chain_stride = (uint64_t)p.chain_stride;
   }

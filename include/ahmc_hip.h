@@ -483,7 +483,10 @@ typedef enum {
                                                since) — ahmc_get_stepsize always fills N values, so a checkpoint asks here whether to hand
                                                back one (FixedIntegrationTime takes nothing else, src/trajectory.jl:241-243)          */,
   AHMC_INFO_WIDE = 15                       /* 1: a wide context (D > 4096, or AHMC_FORCE_WIDE=1 at ahmc_create): no fused-kernel geometry,
-                                               every call runs on the step-synchronous engine; GROUP_LANES / ELEMS_PER_LANE are 0    */
+                                               every call runs on the step-synchronous engine; GROUP_LANES / ELEMS_PER_LANE are 0    */,
+  AHMC_INFO_NORM_TAIL_HITS = 16,            /* NUTS launches whose momentum normals were made by waves appended to the launch before them
+                                               (one chain per wave, AHMC_NORMALS_TAIL) since ahmc_create                             */
+  AHMC_INFO_NORM_PREFETCH_HITS = 17         /* … whose normals were made on the second stream beside the launch before them           */
 } ahmc_info;
 int32_t ahmc_get_info(ahmc_ctx* ctx, int32_t what, int64_t* out);
 
