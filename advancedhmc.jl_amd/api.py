@@ -843,8 +843,12 @@ class Engine:
         if k.refresh_alpha != 0.0:
             # HMCKernel(PartialMomentumRefreshment(α), τ) (src/trajectory.jl:249-254, src/hamiltonian.jl:243-254): the refreshment is part of
             # the sample loop's kernel configuration at the boundary — ONE iteration of that loop is this transition (the iteration counter,
-            # and with it every variate, continues as for the two calls below; the running accumulators count the draw, as for any kept one)
-            self._call("ahmc_sample_from", C.byref(k), 1, 1, 0, 0, None)
+            # and with it every variate, continues as for the two calls below).  It is issued as iteration 2 of 2, i.e. as a RESUMED loop
+            # (ahmc_sample_from with i_first > 1): nothing is reset, and the running accumulators COUNT the draw as a kept one — Σθ, Σθ²,
+            # Σ n_steps, the energy sums and n_transitions of an earlier run() go on, +1 transition.  This differs from the full-refresh
+            # transition below, which leaves the accumulators alone.  (i_first = 1 would be a loop's first kept iteration and clear them.
+            # With n_adapts = 0 no other rule of i_first applies: nothing adapts, and the Stan adaptor's position check needs i_first <= n_adapts.)
+            self._call("ahmc_sample_from", C.byref(k), 2, 2, 0, 0, None)
             return
         if k.nuts:
             self._call("ahmc_nuts_transition", k.max_depth, k.delta_max, k.criterion, k.sampler)

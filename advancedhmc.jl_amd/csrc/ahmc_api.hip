@@ -904,11 +904,22 @@ int resolve_integration_time(Ctx<T>* c, double lambda, int64_t& L) {
 }
 
 // ---- (ABI v6) the reference's matrix-mode early exit, opt-in (src/integrator.jl:252-258) ----
+// isfinite(z) of src/hamiltonian.jl:141-142 over all chains: the values AND the gradients of ℓπ and ℓκ.
+//   ℓπ, ℓκ   stored sanitised: a non-finite value is −Inf;
+//   ∇ℓπ      one pass over g (D·N elements);
+//   ∂H∂r = M⁻¹r (unit / diagonal metric — the only ones this mode runs on) needs no pass of its own: a finite ℓκ = −½ Σ M⁻¹r² has
+//            finite terms (one ±Inf or NaN term makes the sum ±Inf or NaN, stored as −Inf), each computed as (r·r)·M⁻¹ from the values
+//            the product M⁻¹·r is made of.  With |r| >= 1, |M⁻¹r| <= |M⁻¹|r² is finite; with |r| < 1, |M⁻¹r| < |M⁻¹|, and M⁻¹ is finite
+//            (an infinite M⁻¹ gives a term Inf for r != 0 and Inf·0 = NaN for r = 0; a NaN one gives NaN).
+// (After a leapfrog step a non-finite gradient also shows in ℓκ — the closing half kick r − ϵ/2·g carries it into r —, so the pass over
+// g changes no stop step there; it makes the flag the reference's predicate in its own right rather than by that argument.)
 template <class T>
-__global__ __launch_bounds__(256) void k_any_nonfinite(const T* __restrict__ lp, const T* __restrict__ lk, int64_t N, int* __restrict__ flag) {
+__global__ __launch_bounds__(256) void k_any_nonfinite(const T* __restrict__ lp, const T* __restrict__ lk, const T* __restrict__ g, int64_t N, int64_t DN,
+                                                       int* __restrict__ flag) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  // (ℓπ, ℓκ are stored sanitised: a non-finite value is −Inf — `isfinite(z)` of src/hamiltonian.jl:141-142 is false for it)
-  if (i < N && !(is_finite(lp[i]) && is_finite(lk[i]))) atomicOr(flag, 1);
+  bool bad = i < DN && !is_finite(g[i]);
+  if (i < N) bad = bad || !(is_finite(lp[i]) && is_finite(lk[i]));
+  if (bad) atomicOr(flag, 1);
 }
 // one leapfrog step of every chain at a time (k_leapfrog with n = ±1), stopping ALL chains after the first step that left any chain
 // non-finite; `done` = the steps taken.  One launch and one 4-byte read-back per step: a comparison mode.
@@ -926,7 +937,8 @@ int compat_step_loop(Ctx<T>* c, int64_t n_abs, bool fwd, int64_t& done) {
     p.n_steps = fwd ? 1 : -1;
     o->leapfrog(c->G, c->E, group_grid(c), c->stream, p);
     HIPCHK(hipMemsetAsync(c->compat_flag, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL((k_any_nonfinite<T>), dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, c->stream, c->lp, c->lk, c->N, c->compat_flag);
+    const int64_t DN = (int64_t)c->D * c->N;   // (>= N: the grid that covers g covers ℓπ and ℓκ)
+    hipLaunchKernelGGL((k_any_nonfinite<T>), dim3((unsigned)((DN + 255) / 256)), dim3(256), 0, c->stream, c->lp, c->lk, c->g, c->N, DN, c->compat_flag);
     HIPCHK(hipGetLastError());
     int flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, c->compat_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -951,6 +963,9 @@ int compat_hmc_stop_step(Ctx<T>* c, int64_t L, double refresh_alpha, int64_t& L_
   p.refresh_alpha = (T)refresh_alpha;
   o->refresh(c->G, c->E, group_grid(c), c->stream, p);   // the momentum k_hmc will draw (same stream, same counters) and the caches
   HIPCHK(hipGetLastError());
+  // … and the step size k_hmc will integrate with: k_refresh left chain_eps() of this iteration (the RNG_JITTER draw of a JitteredLeapfrog) in
+  // eps_cur; the dry run's k_leapfrog reads the nominal slot, which is part of the saved tbase and comes back with it below
+  if (c->integ_kind == AHMC_INTEGRATOR_JITTERED) HIPCHK(hipMemcpyAsync(c->eps_nom, c->eps_cur, sizeof(T) * c->N, hipMemcpyDeviceToDevice, c->stream));
   int64_t done = 0;
   int rc = compat_step_loop(c, L, true, done);
   L_eff = done > 0 ? done : L;

@@ -834,9 +834,20 @@ __device__ __forceinline__ T kinetic_partial(const T (&r)[E], const T (&minv)[E]
   return s;
 }
 
+// The two updates of a leapfrog, each ONE definition with its contraction spelled out (src/integrator.jl:233-243):
+//   kick   r − (ϵ/2)·g        one fma: the product is not rounded
+//   drift  θ + ϵ·(M⁻¹·r)      M⁻¹·r rounded, then one fma
+// Every leapfrog_step* below and hier_publish_next go through them: what -ffp-contract=on does with `a - b * c` written out in several
+// places is the compiler's choice per place, and hier_publish_next must produce the very bits the next step's own lane 0 will.
+template <class T>
+__device__ __forceinline__ T leapfrog_kick(T r, T eh, T g) { return fma(-eh, g, r); }
+template <class T>
+__device__ __forceinline__ T leapfrog_drift(T th, T eps, T minv, T r) { return fma(eps, minv * r, th); }
+
 // Multi-wave hierarchical target: the chain's first lane publishes θ′[0], θ′[1] of the leapfrog that would FOLLOW this one from the point
-// just completed with the same signed step — r½ = r − ϵ/2·g, θ′ = θ + ϵ·(M⁻¹·r½), the very expressions (and contractions) of the next
-// leapfrog_step, so the bits are the ones its own lane 0 will compute — into xwave_buf_p, before the barrier of the energy exchange.
+// just completed with the same signed step — leapfrog_kick, then leapfrog_drift, the functions the next leapfrog_step calls, so the bits
+// are the ones its own lane 0 will compute (tests/test_device_primitives.py: test_hier_publish_next_is_the_leapfrog_own_expression) —
+// into xwave_buf_p, before the barrier of the energy exchange.
 template <class T, int G, int E, int TK>
 __device__ __forceinline__ void hier_publish_next(const Point<T, E>& z, const T (&minv)[E], T eps) {
   if constexpr (G > 64 && TK == 3 && E >= 2) {
@@ -845,8 +856,8 @@ __device__ __forceinline__ void hier_publish_next(const Point<T, E>& z, const T 
       double* hp = xwave_buf_p();
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
-        const T rh = z.r[k] - eh * z.g[k];
-        const T tn = z.th[k] + eps * (minv[k] * rh);
+        const T rh = leapfrog_kick(z.r[k], eh, z.g[k]);
+        const T tn = leapfrog_drift(z.th[k], eps, minv[k], rh);
         hp[k] = (double)tn;
       }
     }
@@ -863,13 +874,13 @@ __device__ __forceinline__ void leapfrog_step(Point<T, E>& z, const T (&minv)[E]
   if constexpr (TEMPER) temper(lf, z.r, i, true, n);
   const T eh = eps / 2;
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.th[e] = z.th[e] + eps * (minv[e] * z.r[e]);
+  for (int e = 0; e < E; ++e) z.th[e] = leapfrog_drift(z.th[e], eps, minv[e], z.r[e]);
   T red[2];
   red[0] = target_eval<T, G, E, TK>(tp, z.th, z.g, lane, d0, !TEMPER && use_pre);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
   if constexpr (TEMPER) temper(lf, z.r, i, false, n);
   red[1] = kinetic_partial(z.r, minv);
   if constexpr (!TEMPER) hier_publish_next<T, G, E, TK>(z, minv, eps);
@@ -889,12 +900,12 @@ template <class T, int G, int E, int TK>
 __device__ __forceinline__ T leapfrog_step_ne(Point<T, E>& z, const T (&minv)[E], T eps, const TargetP<T>& tp, int lane, int d0) {
   const T eh = eps / 2;
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.th[e] = z.th[e] + eps * (minv[e] * z.r[e]);
+  for (int e = 0; e < E; ++e) z.th[e] = leapfrog_drift(z.th[e], eps, minv[e], z.r[e]);
   const T part = target_eval<T, G, E, TK>(tp, z.th, z.g, lane, d0);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
   const T kin = kinetic_partial(z.r, minv);
   T sv[1] = {part - kin / 2};
   leapfrog_allsum<G, TK>(sv);
@@ -911,13 +922,13 @@ __device__ __forceinline__ void leapfrog_step_plus2(Point<T, E>& z, const T (&mi
                                                     T (&extra)[2], F&& partials, bool use_pre = false) {
   const T eh = eps / 2;
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.th[e] = z.th[e] + eps * (minv[e] * z.r[e]);
+  for (int e = 0; e < E; ++e) z.th[e] = leapfrog_drift(z.th[e], eps, minv[e], z.r[e]);
   T red[4];
   red[0] = target_eval<T, G, E, TK>(tp, z.th, z.g, lane, d0, use_pre);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
   red[1] = kinetic_partial(z.r, minv);
   partials(red[2], red[3]);
   hier_publish_next<T, G, E, TK>(z, minv, eps);

@@ -410,20 +410,26 @@ __global__ __launch_bounds__(256) void k_ebfmi(const T* __restrict__ ea, int64_t
 // ---- ESS on the device: Geyer's initial monotone sequence on the direct autocovariances ---------------------------
 // draws (D, N, K) as ahmc_sample writes them; one thread per (d, c) series.  γ_t by direct sums (a NUTS chain on a
 // well-conditioned target stops after a handful of lags; the loop is capped at K/2 pairs), pairs P_t = ρ_2t + ρ_2t+1
-// truncated at the first non-positive one and made non-increasing; τ = −1 + 2 Σ P_t; ESS = K / τ  (the estimator of
+// truncated at the first non-positive one and made non-increasing; τ = −1 + 2 Σ P_t; ESS = K / τ; NaN for a series with any
+// non-finite draw, K for a constant finite one  (the estimator of
 // advancedhmc.jl_amd/diagnostics.py — the reference computes no ESS itself, MCMCChains.jl does: parity unpinned).
 template <class T>
 __global__ __launch_bounds__(256) void k_ess(const T* __restrict__ draws, int64_t DN, int64_t K, T* __restrict__ out) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= DN) return;
   double mean = 0, lo = (double)draws[s], hi = lo;
+  bool finite = true;
   for (int64_t k = 0; k < K; ++k) {
     const double x = (double)draws[k * DN + s];
+    finite = finite && is_finite(x);
     mean += x;
     lo = x < lo ? x : lo;
     hi = x > hi ? x : hi;
   }
   mean /= (double)K;
+  // a series with a non-finite draw has no ESS: NaN, as ahmc_diag_summary answers (both tests below are also true of a NaN — K there
+  // would read as a perfect score)
+  if (!finite) { out[s] = Lim<T>::nan(); return; }
   // a series that never moved has no autocorrelation to estimate: K.  (Decided on the values, not on γ₀ > 0: Σx / K of K identical
   // values can be an ulp off x, and the "variance" of 1e-32 that leaves gave such a series an ESS of ≈ 1 or K by rounding luck.)
   if (!(hi > lo)) { out[s] = (T)K; return; }

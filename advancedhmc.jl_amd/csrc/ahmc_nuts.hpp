@@ -172,12 +172,12 @@ __device__ __forceinline__ void leapfrog_core(Point<T, E>& z, const T (&minv)[E]
   if constexpr (TEMPER) temper(lf, z.r, 1, true, 1);
   const T eh = eps / 2;
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.th[e] = z.th[e] + eps * (minv[e] * z.r[e]);
+  for (int e = 0; e < E; ++e) z.th[e] = leapfrog_drift(z.th[e], eps, minv[e], z.r[e]);
   (void)target_eval<T, G, E, TK>(tp, z.th, z.g, lane, d0);
 #pragma unroll
-  for (int e = 0; e < E; ++e) z.r[e] = z.r[e] - eh * z.g[e];
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
   if constexpr (TEMPER) temper(lf, z.r, 1, false, 1);
 }
 
@@ -631,12 +631,12 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
             {
               const T e_ = v > 0 ? eps : -eps, eh_ = e_ / 2;
 #pragma unroll
-              for (int e = 0; e < E; ++e) cur.r[e] = cur.r[e] - eh_ * cur.g[e];
+              for (int e = 0; e < E; ++e) cur.r[e] = leapfrog_kick(cur.r[e], eh_, cur.g[e]);
 #pragma unroll
-              for (int e = 0; e < E; ++e) cur.th[e] = cur.th[e] + e_ * (minv[e] * cur.r[e]);
+              for (int e = 0; e < E; ++e) cur.th[e] = leapfrog_drift(cur.th[e], e_, minv[e], cur.r[e]);
               const T part_ = target_eval<T, G, E, TK>(p.tp, cur.th, cur.g, lane, d0);
 #pragma unroll
-              for (int e = 0; e < E; ++e) cur.r[e] = cur.r[e] - eh_ * cur.g[e];
+              for (int e = 0; e < E; ++e) cur.r[e] = leapfrog_kick(cur.r[e], eh_, cur.g[e]);
               const T kin_ = kinetic_partial(cur.r, minv);
               T sv_[1] = {part_ - kin_ / 2};
               asm volatile("" : "+v"(sv_[0]));   // the partial is complete before the stamp

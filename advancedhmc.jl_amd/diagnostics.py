@@ -27,10 +27,13 @@ def autocorrelation(x, axis=0):
 
 def ess(draws, axis=0):
     """Effective sample size of each series along `axis` (Geyer initial monotone sequence).
-    draws: (n_draws, ...) → array of the remaining shape.  Constant series give n_draws."""
+    draws: (n_draws, ...) → array of the remaining shape.  Constant series give n_draws; a series with any non-finite value
+    gives NaN (as k_ess, the CPU checker and ahmc_diag_summary)."""
     x = np.moveaxis(np.asarray(draws, dtype=np.float64), axis, 0)
     n = x.shape[0]
-    rho = autocorrelation(x, axis=0)
+    finite = np.isfinite(x).all(axis=0)
+    with np.errstate(invalid="ignore"):
+        rho = autocorrelation(np.where(finite, x, 0.0), axis=0)
     rho = np.where(np.isfinite(rho), rho, 0.0)
     npair = n // 2
     P = rho[0:2 * npair:2] + rho[1:2 * npair:2]          # P_t = ρ_2t + ρ_2t+1
@@ -41,7 +44,9 @@ def ess(draws, axis=0):
     tau = np.maximum(tau, 1.0 / n)
     # a series that never moved (every transition rejected) has no autocorrelation to estimate: n_draws, as k_ess and the CPU checker
     # (round 6: this function returned n² there — found by tests/test_random_configurations.py::test_random_diagnostics)
-    return np.where(x.max(axis=0) == x.min(axis=0), float(n), n / tau)
+    with np.errstate(invalid="ignore"):
+        still = x.max(axis=0) == x.min(axis=0)
+    return np.where(finite, np.where(still, float(n), n / tau), np.nan)
 
 
 def EBFMI(energies, axis=0):

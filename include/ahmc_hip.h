@@ -458,7 +458,9 @@ int32_t ahmc_gather_state(ahmc_ctx* ctx, void* theta_all);
 int32_t ahmc_ebfmi(ahmc_ctx* ctx, void* out);
 /* Effective sample size of every (dimension, chain) series of `draws` = the (D, N, n_draws) buffer ahmc_sample fills
  * (device pointer): out T (D,N), host or device.  Geyer's initial monotone sequence on the autocovariances.  The
- * reference computes no ESS (MCMCChains.jl does; no reference test calls it): the definition is this engine's.  */
+ * reference computes no ESS (MCMCChains.jl does; no reference test calls it): the definition is this engine's.
+ * A series that contains any non-finite draw (NaN, +Inf, -Inf) has ESS = NaN, as the summary of ahmc_diag.h answers; a series
+ * of n_draws identical finite values has ESS = n_draws.                                                          */
 int32_t ahmc_ess(ahmc_ctx* ctx, const void* draws, int64_t n_draws, void* out);
 
 /* Engine introspection (no reference counterpart; used by bench.py to price the roofline per launch

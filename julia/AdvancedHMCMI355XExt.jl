@@ -270,7 +270,10 @@ end
 # HMCKernel(PartialMomentumRefreshment(α), τ) (src/trajectory.jl:249-254, src/hamiltonian.jl:243-254), static or dynamic: at the boundary the
 # refreshment is part of the sample loop's kernel configuration (`refresh_alpha` of ahmc_kernel_cfg), so ONE iteration of that loop is this
 # transition — the iteration counter, and with it every variate, continues as for the two methods above (as `Engine.transition` of the
-# Python mirror; HIP == CPU checker on it: tests/test_random_configurations.py, tests/test_random_call_sequences.py)
+# Python mirror; HIP == CPU checker on it: tests/test_random_configurations.py, tests/test_random_call_sequences.py).  It is issued as
+# iteration 2 of 2, a RESUMED loop (`i_first > 1`): nothing is reset, and the running accumulators (`accum_state`) count the draw as a kept
+# one on top of what an earlier `sample_device` left — unlike the two methods above, which leave the accumulators alone
+# (tests/test_capi_and_host.py: test_accumulators_survive_a_partial_refresh_transition)
 function AdvancedHMC.transition(
     ::Union{AbstractRNG,AbstractVector{<:AbstractRNG}}, h::Hamiltonian,
     κ::HMCKernel{<:PartialMomentumRefreshment,<:Trajectory{TS,I,TC}}, z::MI355XChains{T},
@@ -281,7 +284,7 @@ function AdvancedHMC.transition(
         set_integrator!(z, κ.τ.integrator)
         cfg = Ref(kernel_cfg(κ))
         check(z.ctx, ccall((:ahmc_sample_from, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Cint, Ptr{T}),
-                           z.ctx, cfg, 1, 1, 0, false, C_NULL))
+                           z.ctx, cfg, 2, 2, 0, false, C_NULL))
     end
     dynamic = TC <: AdvancedHMC.DynamicTerminationCriterion
     tstat = (

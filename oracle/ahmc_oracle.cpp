@@ -2413,13 +2413,16 @@ int32_t ahmc_ess(ahmc_ctx* ctx, const void* draws_v, int64_t K, void* out_v) {
     _Pragma("omp parallel for schedule(static)")
     for (int64_t s2 = 0; s2 < DN; ++s2) {
       double mean = 0, lo = (double)draws[s2], hi = lo;
+      bool finite = true;
       for (int64_t k = 0; k < K; ++k) {
         const double x = (double)draws[k * DN + s2];
+        finite = finite && std::isfinite(x);
         mean += x;
         lo = x < lo ? x : lo;
         hi = x > hi ? x : hi;
       }
       mean /= (double)K;
+      if (!finite) { out[s2] = std::numeric_limits<T>::quiet_NaN(); continue; }   // a non-finite draw: no ESS (k_ess, diagnostics.ess)
       if (!(hi > lo)) { out[s2] = (T)K; continue; }   // a series that never moved: K (decided on the values, not on a γ₀ of rounding noise)
       auto gamma = [&](int64_t t) {
         double g = 0;

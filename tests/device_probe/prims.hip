@@ -308,6 +308,61 @@ PROBE_TARGET_GEOM(float, f32)
 PROBE_TARGET_GEOM(double, f64)
 
 // ---------------------------------------------------------------------------------------------------------------------
+// G2. Two consecutive leapfrog_steps of a multi-wave hierarchical chain (TK = 3, one chain per workgroup of G threads), the second
+// with or without `use_pre`: with it, the other waves read μ and log τ that hier_publish_next computed during the FIRST step; without
+// it, the ones lane 0 computed in the second.  Both are the half kick and the drift of elements 0 and 1 — one definition
+// (leapfrog_kick / leapfrog_drift), so every lane's result must not depend on the switch.  Record per thread, REC = 3E + 4:
+//   [0,E) θ   [E,2E) r   [2E,3E) −∇ℓπ   3E ℓπ   3E+1 ℓκ   (all after the second step)
+//   3E+2..3  what hier_publish_next left in xwave_buf_p during the first step (the chain's first lane; 0 elsewhere)
+// ---------------------------------------------------------------------------------------------------------------------
+template <class T, int G, int E>
+__device__ __forceinline__ void hier2_body(const T* __restrict__ theta, const T* __restrict__ mom, const T* __restrict__ minv_in, int D,
+                                           long long nchains, T eps, int use_pre, T* __restrict__ out) {
+  constexpr int TK = 3, REC = 3 * E + 4;
+  const long long gid = GID;
+  const long long c = gid / G;
+  const bool live = c < nchains;
+  const long long cc = live ? c : 0;
+  const int lane = (int)(gid % G), d0 = lane * E;
+  const TargetP<T> tp{TK, D, nullptr};
+  const LeapfrogP<T> lf{0, T(1)};
+  Point<T, E> z;
+  T minv[E];
+  load_vec(z.th, theta, cc * D, d0, D, T(0));
+  load_vec(z.r, mom, cc * D, d0, D, T(0));
+  load_vec(minv, minv_in, cc * D, d0, D, T(1));
+  fill_caches<T, G, E, TK>(z, minv, tp, lane, d0);
+  leapfrog_step<T, G, E, TK, false>(z, minv, eps, tp, lf, lane, d0, 1, 2, false);
+  T pub0 = 0, pub1 = 0;
+  if (threadIdx.x == 0) {  // published before the first step's energy barrier
+    pub0 = (T)xwave_buf_p()[0];
+    pub1 = (T)xwave_buf_p()[1];
+  }
+  leapfrog_step<T, G, E, TK, false>(z, minv, eps, tp, lf, lane, d0, 2, 2, use_pre != 0);
+  if (live) {
+    T* o = out + gid * REC;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      o[e] = z.th[e];
+      o[E + e] = z.r[e];
+      o[2 * E + e] = z.g[e];
+    }
+    o[3 * E + 0] = z.lp;
+    o[3 * E + 1] = z.lk;
+    o[3 * E + 2] = pub0;
+    o[3 * E + 3] = pub1;
+  }
+}
+#define PROBE_HIER2(T, TN, G, E)                                                                                             \
+  extern "C" PROBE void p_hier2_##TN##_g##G##_e##E(const T* __restrict__ theta, const T* __restrict__ mom,                   \
+                                                   const T* __restrict__ minv, int D, long long nchains, T eps, int use_pre, \
+                                                   T* __restrict__ out) {                                                    \
+    hier2_body<T, G, E>(theta, mom, minv, D, nchains, eps, use_pre, out);                                                    \
+  }
+PROBE_HIER2(float, f32, 128, 4) PROBE_HIER2(float, f32, 256, 8) PROBE_HIER2(float, f32, 512, 8)
+PROBE_HIER2(double, f64, 128, 4) PROBE_HIER2(double, f64, 256, 8) PROBE_HIER2(double, f64, 512, 8)
+
+// ---------------------------------------------------------------------------------------------------------------------
 // H. load_vec / store_vec.  Chain c = gid / L (L lanes per chain, lane l owns d0 = l·E) lives at base[off0 + c·stride ..];
 // `loaded` receives every lane's E registers (padding included), then store_vec writes them back into dst.
 // ---------------------------------------------------------------------------------------------------------------------

@@ -337,3 +337,108 @@ def test_checkpoint_keeps_one_nominal_step_size_one(oracle):
     assert c.info("stepsize_scalar") == 0
     for e in (a, b, c):
         e.close()
+
+
+# ---- the running accumulators survive a transition with PartialMomentumRefreshment ----
+def _partial_refresh_case(lib, which, peer=None):
+    """`run(k, 10)`, then three `transition`s with PartialMomentumRefreshment(0.3) on engine `lib` (and, in step, on the CPU checker
+    `peer`): the accumulators the run left — Σθ, Σθ², Σ n_steps, n_transitions, the checkpoint's per-chain sums — go on from where
+    they stood, each of the three transitions counted as a kept draw.  (A full-refresh `transition` does not count; this one is one
+    iteration of the sample loop — `Engine.transition`.)"""
+    D, N, dtype = 5, 7, np.float64
+    rs = np.random.default_rng(31)
+    h = A.Hamiltonian(A.DiagEuclideanMetric(np.asfortranarray(0.5 + rs.random((D, N)))), A.IsoGaussian(D))
+    lf = A.Leapfrog(np.full(N, 0.3))
+    pr = A.PartialMomentumRefreshment(0.3)
+    k = {"nuts": A.HMCKernel(pr, A.Trajectory(A.MultinomialTS, lf, A.GeneralisedNoUTurn(max_depth=6))),
+         "hmc": A.HMCKernel(pr, A.Trajectory(A.EndPointTS, lf, A.FixedNSteps(6)))}[which]
+    th0 = rs.normal(size=(D, N))
+
+    def fresh(library, iteration=0):
+        e = A.Engine(h, N, dtype=dtype, rng=A.PhiloxRNG(41, iteration=iteration), lib=library)
+        e.set_integrator(lf)
+        e.set_position(th0)
+        return e
+
+    e = fresh(lib)
+    e.run(k, 10)
+    o = None
+    if peer is not None:   # the checker in step with the engine: both continue from the checker's phase point
+        import parity_util as PU
+        from test_gpu_parity import compare_transition_stats
+
+        o = fresh(peer)
+        o.run(k, 10)
+        z = o.phasepoint()
+        for x in (e, o):
+            x.set_position(z.theta, z.r)
+        PU.reset_margin(o)
+    kept, st = e.accum(), e.get_state()
+    assert kept["n_transitions"] == 10 and st["accum"]["n_transitions"] == 10
+    assert np.abs(kept["sum_theta"]).min() > 0 and kept["total_n_steps"] >= 10 * N
+    want_sum, want_sq = kept["sum_theta"].copy(), kept["sumsq_theta"].copy()
+    mag_sum, mag_sq = np.abs(want_sum), want_sq.copy()
+    want_steps, want_steps_c = kept["total_n_steps"], st["accum"]["n_steps"].copy()
+    thetas = []
+    for j in range(3):
+        e.transition(k)
+        th, ns = e.theta(), e.stats()["n_steps"]
+        if o is not None:
+            o.transition(k)
+            same = compare_transition_stats(e.stats(), o.stats(), dtype, o, f"partial-refresh transition {j} ({which})")
+            assert same.all()   # (7 Float64 chains: a near-tie would be reported by name above)
+            np.testing.assert_allclose(th, o.theta(), rtol=1e-9, atol=1e-9)
+        thetas.append(th.copy())
+        want_sum = want_sum + th           # the additions are in T, in this order
+        want_sq = want_sq + th * th
+        mag_sum, mag_sq = mag_sum + np.abs(th), mag_sq + th * th
+        want_steps += int(ns.sum())
+        want_steps_c += ns
+    acc = e.accum()
+    print(f"{which}: n_transitions {acc['n_transitions']} (want 13), total_n_steps {acc['total_n_steps']} (want {want_steps}), "
+          f"max |ΔΣθ| {np.abs(acc['sum_theta'] - want_sum).max():.3g}, max |ΔΣθ²| {np.abs(acc['sumsq_theta'] - want_sq).max():.3g}")
+    assert acc["n_transitions"] == 13
+    assert acc["total_n_steps"] == want_steps
+    # a few ulps of T at the size of the sums: each of the three additions rounds once (Σθ² twice: the square, or its fma)
+    assert np.all(np.abs(acc["sum_theta"] - want_sum) <= 4 * np.spacing(mag_sum))
+    assert np.all(np.abs(acc["sumsq_theta"] - want_sq) <= 4 * np.spacing(mag_sq))
+    # the checkpoint's form of the same sums, and its round trip through set_state
+    st2 = e.get_state()
+    a2 = st2["accum"]
+    assert a2["n_transitions"] == 13
+    np.testing.assert_array_equal(a2["n_steps"], want_steps_c)
+    np.testing.assert_array_equal(a2["sum_theta"], acc["sum_theta"].T)
+    assert np.all(a2["energy_sums"][0] == 13)          # the energies of EBFMI counted thirteen transitions too
+    f = fresh(lib)
+    f.set_state(st2)
+    a3, acc3 = f.get_state()["accum"], f.accum()
+    for key in a2:
+        np.testing.assert_array_equal(a3[key], a2[key], err_msg=key)
+    for key in acc:
+        np.testing.assert_array_equal(acc3[key], acc[key], err_msg=key)
+    f.close()
+    # the positions do not depend on the route: a second engine takes the three transitions from the same state and iteration
+    # WITHOUT the run before them (a checkpoint without the accumulators) — same draws, and sums over exactly these three
+    b = fresh(lib, iteration=10)
+    b.set_state(dict(st, accum=None))
+    for j in range(3):
+        b.transition(k)
+        np.testing.assert_array_equal(b.theta(), thetas[j])
+    accb = b.accum()
+    assert accb["n_transitions"] == 3
+    assert np.all(np.abs(accb["sum_theta"] - (thetas[0] + thetas[1] + thetas[2])) <= 4 * np.spacing(mag_sum))
+    b.close()
+    e.close()
+    if o is not None:
+        o.close()
+
+
+@pytest.mark.parametrize("which", ["nuts", "hmc"])
+def test_accumulators_survive_a_partial_refresh_transition(oracle, which):
+    _partial_refresh_case(oracle, which)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["nuts", "hmc"])
+def test_hip_accumulators_survive_a_partial_refresh_transition(hip, oracle, which):
+    _partial_refresh_case(hip, which, peer=oracle)

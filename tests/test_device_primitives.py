@@ -73,7 +73,8 @@ def test_probe_compiles_without_scratch_or_spills(variant):
         sys.path.pop(0)
     meta = kernel_meta.kernel_meta(co)
     names = {k["name"] for k in meta}
-    for want in ("p_exp_table_uniform", "p_red_f64_g512_k8", "p_once_f32_g128_k3", "p_target_f64_g512_e8_t3", "p_vec_f32_e8", "p_philox"):
+    for want in ("p_exp_table_uniform", "p_red_f64_g512_k8", "p_once_f32_g128_k3", "p_target_f64_g512_e8_t3", "p_vec_f32_e8", "p_philox",
+                 "p_hier2_f32_g128_e4", "p_hier2_f64_g256_e8", "p_hier2_f64_g512_e8"):
         assert want in names, want
     bad = [(k["name"], k.get("private_segment_fixed_size"), k.get("vgpr_spill_count"), k.get("sgpr_spill_count")) for k in meta
            if k.get("private_segment_fixed_size") or k.get("vgpr_spill_count") or k.get("sgpr_spill_count")]
@@ -809,6 +810,59 @@ def test_targets_and_leapfrog(probe, dt, tk):
                     pub, nxt = sc[:, 0, 8:10], sc[:, 0, 10:12]
                     assert (_bits(pub) == _bits(nxt)).all(), (tag, pub[:2], nxt[:2])
     print(f"targets {TN[dt]} tk={tk}: worst ℓπ error / bound {worst[0]:.3f}, gradient {worst[1]:.3f}")
+
+
+HIER2_GEOMS = ((128, 4), (256, 8), (512, 8))
+
+
+def _hier2_inputs(rs, C, D, dt):
+    """θ, r, M⁻¹ of mixed magnitudes (two decades each), μ and log τ kept where exp(−2 log τ) stays finite after two steps"""
+    mag = lambda: 10.0 ** rs.uniform(-1, 1, (C, D))  # noqa: E731
+    th, r, minv = rs.normal(size=(C, D)) * mag(), rs.normal(size=(C, D)) * mag(), mag()
+    th[:, 1] = rs.uniform(-1, 1, C)
+    return th.astype(dt), r.astype(dt), minv.astype(dt)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+def test_hier_publish_next_is_the_leapfrog_own_expression(probe, dt):
+    """G2. The multi-wave hierarchical chain's first lane publishes θ′[0..1] of the NEXT leapfrog (hier_publish_next) for the other waves.
+    It is the half kick and the drift of the leapfrog itself — one definition with explicit fma, not a second copy the compiler may
+    contract differently.  Two consecutive steps at (G, E) = (128, 4), (256, 8), (512, 8), the second with and without `use_pre`: θ, r,
+    −∇ℓπ, ℓπ, ℓκ of EVERY lane bit-identical between the two runs, and the published pair bit-identical to lane 0's own θ[0], θ[1]
+    after the second step."""
+    rs = np.random.default_rng(77)
+    eps = 0.1
+    C = 16
+    n_finite = n_all = 0
+    for G, E in HIER2_GEOMS:
+        rec = 3 * E + 4
+        for D in (G * E, G * E - E - 1):
+            th, r, minv = _hier2_inputs(rs, C, D, dt)
+            # the inputs tell a fused drift from an unfused one: θ + ϵ·(M⁻¹r) with one rounding or two differ for a visible share
+            prod = (minv * r).astype(dt)
+            fused = (th.astype(LD) + LD(dt(eps)) * prod.astype(LD)).astype(dt)
+            unfused = (th + (dt(eps) * prod).astype(dt)).astype(dt)
+            assert (fused != unfused).mean() > 0.1, (TN[dt], G, D, float((fused != unfused).mean()))
+            outs = []
+            for use_pre in (0, 1):
+                o = _empty(C * G * rec, dt)
+                probe.launch(f"p_hier2_{TN[dt]}_g{G}_e{E}", C, G, _dev(th), _dev(r), _dev(minv), int(D), np.int64(C), dt(eps), int(use_pre), o)
+                outs.append(_host(o).reshape(C, G, rec))
+            a, b = outs
+            tag = (TN[dt], G, E, D)
+            assert not np.isnan(a[:, :, :3 * E + 2]).all(), tag                      # the kernel wrote its records
+            for name, lo, hi in (("θ", 0, E), ("r", E, 2 * E), ("−∇ℓπ", 2 * E, 3 * E), ("ℓπ", 3 * E, 3 * E + 1), ("ℓκ", 3 * E + 1, 3 * E + 2)):
+                same = _same_bits(a[:, :, lo:hi], b[:, :, lo:hi])
+                assert same.all(), (tag, name, "use_pre changes the result", int((~same).sum()))
+            for o_, pre in ((a, 0), (b, 1)):
+                pub, own = o_[:, 0, 3 * E + 2:3 * E + 4], o_[:, 0, 0:2]
+                assert _same_bits(pub, own).all(), (tag, pre, "published pair != lane 0's θ[0..1]", pub[:2], own[:2])
+                assert (_bits(o_[:, :, 3 * E]) == _bits(o_[:, :1, 3 * E])).all(), (tag, pre, "ℓπ differs between lanes")
+            n_finite += int(np.isfinite(a[:, 0, 3 * E]).sum())
+            n_all += C
+    print(f"hier2 {TN[dt]}: {n_finite} of {n_all} chains with a finite ℓπ after the second step")
+    assert n_finite >= n_all // 2                                                     # (a −Inf compares equal to anything that overflowed)
 
 
 @pytest.mark.gpu

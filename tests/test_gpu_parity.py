@@ -1373,6 +1373,94 @@ def test_fixed_integration_time_hmcda(hip, oracle, rng):
     np.testing.assert_allclose(res[0][2], res[1][2], rtol=1e-6, atol=1e-8)
 
 
+JIT_EXIT = dict(D=8, N=32, L=400, jitter=0.5, seed=3, marginal={3: 1.8, 11: 1.95, 20: 2.2, 27: 2.5})
+
+
+def jittered_exit_case():
+    """static EndPointTS on the unit-metric iso-Gaussian (the leapfrog's stability limit is ϵ = 2) with four chains whose NOMINAL step
+    sizes sit on both sides of that limit and a jitter of ±50 %: whether, and after how many of the L steps, such a chain leaves the
+    finite numbers depends on the step size the transition actually uses"""
+    c = JIT_EXIT
+    rs = np.random.default_rng(5)
+    eps = 0.2 * (0.7 + 0.6 * rs.random(c["N"]))
+    for ch, e in c["marginal"].items():
+        eps[ch] = e
+    th = rs.normal(size=(c["D"], c["N"]))
+    h = A.Hamiltonian(A.UnitEuclideanMetric((c["D"], c["N"])), A.IsoGaussian(c["D"]))
+    stable = np.ones(c["N"], dtype=bool)
+    stable[list(c["marginal"])] = False
+    return h, eps, th, stable
+
+
+def compat_stop_step(oracle, h, lf, th, L, seed, iteration, stable):
+    """how many leapfrog steps a ref_compat static EndPointTS transition of the ORACLE took (L: no chain left the finite numbers): the
+    transition is run, then its momentum draw is repeated (`refresh` at the same iteration), and a second engine steps every chain
+    with the step size the transition reports until the stable, accepted chains stand where the transition left them.  Returns
+    (steps, the transition's statistics, its end positions)."""
+    N = th.shape[1]
+    e = A.Engine(h, N, dtype=np.float64, rng=A.PhiloxRNG(seed, iteration=iteration), lib=oracle)
+    e.set_integrator(lf)
+    e.set_ref_compat(True)
+    e.set_position(th)
+    e.transition(A.HMCKernel(A.Trajectory(A.EndPointTS, lf, A.FixedNSteps(L))))
+    st, end = e.stats(), e.theta()
+    e.close()
+    m = A.Engine(h, N, dtype=np.float64, rng=A.PhiloxRNG(seed, iteration=iteration), lib=oracle)
+    m.set_integrator(A.Leapfrog(st["step_size"]))
+    m.set_position(th)
+    m.refresh()
+    on = stable & st["is_accept"]
+    assert on.sum() >= 8, on.sum()
+    taken = None
+    for k in range(1, L + 1):
+        m.step(1)
+        if np.allclose(m.theta()[:, on], end[:, on], rtol=1e-12, atol=1e-12):
+            taken = k
+            break
+    m.close()
+    assert taken is not None
+    return taken, st, end
+
+
+def test_reference_batch_exit_compat_mode_jittered(hip, oracle):
+    """`ahmc_set_ref_compat` with a JitteredLeapfrog: the dry run that finds the coupled stop step integrates with the step size the
+    transition itself uses (the RNG_JITTER draw of its iteration), not the nominal one.  Not vacuous: on the oracle alone, the stop step
+    under the jittered integrator differs from the one a plain Leapfrog(ϵ_nom) gives for the same configuration, in both iterations.
+    Then HIP == oracle with this file's comparison: the n_steps statistic (the nominal L) and the end state of every chain."""
+    c = JIT_EXIT
+    h, eps, th, stable = jittered_exit_case()
+    N, L = c["N"], c["L"]
+    lf = A.JitteredLeapfrog(eps, c["jitter"])
+    kern = A.HMCKernel(A.Trajectory(A.EndPointTS, lf, A.FixedNSteps(L)))
+    for it in (0, 1):
+        stop_j, so_ref, end_ref = compat_stop_step(oracle, h, lf, th, L, c["seed"], it, stable)
+        stop_n, _, _ = compat_stop_step(oracle, h, A.Leapfrog(eps), th, L, c["seed"], it, stable)
+        print(f"iteration {it}: the oracle stops after {stop_j} of {L} steps with the jittered step sizes, after {stop_n} with the nominal ones")
+        assert stop_j != stop_n and min(stop_j, stop_n) < L, (it, stop_j, stop_n)
+        assert np.ptp(so_ref["step_size"] / eps) > 0.5          # the jitter is there
+        g, o = (A.Engine(h, N, dtype=np.float64, rng=A.PhiloxRNG(c["seed"], iteration=it), lib=lib) for lib in (hip, oracle))
+        for e in (g, o):
+            e.set_integrator(lf)
+            e.set_ref_compat(True)
+            e.set_position(th)
+            e.transition(kern)
+        sg, so = g.stats(), o.stats()
+        np.testing.assert_array_equal(o.theta(), end_ref)
+        same = compare_transition_stats(sg, so, np.float64, o, f"static hmc, jittered batch exit, iteration {it}")
+        assert (sg["n_steps"] == L).all() and (so["n_steps"] == L).all()
+        np.testing.assert_allclose(sg["step_size"], so["step_size"], rtol=1e-12)
+        assert same[stable].all(), np.flatnonzero(~same)
+        zg, zo = g.phasepoint(), o.phasepoint()
+        # every chain: the stable ones to the file's tolerance; a chain beyond the stability limit has grown by up to 1e150 and is held
+        # on its finiteness pattern and, where finite, to the same RELATIVE tolerance (no absolute one means anything at that size)
+        np.testing.assert_allclose(zg.theta[:, same & stable], zo.theta[:, same & stable], rtol=1e-9, atol=1e-9)
+        np.testing.assert_array_equal(np.isfinite(zg.theta), np.isfinite(zo.theta))
+        np.testing.assert_array_equal(np.isfinite(zg.lp.value), np.isfinite(zo.lp.value))
+        fin = np.isfinite(zo.theta)
+        np.testing.assert_allclose(zg.theta[fin], zo.theta[fin], rtol=1e-6)
+        g.close(); o.close()
+
+
 def test_reference_batch_exit_compat_mode(hip, oracle, rng):
     """(ABI v6) `ahmc_set_ref_compat`: the reference's MATRIX-MODE early exit — `step` ends the integration of every chain at the first step
     after which ANY chain's phase point is non-finite (src/integrator.jl:252-258 with isfinite over all columns, src/hamiltonian.jl:141-142;

@@ -100,3 +100,13 @@ def test_struct_layouts_match():
     jfields = [tuple(f.strip().split("::")) for line in jbody.splitlines() for f in line.split(";") if "::" in f]
     width = {"int32_t": "Cint", "double": "Cdouble", "int64_t": "Int64"}
     assert [(n, width[t]) for n, t in cfields] == jfields, (cfields, jfields)
+
+
+def test_partial_refresh_transition_is_a_resumed_iteration():
+    """the `transition` method for PartialMomentumRefreshment issues ONE iteration of the sample loop as a RESUMED one (i_first = 2 of
+    n_samples = 2, n_adapts = 0), as `Engine.transition` does: with i_first = 1 the call would clear the running accumulators an earlier
+    `sample_device` left (tests/test_capi_and_host.py: test_accumulators_survive_a_partial_refresh_transition)"""
+    single = [args for name, _, _, args in julia_ccalls() if name == "ahmc_sample_from" and args[2].isdigit()]   # (literal iteration numbers)
+    assert single == [["z.ctx", "cfg", "2", "2", "0", "false", "C_NULL"]], single
+    py = open(os.path.join(ROOT, "advancedhmc.jl_amd", "api.py"), encoding="utf-8").read()
+    assert '"ahmc_sample_from", C.byref(k), 2, 2, 0, 0, None)' in py and '"ahmc_sample_from", C.byref(k), 1, 1, 0, 0, None)' not in py

@@ -485,6 +485,26 @@ def test_random_reference_batch_exit(hip, oracle, i):
             same = compare_transition_stats(g.stats(), o.stats(), np.float64, o, what)
             np.testing.assert_allclose(g.phasepoint().theta[:, same & ok], o.phasepoint().theta[:, same & ok], rtol=1e-9, atol=1e-9, err_msg=what)
             realign(g, o, same)
+        # (appended draws — the ones above are as they were) the same with a JitteredLeapfrog: the blow-up chains now sit AT the leapfrog's
+        # stability limit (ϵ²·max M⁻¹ between 3 and 9: the limit is 4), so whether and when one of them leaves the finite numbers within
+        # a few hundred steps depends on the jittered step size the transition uses — which the coupled stop step has to be found with
+        jitter = float(rs.uniform(0.2, 0.6))
+        L = int(rs.integers(150, 400))
+        mmax = np.ones(N) if metric == "unit" else (np.full(N, np.max(m.Minv)) if metric == "diag_shared" else np.max(m.Minv, axis=0))
+        eps_j = eps.copy()
+        eps_j[bad] = np.sqrt(rs.uniform(3.0, 9.0, size=bad.size) / mmax[bad])
+        lfj = A.JitteredLeapfrog(eps_j, jitter)
+        kern = A.HMCKernel(A.Trajectory(A.EndPointTS, lfj, A.FixedNSteps(L)))
+        for e in (g, o):
+            e.set_integrator(lfj)
+            e.set_position(th)
+        for _ in range(2):
+            for e in (g, o):
+                e.transition(kern)
+            whatj = what + f" jitter={jitter:.2f} L={L}"
+            same = compare_transition_stats(g.stats(), o.stats(), np.float64, o, whatj)
+            np.testing.assert_allclose(g.phasepoint().theta[:, same & ok], o.phasepoint().theta[:, same & ok], rtol=1e-9, atol=1e-9, err_msg=whatj)
+            realign(g, o, same)
     finally:
         for e in engines:
             e.close()

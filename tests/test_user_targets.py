@@ -403,3 +403,62 @@ def test_kernel_target_against_oracle(hip, oracle, name, D, metric):
     PU.check_flips(on, PU.decision_margin(o), np.float64, f"kernel target {name} bulk run of 3")   # (free-running: a flip stays)
     assert g.accum()["n_transitions"] == 3
     g.close(); o.close()
+
+
+@pytest.mark.gpu
+def test_coupled_exit_sees_a_nonfinite_gradient(hip, oracle):
+    """`ahmc_set_ref_compat`: isfinite(z) of the reference (src/hamiltonian.jl:141-142) asks for a finite ∇ℓπ as well as finite values.
+    tests/user_targets/inf_grad.hpp keeps ℓπ finite and returns ∂ℓπ/∂θ₀ = +Inf once |θ₀| passes a threshold; exactly one of nine chains
+    crosses it, at step 3 of 8.  The HIP engine (the density inside the fused k_leapfrog) and the oracle (the same density as a host
+    kernel) must both stop EVERY chain after step 3."""
+    D, N, n, eps, bad = 4, 9, 8, 0.1, 5
+    rs = np.random.default_rng(12)
+    minv = np.asfortranarray(0.5 + rs.random((D, N)))
+    th0, r0 = 0.3 * rs.normal(size=(D, N)), 0.3 * rs.normal(size=(D, N))
+    th0[0, bad], r0[0, bad] = 1.0, 2.0 / minv[0, bad]
+    lf = A.Leapfrog(np.full(N, eps))
+    # the trajectory of θ₀ under the plain iso-Gaussian places the threshold: between steps 2 and 3 of chain `bad`, above everyone else
+    ref = A.Engine(A.Hamiltonian(A.DiagEuclideanMetric(minv), A.IsoGaussian(D)), N, rng=A.PhiloxRNG(2), lib=oracle)
+    ref.set_integrator(lf)
+    ref.set_position(th0, r0)
+    path = [ref.phasepoint()]
+    for _ in range(n):
+        ref.step(1)
+        path.append(ref.phasepoint())
+    ref.close()
+    a0 = np.abs(np.array([z.theta[0] for z in path]))          # (n + 1, N)
+    thr = (a0[2, bad] + a0[3, bad]) / 2
+    others = np.arange(N) != bad
+    assert a0[:3, bad].max() < thr < a0[3, bad] and a0[:, others].max() < thr, (a0[:, bad], a0[:, others].max(), thr)
+
+    def fn(th):
+        lp = np.zeros(th.shape[1])
+        for d in range(th.shape[0]):
+            lp += -(LOG2PI + th[d] * th[d]) / 2
+        g = -th.copy()
+        g[0, np.abs(th[0]) > thr] = np.inf
+        return lp, g
+
+    cb = host_kernel(fn)
+    g = A.Engine(A.Hamiltonian(A.DiagEuclideanMetric(minv), A.PluginTarget(D, os.path.join(UT, "inf_grad.hpp"), params=np.array([thr]))), N,
+                 rng=A.PhiloxRNG(2), lib=hip)
+    o = A.Engine(A.Hamiltonian(A.DiagEuclideanMetric(minv), A.KernelTarget(D, cb, handle_kind=capi.KERNEL_HOST)), N, rng=A.PhiloxRNG(2), lib=oracle)
+    for e in (g, o):
+        e.set_integrator(lf)
+        e.set_ref_compat(True)
+        e.set_position(th0, r0)
+        e.step(n)
+    zg, zo = g.phasepoint(), o.phasepoint()
+    taken = {}
+    for name, z in (("hip", zg), ("oracle", zo)):
+        hits = [k for k in range(n + 1) if np.allclose(z.theta[:, others], path[k].theta[:, others], rtol=1e-10, atol=1e-12)]
+        taken[name] = hits
+    print(f"steps taken by the healthy chains: {taken}; chain {bad} after the exit: hip ℓπ {zg.lp.value[bad]}, ℓκ {zg.lk.value[bad]}, "
+          f"−∇ℓπ₀ {zg.lp.gradient[0, bad]}; oracle ℓπ {zo.lp.value[bad]}, ℓκ {zo.lk.value[bad]}, −∇ℓπ₀ {zo.lp.gradient[0, bad]}")
+    assert taken["oracle"] == [3], taken
+    assert taken["hip"] == [3], taken
+    np.testing.assert_allclose(zg.theta[:, others], zo.theta[:, others], rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(zg.r[:, others], zo.r[:, others], rtol=1e-10, atol=1e-12)
+    assert np.isfinite(zg.lp.value[bad]) and np.isfinite(zo.lp.value[bad])             # the value never left the finite numbers …
+    assert not np.isfinite(zg.lp.gradient[0, bad]) and not np.isfinite(zo.lp.gradient[0, bad])   # … the gradient did
+    g.close(); o.close()

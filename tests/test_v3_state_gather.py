@@ -143,6 +143,45 @@ def diag_checks(lib, rng, tol):
     return draws
 
 
+def nonfinite_ess_series(dtype):
+    """K = 16 draws of D·N = 8 series (D = 2, N = 4; series s = d + D·c as the draws buffer orders them): NaN first, NaN in the middle
+    only, +Inf once, all NaN, constant, and three ordinary AR(1) series.  Returns (draws (K, N, D), want_nan (D, N), constant (D, N))."""
+    K, N, D = 16, 4, 2
+    rs = np.random.default_rng(44)
+    x = np.zeros((K, D * N))
+    z = rs.normal(size=(K, D * N))
+    for t in range(1, K):
+        x[t] = 0.5 * x[t - 1] + z[t]
+    x[0, 0] = np.nan
+    x[7, 1] = np.nan
+    x[11, 2] = np.inf
+    x[:, 3] = np.nan
+    x[:, 4] = 1.0 / 3.0
+    draws = np.ascontiguousarray(x.reshape(K, N, D).astype(dtype))
+    flat = lambda idx: np.isin(np.arange(D * N), idx).reshape(N, D).T  # noqa: E731
+    return draws, flat([0, 1, 2, 3]), flat([4])
+
+
+def check_nonfinite_ess(ess_of, dtype):
+    """one rule in every estimator: a series with any non-finite value has ESS = NaN (never K, which reads as a perfect score, nor K²);
+    a constant finite series still gives K; the ordinary series agree with the FFT formulation as before"""
+    draws, want_nan, const = nonfinite_ess_series(dtype)
+    K = draws.shape[0]
+    got = ess_of(draws)
+    with np.errstate(all="ignore"):
+        host = A.diagnostics.ess(draws, axis=0).T
+    print(f"ESS {np.dtype(dtype).name}: device/checker {got.T.ravel().tolist()}, diagnostics.ess {host.T.ravel().tolist()}")
+    assert got.dtype == np.dtype(dtype) and got.shape == want_nan.shape
+    np.testing.assert_array_equal(np.isnan(got), want_nan)
+    np.testing.assert_array_equal(np.isnan(host), want_nan)
+    assert (got[const] == K).all() and (host[const] == K).all()
+    rest = ~want_nan & ~const
+    assert rest.sum() == 3 and np.all(got[rest] > 1) and np.all(got[rest] < K * K)
+    # f64: the files' agreement; f32: the result is rounded to T once more (2^-24 relative)
+    np.testing.assert_allclose(got[rest], host[rest], rtol=1e-8 if dtype == np.float64 else 1e-6)
+    return got
+
+
 def test_ebfmi_moments_and_ess_on_the_oracle(oracle, rng):
     draws = diag_checks(oracle, rng, 1e-10)
     K, N, D = draws.shape
@@ -172,6 +211,11 @@ def test_ebfmi_moments_and_ess_on_the_oracle(oracle, rng):
     np.testing.assert_allclose(got[0, 0], want[0, 0], rtol=1e-8)
     assert got[0, 0] < K3 / 4                          # a ramp is as autocorrelated as a series gets
     e.close()
+    # non-finite draws: NaN, in the checker and in diagnostics.ess alike
+    for dtype in (np.float64, np.float32):
+        e = A.Engine(A.Hamiltonian(A.UnitEuclideanMetric(dtype, (2, 4)), A.IsoGaussian(2)), 4, dtype=dtype, lib=oracle)
+        check_nonfinite_ess(lambda d: e.ess(d, d.shape[0]), dtype)
+        e.close()
 
 
 GLOO_WORKER = r'''
@@ -351,6 +395,17 @@ def test_hip_ebfmi_moments_ess_and_one_rank_rccl(hip, oracle, rng):
     # ESS: device kernel == the oracle's implementation of the same estimator == the FFT formulation
     got = e.ess(draws_d.data_ptr(), K)
     np.testing.assert_allclose(got, A.diagnostics.ess(draws, axis=0).T, rtol=1e-8)
+    # non-finite draws: NaN from k_ess as from the checker and diagnostics.ess; the ordinary series of the same buffer as the checker's
+    for dtype in (np.float64, np.float32):
+        res = []
+        for lib in (hip, oracle):
+            ed = A.Engine(A.Hamiltonian(A.UnitEuclideanMetric(dtype, (2, 4)), A.IsoGaussian(2)), 4, dtype=dtype, lib=lib)
+            if lib is hip:
+                res.append(check_nonfinite_ess(lambda d: ed.ess(torch.from_numpy(d).cuda().data_ptr(), d.shape[0]), dtype))
+            else:
+                res.append(check_nonfinite_ess(lambda d: ed.ess(d, d.shape[0]), dtype))
+            ed.close()
+        np.testing.assert_allclose(res[0], res[1], rtol=1e-8 if dtype == np.float64 else 1e-6, equal_nan=True)
     # EBFMI: the running sums of the fused kernel against the energies of the same chains replayed on the oracle
     eb = e.ebfmi()
     rng2 = np.random.default_rng(20260925)
