@@ -813,7 +813,10 @@ class Engine:
         self._call("ahmc_set_ref_compat", 1 if on else 0)
 
     def refresh(self, refreshment=None):
-        """refresh(rng, refreshment, h, z) (src/hamiltonian.jl:213-254)"""
+        """refresh(rng, refreshment, h, z) (src/hamiltonian.jl:213-254).  Does NOT advance the iteration: the transition that follows
+        draws the same (chain, iteration, momentum) normals ξ again.  With FullMomentumRefreshment that merely repeats the draw; a
+        transition with PartialMomentumRefreshment(α) after `refresh()` starts from r = (α + √(1 − α²))·ξ, variance 1.78·M at α = 0.9
+        instead of M.  A stationary start for such a transition is `set_position(θ, r)` with r ~ N(0, M) drawn by the caller."""
         self._call("ahmc_refresh_momentum", float(getattr(refreshment, "alpha", 0.0)))
 
     def step(self, n_steps=1):

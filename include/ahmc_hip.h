@@ -207,7 +207,12 @@ int32_t ahmc_get_phasepoint(ahmc_ctx* ctx, void* theta, void* r, void* lp, void*
 
 /* refresh(rng, FullMomentumRefreshment(), h, z) (src/hamiltonian.jl:213-220) with
  * rand_momentum (src/metric.jl:290-320); alpha in (0,1) selects PartialMomentumRefreshment(α)
- * (:243-254); alpha == 0 → full.  Uses and does NOT advance the iteration counter.           */
+ * (:243-254); alpha == 0 → full.  Uses and does NOT advance the iteration counter: the
+ * transition that follows draws the SAME (chain, iteration, momentum) normals ξ.  After a full
+ * refreshment that only repeats the draw; a transition with PartialMomentumRefreshment(α) after
+ * this call starts from r = (α + √(1 − α²))·ξ — variance 1.78·M at α = 0.9, not M.  To start
+ * such a transition from a stationary momentum hand r ~ N(0, M) in with ahmc_set_position
+ * (tests/invariance_util.py).                                                                */
 int32_t ahmc_refresh_momentum(ahmc_ctx* ctx, double alpha);
 
 /* step(lf, h, z, n_steps; fwd = n_steps > 0) (src/integrator.jl:216-265) with the built-in
