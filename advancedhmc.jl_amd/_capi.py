@@ -210,6 +210,17 @@ GLM_SIGNATURES = {
     "ahmc_glm_pointwise": (_i32, [_vp, _vp, _vp]),
 }
 
+# include/ahmc_glm_hier.h: coefficient groups whose prior scale is sampled (likewise: the HIP engine only)
+AHMC_HGLM_VERSION = 1
+HGLM_MAX_GROUPS = 32
+_pi32 = C.POINTER(_i32)
+HGLM_SIGNATURES = {
+    "ahmc_hglm_version": (_i32, []),
+    "ahmc_hglm_set_target": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _pi32, _pi32, _pi32, C.POINTER(_f64)]),
+    "ahmc_hglm_get_target": (_i32, [_vp, C.POINTER(_i64), _pi32, _pi32, _pi32, _pi32, C.POINTER(_f64)]),
+    "ahmc_hglm_coefficients": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+}
+
 class CLib:
     """One loaded implementation of the ABI."""
 
@@ -273,6 +284,16 @@ class CLib:
             v = self.dll.ahmc_glm_version()
             if v != AHMC_GLM_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm version {v}, expected {AHMC_GLM_VERSION}")
+        # ahmc_glm_hier.h: likewise
+        hglm = [getattr(self.dll, name, None) for name in HGLM_SIGNATURES]
+        self.has_hglm = all(fn is not None for fn in hglm)
+        if self.has_hglm:
+            for fn, (res, args) in zip(hglm, HGLM_SIGNATURES.values()):
+                fn.restype = res
+                fn.argtypes = args
+            v = self.dll.ahmc_hglm_version()
+            if v != AHMC_HGLM_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_hier version {v}, expected {AHMC_HGLM_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

@@ -342,6 +342,50 @@ class GLMTarget:
         return f"GLMTarget(n_obs={self.n_obs}, D={self.D}, family={self.family})"
 
 
+@dataclass(frozen=True)
+class CoefGroup:
+    """Coefficients [start, stop) of a HierGLMTarget that share a prior scale τ ~ half-normal(scale), itself sampled (as log τ).
+    `centered`: the members are sampled on their own scale, β_d ~ N(0, τ²); otherwise standardised, β_d = τ·z_d with z_d ~ N(0, 1)
+    (the non-centred parametrisation: what NUTS needs when the data say little about each member)."""
+    start: int
+    stop: int
+    centered: bool = False
+    scale: float = 1.0
+
+
+class HierGLMTarget(GLMTarget):
+    """A GLMTarget whose coefficient `groups` (CoefGroup, ascending and disjoint) each have a sampled prior scale
+    (include/ahmc_glm_hier.h; arithmetic: glm.hier_logdensity).  θ has D = P + G entries: the P = X.shape[1] coefficient parameters,
+    then log τ of each group.  `prior_scale` / `prior_prec` cover the coefficients in no group; on members they are forced to 0.
+    `.coefficients(θ)` gives (β, τ) on the model's own scale.  HIP engine only."""
+
+    def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0):
+        super().__init__(X, y, family=family, prior_scale=prior_scale, prior_prec=prior_prec, offset=offset, scale=scale)
+        self.P = self.X.shape[1]
+        groups = [g if isinstance(g, CoefGroup) else CoefGroup(*g) for g in groups]
+        try:
+            _glm.check_groups(groups, self.P)
+        except (ValueError, TypeError) as e:
+            raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+        self.groups = tuple(CoefGroup(int(g.start), int(g.stop), bool(g.centered), float(g.scale)) for g in groups)
+        self.D = self.P + len(self.groups)
+        if self.prior_prec is not None:
+            self.prior_prec = self.prior_prec.copy()
+            for g in self.groups:
+                self.prior_prec[g.start:g.stop] = 0.0
+
+    def logdensity(self, theta):
+        """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
+        return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale)
+
+    def coefficients(self, theta):
+        """(β (P, n), τ (G, n)) of draws θ (D, n) by the numpy mirror"""
+        return _glm.hier_coefficients(theta, self.P, self.groups)
+
+    def __repr__(self):
+        return f"HierGLMTarget(n_obs={self.n_obs}, P={self.P}, groups={len(self.groups)}, family={self.family})"
+
+
 @dataclass
 class Hamiltonian:
     """src/hamiltonian.jl:1-20 (GaussianKinetic only, :18-20)"""
@@ -674,6 +718,9 @@ class Engine:
                                                  n_params=-1 if p is None else p.size)
             self._call("ahmc_set_target_plugin", so.encode(), capi.as_ptr(p), 0 if p is None else p.size)
             return
+        if isinstance(target, HierGLMTarget):
+            self._set_hglm(target)
+            return
         if isinstance(target, GLMTarget):
             self._set_glm(target)
             return
@@ -699,6 +746,49 @@ class Engine:
         off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
         p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
         self._call("ahmc_set_target_glm", int(t.family), int(t.n_obs), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p), float(t.scale))
+
+    def _need_hglm(self, what):
+        if not getattr(self.lib, "has_hglm", False):
+            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_glm_hier.h")
+
+    def _set_hglm(self, t):
+        self._need_hglm("HierGLMTarget")
+        if t.D != self.D:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: the model has P + G = {t.P} + {len(t.groups)} parameters, the context has D = {self.D}")
+        X = np.asfortranarray(t.X, dtype=self.dtype)
+        y = np.ascontiguousarray(t.y, dtype=self.dtype)
+        off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
+        p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
+        G = len(t.groups)
+        lo = (C.c_int32 * max(G, 1))(*[g.start for g in t.groups])
+        hi = (C.c_int32 * max(G, 1))(*[g.stop for g in t.groups])
+        cen = (C.c_int32 * max(G, 1))(*[int(g.centered) for g in t.groups])
+        A = (C.c_double * max(G, 1))(*[g.scale for g in t.groups])
+        self._call("ahmc_hglm_set_target", int(t.family), int(t.n_obs), int(t.P), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p),
+                   float(t.scale), G, lo, hi, cen, A)
+
+    def hglm_coefficients(self, theta=None, n_cols=None):
+        """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer
+        (an int) together with `n_cols`: ahmc_hglm_coefficients"""
+        self._need_hglm("hglm_coefficients")
+        P, G = C.c_int64(), C.c_int32()
+        self._call("ahmc_hglm_get_target", C.byref(P), C.byref(G), None, None, None, None)
+        if isinstance(theta, (int, C.c_void_p)):
+            if n_cols is None:
+                raise ArgumentError(capi.ERR_ARGUMENT, "hglm_coefficients: a pointer needs n_cols")
+            ptr, n = (C.c_void_p(theta) if isinstance(theta, int) else theta), int(n_cols)
+        else:
+            th = np.asarray(self.theta() if theta is None else theta)
+            if th.ndim == 1:
+                th = th.reshape(-1, 1)
+            if th.ndim != 2 or th.shape[0] != P.value + G.value or (n_cols is not None and n_cols != th.shape[1]):
+                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({P.value + G.value}, {n_cols if n_cols is not None else 'n'})")
+            th = np.asfortranarray(th, dtype=self.dtype)
+            ptr, n = capi.as_ptr(th), th.shape[1]
+        beta = np.empty((P.value, n), dtype=self.dtype, order="F")
+        tau = np.empty((G.value, n), dtype=self.dtype, order="F")
+        self._call("ahmc_hglm_coefficients", ptr, n, capi.as_ptr(beta) if beta.size else None, capi.as_ptr(tau) if tau.size else None)
+        return beta, tau
 
     def glm_pointwise(self):
         """(η, ℓ(y_i, η_i)) at the context's current θ, each (n_obs, N): ahmc_glm_pointwise"""

@@ -6,6 +6,7 @@
 #include "ahmc_diag.h"
 #include "ahmc_rank_update.h"
 #include "ahmc_glm.h"
+#include "ahmc_glm_hier.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -241,9 +242,15 @@ struct Ctx : CtxBase {
   size_t ru_cap = 0;
   int64_t ru_off[7] = {0, 0, 0, 0, 0, 0, 0};
   int ru_k = 0;
-  // AHMC_TARGET_GLM (ahmc_glm_host.hpp): one slab of X, Xᵀ, y, offset, p, U, partial, gs at glm_off[0..7]
+  // AHMC_TARGET_GLM (ahmc_glm_host.hpp): one slab of X, Xᵀ, y, offset, p, U, partial, gs at glm_off[0..7]; with coefficient groups
+  // (ahmc_glm_hier.h) also W, R, a zero precision and the group table at glm_off[8..11]
   T* glm_buf = nullptr;
-  int64_t glm_off[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t glm_off[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  bool hglm_bound = false;  // bound through ahmc_hglm_set_target (n_groups = 0 included)
+  int64_t hglm_P = 0;
+  int hglm_G = 0;
+  int32_t hglm_lo[32] = {}, hglm_hi[32] = {}, hglm_centered[32] = {};
+  double hglm_A[32] = {};
   int glm_family = 0;
   int64_t glm_nobs = 0;
   bool glm_has_offset = false;
@@ -2195,6 +2202,40 @@ int32_t ahmc_get_target_glm(ahmc_ctx* ctx, int32_t* family, int64_t* n_obs, doub
 
 int32_t ahmc_glm_pointwise(ahmc_ctx* ctx, void* eta_out, void* loglik_out) {
   FOR_CTX_MUT(ctx, { return glm_pointwise(c, eta_out, loglik_out); });
+}
+
+// ---- include/ahmc_glm_hier.h: coefficient groups whose prior scale is sampled ----------------------------------------------------------
+int32_t ahmc_hglm_version(void) { return AHMC_HGLM_VERSION; }
+
+int32_t ahmc_hglm_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset,
+                             const void* prior_prec, double scale, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
+                             const double* hyper_scale) {
+  FOR_CTX_MUT(ctx, {
+    int rc = hglm_set(c, (int)family, n_obs, n_coef, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset),
+                      static_cast<const T*>(prior_prec), scale, (int)n_groups, lo, hi, centered, hyper_scale);
+    if (rc) return rc;
+    return dn_refresh_fused(c);
+  });
+}
+
+int32_t ahmc_hglm_get_target(ahmc_ctx* ctx, int64_t* n_coef, int32_t* n_groups, int32_t* lo, int32_t* hi, int32_t* centered, double* hyper_scale) {
+  FOR_CTX(ctx, {
+    if (c->target_kind != AHMC_TARGET_GLM || !c->hglm_bound)
+      return fail(c, AHMC_ERR_ARGUMENT, "hglm_get_target: no hierarchical GLM is bound (ahmc_hglm_set_target)");
+    if (n_coef) *n_coef = c->D - c->hglm_G;
+    if (n_groups) *n_groups = c->hglm_G;
+    for (int k = 0; k < c->hglm_G; ++k) {
+      if (lo) lo[k] = c->hglm_lo[k];
+      if (hi) hi[k] = c->hglm_hi[k];
+      if (centered) centered[k] = c->hglm_centered[k];
+      if (hyper_scale) hyper_scale[k] = c->hglm_A[k];
+    }
+    return AHMC_OK;
+  });
+}
+
+int32_t ahmc_hglm_coefficients(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* beta_out, void* tau_out) {
+  FOR_CTX_MUT(ctx, { return hglm_coefficients(c, theta, n_cols, beta_out, tau_out); });
 }
 
 }  // extern "C"

@@ -299,4 +299,106 @@ __global__ __launch_bounds__(256) void k_glm_lp(const T* __restrict__ partial, c
   if (lane == 0) lp[c] = sanitize_lp ? sanitize(v) : v;
 }
 
+// ---- include/ahmc_glm_hier.h: coefficient groups whose prior scale is sampled -------------------------------------------------------
+// θ (D = P + G): θ[0:P] coefficient parameters, θ[P + k] = s_k = log τ_k of group k = [lo_k, hi_k).  The products above run on the
+// EFFECTIVE coefficients W (P, N) — w_d = θ_d, or τ_k·θ_d for a member of a non-centred group — with th := W, D := P, prec := 0 and
+// g := R, so R = −Xᵀu; k_hglm_coef makes W before them and k_hglm_finish the chain's ℓπ and all D rows of g after them.  Formulas
+// and the order of every sum: glm.py.  Both are one wave per chain, four chains per block, every group loop wave-uniform.
+constexpr int HGLM_MAX_GROUPS = 32;
+
+template <class T>
+struct HglmTab {  // the group table, in the model's slab
+  int lo[HGLM_MAX_GROUPS], hi[HGLM_MAX_GROUPS], centered[HGLM_MAX_GROUPS];
+  T inv_a2[HGLM_MAX_GROUPS];  // 1/A_k²
+};
+
+// W (column stride P) and / or τ (column stride G) of the listed columns of th (column stride P + G); either output may be nullptr.
+// One exp per (column, group).
+template <class T>
+__global__ __launch_bounds__(256) void k_hglm_coef(const T* __restrict__ th, const HglmTab<T>* __restrict__ tab, T* __restrict__ W, T* __restrict__ tau_out, int P,
+                                                   int G, int64_t ncols, const int* __restrict__ idx) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= ncols) return;
+  const int64_t c = idx ? (int64_t)idx[j] : j;
+  const T* t = th + c * ((int64_t)P + G);
+  T* w = W ? W + c * P : nullptr;
+  int prev = 0;
+  for (int k = 0; k <= G; ++k) {
+    const int lo = k < G ? tab->lo[k] : P;
+    if (w)
+      for (int d = prev + lane; d < lo; d += 64) w[d] = t[d];
+    if (k == G) break;
+    const int hi = tab->hi[k];
+    const T tau = exp(t[P + k]);
+    if (tau_out && lane == 0) tau_out[c * G + k] = tau;
+    if (w) {
+      if (tab->centered[k])
+        for (int d = lo + lane; d < hi; d += 64) w[d] = t[d];
+      else
+        for (int d = lo + lane; d < hi; d += 64) w[d] = tau * t[d];
+    }
+    prev = hi;
+  }
+}
+
+// ℓπ and g of the listed chains from partial (Σℓ per row block), R = −Xᵀu, W and θ.  k_glm_lp's sums first (Σ partial, Σ p_d θ_d² over
+// d < P: members have p_d = 0), then per group, ascending: (S_k, T_k) lane-strided from lo_k and wave_allsum2, the hyperprior, the
+// members' rows of g and the row of s_k; the coefficients in no group last.  No LDS, no atomics.
+template <class T>
+__global__ __launch_bounds__(256) void k_hglm_finish(const T* __restrict__ partial, const T* __restrict__ R, const T* __restrict__ W, const T* __restrict__ prec,
+                                                     const T* __restrict__ th, const HglmTab<T>* __restrict__ tab, T* __restrict__ lp, T* __restrict__ g, int nrb,
+                                                     int P, int G, int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= ncols) return;
+  const int64_t c = idx ? (int64_t)idx[j] : j;
+  const T* t = th + c * ((int64_t)P + G);
+  const T* r = R + c * P;
+  const T* w = W + c * P;
+  T* gc = g + c * ((int64_t)P + G);
+  T s[2] = {0, 0};
+  for (int rb = lane; rb < nrb; rb += 64) s[0] += partial[(int64_t)rb * N + c];
+  for (int d = lane; d < P; d += 64) {
+    const T td = t[d];
+    s[1] = fma(prec[d] * td, td, s[1]);
+  }
+  wave_allsum2<64>(s[0], s[1]);
+  T v = fma(T(-0.5), s[1], s[0]);
+  int prev = 0;
+  for (int k = 0; k <= G; ++k) {
+    const int lo = k < G ? tab->lo[k] : P;
+    for (int d = prev + lane; d < lo; d += 64) gc[d] = fma(prec[d], t[d], r[d]);
+    if (k == G) break;
+    const int hi = tab->hi[k];
+    const bool cen = tab->centered[k] != 0;
+    const T sk = t[P + k], ia2 = tab->inv_a2[k], m = (T)(hi - lo);
+    T a[2] = {0, 0};  // S_k, T_k
+    for (int d = lo + lane; d < hi; d += 64) {
+      const T td = t[d];
+      a[0] = fma(td, td, a[0]);
+      a[1] = fma(r[d], w[d], a[1]);
+    }
+    wave_allsum2<64>(a[0], a[1]);
+    const T e2 = exp(T(2) * sk);
+    const T h = fma(T(-0.5) * e2, ia2, sk), hp = fma(-e2, ia2, T(1));
+    T b, gs;
+    if (cen) {
+      const T q = exp(T(-2) * sk);
+      b = fma(-m, sk, (T(-0.5) * q) * a[0]);
+      gs = fma(-q, a[0], m) - hp;
+      for (int d = lo + lane; d < hi; d += 64) gc[d] = fma(q, t[d], r[d]);
+    } else {
+      const T tau = exp(sk);
+      b = T(-0.5) * a[0];
+      gs = a[1] - hp;
+      for (int d = lo + lane; d < hi; d += 64) gc[d] = fma(tau, r[d], t[d]);
+    }
+    v += h + b;
+    if (lane == 0) gc[P + k] = gs;
+    prev = hi;
+  }
+  if (lane == 0) lp[c] = sanitize_lp ? sanitize(v) : v;
+}
+
 }  // namespace ahmc

@@ -1,5 +1,6 @@
-// ahmc_glm_host.hpp — host side of the generalised-linear-model target (include/ahmc_glm.h; kernels: ahmc_glm.hpp).  Included by
-// ahmc_api.hip after the context, before ahmc_dense_host.hpp, whose dn_other_target routes to glm_target.
+// ahmc_glm_host.hpp — host side of the generalised-linear-model target (include/ahmc_glm.h; kernels: ahmc_glm.hpp) and of its
+// hierarchical form (include/ahmc_glm_hier.h: coefficient groups whose prior scale is sampled).  Included by ahmc_api.hip after the
+// context, before ahmc_dense_host.hpp, whose dn_other_target routes to glm_target.
 #pragma once
 
 // the targets that fill lp and g for a LIST of chains from th, on the step-synchronous engine: the user's kernel and the GLM
@@ -8,7 +9,21 @@ bool listed_target(const Ctx<T>* c) {
   return c->target_kind == AHMC_TARGET_KERNEL || c->target_kind == AHMC_TARGET_GLM;
 }
 
-enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS };
+enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PARTS };
+
+// a hierarchical model's groups as ahmc_hglm_set_target received them (n_groups may be 0: the plain model)
+struct HglmSpec {
+  int64_t P;
+  int G;
+  const int32_t *lo, *hi, *centered;
+  const double* A;
+};
+
+// the columns of X: D, or P when groups are bound (θ then carries the G log-scales after the P coefficient parameters)
+template <class T>
+int64_t glm_ncoef(const Ctx<T>* c) {
+  return c->hglm_G > 0 ? c->hglm_P : c->D;
+}
 
 template <class T>
 int glm_slices(const Ctx<T>* c) {
@@ -23,14 +38,17 @@ int glm_release(Ctx<T>* c) {
   HIPCHK(hipFree(c->glm_buf));
   c->glm_buf = nullptr;
   c->glm_nobs = 0;
+  c->hglm_bound = false;
+  c->hglm_P = 0;
+  c->hglm_G = 0;
   return AHMC_OK;
 }
 
-// η (and from it U, partial; on request η and ℓ themselves) for ncols listed chains
+// η (and from it U, partial; on request η and ℓ themselves) for ncols listed chains; th: the coefficients, (D, N) with column stride D
 template <class T>
-int glm_launch_eta(Ctx<T>* c, const int* list, int64_t ncols, bool small, T* eta_out, T* ll_out) {
+int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols, bool small, T* eta_out, T* ll_out) {
   const T* b = c->glm_buf;
-  const int n_obs = (int)c->glm_nobs, D = (int)c->D;
+  const int n_obs = (int)c->glm_nobs;
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M;
   const T* X = b + c->glm_off[GLM_X];
   const T* y = b + c->glm_off[GLM_Y];
@@ -39,7 +57,7 @@ int glm_launch_eta(Ctx<T>* c, const int* list, int64_t ncols, bool small, T* eta
   T* part = c->glm_buf + c->glm_off[GLM_PART];
   const dim3 grid = small ? dim3((unsigned)nrb, (unsigned)((ncols + 15) / 16)) : dim3((unsigned)(nrb * (((ncols + GB_N - 1) / GB_N + 7) / 8 * 8)));
 #define AHMC_GLM_ETA(FAM, BN) \
-  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)c->glm_scale, (const T*)c->th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out)
+  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)c->glm_scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out)
   switch (c->glm_family * 2 + (small ? 1 : 0)) {
     case 0: AHMC_GLM_ETA(0, 64); break;
     case 1: AHMC_GLM_ETA(0, 16); break;
@@ -71,33 +89,44 @@ template <class T>
 int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   if (n <= 0) return AHMC_OK;
   if (!c->glm_buf) return fail(c, AHMC_ERR_STATE, "AHMC_TARGET_GLM without a model (ahmc_set_target_glm)");
-  const int n_obs = (int)c->glm_nobs, D = (int)c->D, ns = glm_slices(c);
+  // groups bound: the products run on the effective coefficients W (P, N) with a zero precision and leave R = −Xᵀu;
+  // k_hglm_coef before them and k_hglm_finish after them are the model (ahmc_glm.hpp)
+  const bool hier = c->hglm_G > 0;
+  const int n_obs = (int)c->glm_nobs, D = (int)glm_ncoef(c), G = c->hglm_G, ns = glm_slices(c);
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, nrbD = (int64_t)(D + GB_M - 1) / GB_M * ns;
-  int rc = glm_launch_eta(c, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr);
-  if (rc) return rc;
   const T* b = c->glm_buf;
+  const T* th = hier ? b + c->glm_off[GLM_W] : (const T*)c->th;
+  const T* prec = b + c->glm_off[hier ? GLM_ZERO : GLM_PREC];
+  T* g = hier ? c->glm_buf + c->glm_off[GLM_R] : c->g;
+  const HglmTab<T>* tab = reinterpret_cast<const HglmTab<T>*>(b + c->glm_off[GLM_TAB]);
+  if (hier) hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, tab, c->glm_buf + c->glm_off[GLM_W], (T*)nullptr, D, G, n, list);
+  int rc = glm_launch_eta(c, th, D, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr);
+  if (rc) return rc;
   const T* Xt = b + c->glm_off[GLM_XT];
   const T* U = b + c->glm_off[GLM_U];
-  const T* prec = b + c->glm_off[GLM_PREC];
   T* gs = c->glm_buf + c->glm_off[GLM_GS];
   if (glm_small(c, nrbD, n))
-    hipLaunchKernelGGL((k_glm_grad<T, 16>), dim3((unsigned)nrbD, (unsigned)((n + 15) / 16)), dim3(256), 0, c->stream, Xt, U, prec, (const T*)c->th, c->g, gs,
-                       n_obs, D, n, c->N, list, ns);
-  else
-    hipLaunchKernelGGL((k_glm_grad<T, 64>), dim3((unsigned)(nrbD * (((n + GB_N - 1) / GB_N + 7) / 8 * 8))), dim3(256), 0, c->stream, Xt, U, prec,
-                       (const T*)c->th, c->g, gs, n_obs, D, n, c->N, list, ns);
-  if (ns > 1)
-    hipLaunchKernelGGL((k_glm_gsum<T>), dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, (const T*)c->th, c->g, D, n, c->N,
+    hipLaunchKernelGGL((k_glm_grad<T, 16>), dim3((unsigned)nrbD, (unsigned)((n + 15) / 16)), dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, D, n, c->N,
                        list, ns);
-  hipLaunchKernelGGL((k_glm_lp<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], prec, (const T*)c->th, c->lp, (int)nrb, D, n,
-                     c->N, list, sanitize_lp ? 1 : 0);
+  else
+    hipLaunchKernelGGL((k_glm_grad<T, 64>), dim3((unsigned)(nrbD * (((n + GB_N - 1) / GB_N + 7) / 8 * 8))), dim3(256), 0, c->stream, Xt, U, prec, th, g, gs,
+                       n_obs, D, n, c->N, list, ns);
+  if (ns > 1)
+    hipLaunchKernelGGL((k_glm_gsum<T>), dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, th, g, D, n, c->N, list, ns);
+  if (hier)
+    hipLaunchKernelGGL((k_hglm_finish<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], (const T*)g, th,
+                       b + c->glm_off[GLM_PREC], (const T*)c->th, tab, c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0);
+  else
+    hipLaunchKernelGGL((k_glm_lp<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], prec, th, c->lp, (int)nrb, D, n, c->N, list,
+                       sanitize_lp ? 1 : 0);
   HIPCHK(hipGetLastError());
   return AHMC_OK;
 }
 
 template <class T>
-int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale) {
-  const int64_t D = c->D, N = c->N;
+int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, const HglmSpec* hs = nullptr) {
+  const int G = hs ? hs->G : 0;
+  const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the columns of X)
   if (family != AHMC_GLM_BERNOULLI_LOGIT && family != AHMC_GLM_POISSON_LOG && family != AHMC_GLM_GAUSSIAN_IDENTITY)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family));
   if (n_obs < 1) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: n_obs must be >= 1; got " + std::to_string(n_obs));
@@ -106,11 +135,18 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
                                              std::to_string((long long)AHMC_GLM_MAX_OBS));
   if (!X || !y) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: X or y is NULL");
   if (!(std::isfinite(scale) && scale > 0)) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: scale must be finite and > 0; got " + std::to_string(scale));
-  // the slab: X, Xᵀ, y, offset, p, then the workspaces U, partial, gs
+  // the slab: X, Xᵀ, y, offset, p [, a zero precision, the group table], then the workspaces U, partial, gs [, W, R]
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, ns = (n_obs + GLM_K_SLICE - 1) / GLM_K_SLICE;
-  const int64_t sizes[8] = {n_obs * D, n_obs * D, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * D * N : 0};
-  int64_t off[8], total = 0;
-  for (int i = 0; i < 8; ++i) {
+  const int64_t tab_elems = (int64_t)((sizeof(HglmTab<T>) + sizeof(T) - 1) / sizeof(T));
+  int64_t sizes[GLM_PARTS] = {n_obs * D, n_obs * D, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * D * N : 0, 0, 0, 0, 0};
+  if (G > 0) {
+    sizes[GLM_W] = sizes[GLM_R] = D * N;
+    sizes[GLM_ZERO] = D;
+    sizes[GLM_TAB] = tab_elems;
+  }
+  const int layout[GLM_PARTS] = {GLM_X, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_ZERO, GLM_TAB, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R};
+  int64_t off[GLM_PARTS], total = 0;
+  for (int i : layout) {
     off[i] = total;
     total += (sizes[i] + 1) / 2 * 2;  // (16-byte alignment of every part, Float32 included)
   }
@@ -136,6 +172,19 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
     if (!std::isfinite(pd)) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: prior_prec holds a non-finite value");
     if (pd < 0) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: prior_prec[" + std::to_string(d + 1) + "] = " + std::to_string(pd) + " is negative");
   }
+  if (G > 0) {
+    HglmTab<T> tab{};
+    for (int k = 0; k < G; ++k) {
+      for (int64_t d = hs->lo[k]; d < hs->hi[k]; ++d)
+        if ((double)h[off[GLM_PREC] + d] != 0)
+          return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: prior_prec[" + std::to_string(d + 1) + "] must be 0: the coefficient is a member of group " + std::to_string(k + 1));
+      tab.lo[k] = hs->lo[k];
+      tab.hi[k] = hs->hi[k];
+      tab.centered[k] = hs->centered && hs->centered[k] ? 1 : 0;
+      tab.inv_a2[k] = (T)(1.0 / (hs->A[k] * hs->A[k]));
+    }
+    memcpy(h.data() + off[GLM_TAB], &tab, sizeof(tab));
+  }
   T* hXt = h.data() + off[GLM_XT];
   for (int64_t d = 0; d < D; ++d)
     for (int64_t i = 0; i < n_obs; ++i) hXt[d + i * D] = hX[i + d * n_obs];
@@ -144,7 +193,8 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   if (hipMalloc(reinterpret_cast<void**>(&buf), sizeof(T) * (size_t)total) != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, AHMC_ERR_RUNTIME, "set_target_glm: cannot allocate " + std::to_string((long long)(sizeof(T) * (size_t)total)) + " bytes for the model (" +
-                                         std::to_string((long long)(sizeof(T) * (size_t)n_data)) + ") and its workspaces U (n_obs × N), partial and the slice sums");
+                                         std::to_string((long long)(sizeof(T) * (size_t)n_data)) + ") and its workspaces U (n_obs × N), partial and the slice sums" +
+                                         (G > 0 ? ", W and R (n_coef × N)" : ""));
   }
   if (hipMemcpy(buf, h.data(), sizeof(T) * (size_t)n_data, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
     (void)hipFree(buf);
@@ -153,7 +203,16 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   if (c->glm_buf) (void)hipFree(c->glm_buf);  // (the stream is idle)
   if (c->tparams) { (void)hipFree(c->tparams); c->tparams = nullptr; }
   c->glm_buf = buf;
-  for (int i = 0; i < 8; ++i) c->glm_off[i] = off[i];
+  for (int i = 0; i < GLM_PARTS; ++i) c->glm_off[i] = off[i];
+  c->hglm_bound = hs != nullptr;
+  c->hglm_P = hs ? hs->P : 0;
+  c->hglm_G = G;
+  for (int k = 0; k < G; ++k) {
+    c->hglm_lo[k] = hs->lo[k];
+    c->hglm_hi[k] = hs->hi[k];
+    c->hglm_centered[k] = hs->centered && hs->centered[k] ? 1 : 0;
+    c->hglm_A[k] = hs->A[k];
+  }
   c->glm_family = family;
   c->glm_nobs = n_obs;
   c->glm_has_offset = offset != nullptr;
@@ -175,7 +234,14 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
     return fail(c, AHMC_ERR_RUNTIME, "glm_pointwise: cannot allocate " + std::to_string((long long)(sizeof(T) * 2 * n)) + " bytes");
   }
   const int64_t nrb = (c->glm_nobs + GB_M - 1) / GB_M;
-  int rc = glm_launch_eta(c, (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_out ? tmp : (T*)nullptr, ll_out ? tmp + n : (T*)nullptr);
+  const T* th = c->th;
+  if (c->hglm_G > 0) {  // the effective coefficients first
+    T* W = c->glm_buf + c->glm_off[GLM_W];
+    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th,
+                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, (T*)nullptr, (int)c->hglm_P, c->hglm_G, c->N, (const int*)nullptr);
+    th = W;
+  }
+  int rc = glm_launch_eta(c, th, (int)glm_ncoef(c), (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_out ? tmp : (T*)nullptr, ll_out ? tmp + n : (T*)nullptr);
   hipError_t e = hipSuccess;
   if (!rc && eta_out) e = hipMemcpyAsync(eta_out, tmp, sizeof(T) * n, hipMemcpyDefault, c->stream);
   if (!rc && e == hipSuccess && ll_out) e = hipMemcpyAsync(ll_out, tmp + n, sizeof(T) * n, hipMemcpyDefault, c->stream);
@@ -183,5 +249,66 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
   (void)hipFree(tmp);
   if (rc) return rc;
   if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("glm_pointwise: ") + hipGetErrorString(e != hipSuccess ? e : es));
+  return AHMC_OK;
+}
+
+// ---- include/ahmc_glm_hier.h ----
+template <class T>
+int hglm_set(Ctx<T>* c, int family, int64_t n_obs, int64_t n_coef, const T* X, const T* y, const T* offset, const T* prec, double scale, int n_groups,
+             const int32_t* lo, const int32_t* hi, const int32_t* centered, const double* A) {
+  if (n_groups < 0) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: n_groups must be >= 0; got " + std::to_string(n_groups));
+  if (n_groups > AHMC_HGLM_MAX_GROUPS)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "hglm_set_target: n_groups = " + std::to_string(n_groups) + " is beyond the engine's limit AHMC_HGLM_MAX_GROUPS = " +
+                                             std::to_string(AHMC_HGLM_MAX_GROUPS));
+  if (n_coef < 1 || c->D != n_coef + n_groups)
+    return fail(c, AHMC_ERR_ARGUMENT, "DimensionMismatch: the context has D = " + std::to_string((long long)c->D) + ", the model n_coef + n_groups = " +
+                                          std::to_string((long long)n_coef) + " + " + std::to_string(n_groups));
+  if (n_groups > 0 && (!lo || !hi || !A)) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: lo, hi or hyper_scale is NULL");
+  int64_t prev = 0;
+  for (int k = 0; k < n_groups; ++k) {
+    const std::string grp = "group " + std::to_string(k + 1) + " = [" + std::to_string(lo[k]) + ", " + std::to_string(hi[k]) + ")";
+    if (lo[k] < 0 || hi[k] > n_coef) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is out of bounds [0, " + std::to_string((long long)n_coef) + ")");
+    if (hi[k] <= lo[k]) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is empty");
+    if (lo[k] < prev) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " overlaps the group before it or is out of order");
+    if (!(std::isfinite(A[k]) && A[k] > 0))
+      return fail(c, AHMC_ERR_ARGUMENT, "DomainError: hyper_scale[" + std::to_string(k + 1) + "] = " + std::to_string(A[k]) + " must be finite and > 0");
+    prev = hi[k];
+  }
+  const HglmSpec hs{n_coef, n_groups, lo, hi, centered, A};
+  return glm_set(c, family, n_obs, X, y, offset, prec, scale, &hs);
+}
+
+// β (P, n_cols) and / or τ (G, n_cols) of any (D, n_cols) array of draws, host or device pointers
+template <class T>
+int hglm_coefficients(Ctx<T>* c, const void* theta, int64_t n_cols, void* beta_out, void* tau_out) {
+  if (c->target_kind != AHMC_TARGET_GLM || !c->glm_buf || !c->hglm_bound)
+    return fail(c, AHMC_ERR_ARGUMENT, "hglm_coefficients: no hierarchical GLM is bound (ahmc_hglm_set_target)");
+  if (n_cols < 0 || (n_cols > 0 && !theta)) return fail(c, AHMC_ERR_ARGUMENT, "hglm_coefficients: theta is NULL or n_cols < 0");
+  if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, "hglm_coefficients: n_cols beyond 2^31 - 1");
+  if (n_cols == 0 || (!beta_out && !tau_out)) return AHMC_OK;
+  const int64_t P = glm_ncoef(c), G = c->hglm_G, D = P + G;
+  if (G == 0) {  // the plain model: β = θ
+    if (beta_out) HIPCHK(hipMemcpyAsync(beta_out, theta, sizeof(T) * (size_t)(P * n_cols), hipMemcpyDefault, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return AHMC_OK;
+  }
+  T* tmp = nullptr;
+  const size_t total = (size_t)((D + P + G) * n_cols);
+  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * total) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, AHMC_ERR_RUNTIME, "hglm_coefficients: cannot allocate " + std::to_string((long long)(sizeof(T) * total)) + " bytes");
+  }
+  T *th = tmp, *W = tmp + D * n_cols, *tau = W + P * n_cols;
+  hipError_t e = hipMemcpyAsync(th, theta, sizeof(T) * (size_t)(D * n_cols), hipMemcpyDefault, c->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, c->stream, (const T*)th,
+                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, tau, (int)P, (int)G, n_cols, (const int*)nullptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && beta_out) e = hipMemcpyAsync(beta_out, W, sizeof(T) * (size_t)(P * n_cols), hipMemcpyDefault, c->stream);
+  if (e == hipSuccess && tau_out) e = hipMemcpyAsync(tau_out, tau, sizeof(T) * (size_t)(G * n_cols), hipMemcpyDefault, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  (void)hipFree(tmp);
+  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("hglm_coefficients: ") + hipGetErrorString(e != hipSuccess ? e : es));
   return AHMC_OK;
 }

@@ -516,5 +516,6 @@ include("AdvancedHMCMI355XDiag.jl")  # summarystats_device: include/ahmc_diag.h
 include("AdvancedHMCMI355XRankUpdate.jl")  # set_metric!(z, ::RankUpdateEuclideanMetric): include/ahmc_rank_update.h
 include("AdvancedHMCMI355XLowRankAdapt.jl")  # lowrank_adaptor_init!: include/ahmc_lowrank_adapt.h
 include("AdvancedHMCMI355XGLM.jl")  # set_target!(z, ::GLMTarget), glm_pointwise: include/ahmc_glm.h
+include("AdvancedHMCMI355XGLMHier.jl")  # set_target!(z, ::HierGLMTarget), hglm_coefficients: include/ahmc_glm_hier.h
 
 end # module
