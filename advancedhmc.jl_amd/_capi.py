@@ -221,6 +221,17 @@ HGLM_SIGNATURES = {
     "ahmc_hglm_coefficients": (_i32, [_vp, _vp, _i64, _vp, _vp]),
 }
 
+# include/ahmc_glm_aux.h: families of the GLM target whose dispersion is sampled (likewise: the HIP engine only)
+AHMC_GLM_AUX_VERSION = 1
+GLM_AUX_MAX_GROUPS = 31
+GLM_GAUSSIAN_IDENTITY_SIGMA, GLM_NEGBINOMIAL_LOG = 3, 4
+GLM_AUX_SIGNATURES = {
+    "ahmc_glm_aux_version": (_i32, []),
+    "ahmc_glm_aux_set_target": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _pi32, _pi32, _pi32, C.POINTER(_f64), _f64, _f64]),
+    "ahmc_glm_aux_get_target": (_i32, [_vp, C.POINTER(_f64), C.POINTER(_f64)]),
+    "ahmc_glm_dispersion": (_i32, [_vp, _vp, _i64, _vp]),
+}
+
 class CLib:
     """One loaded implementation of the ABI."""
 
@@ -294,6 +305,16 @@ class CLib:
             v = self.dll.ahmc_hglm_version()
             if v != AHMC_HGLM_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm_hier version {v}, expected {AHMC_HGLM_VERSION}")
+        # ahmc_glm_aux.h: likewise
+        gaux = [getattr(self.dll, name, None) for name in GLM_AUX_SIGNATURES]
+        self.has_glm_aux = all(fn is not None for fn in gaux)
+        if self.has_glm_aux:
+            for fn, (res, args) in zip(gaux, GLM_AUX_SIGNATURES.values()):
+                fn.restype = res
+                fn.argtypes = args
+            v = self.dll.ahmc_glm_aux_version()
+            if v != AHMC_GLM_AUX_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_aux version {v}, expected {AHMC_GLM_AUX_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

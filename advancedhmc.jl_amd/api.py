@@ -304,14 +304,17 @@ class KernelTarget:
 class GLMTarget:
     """A generalised linear model as the target (include/ahmc_glm.h; arithmetic: advancedhmc.jl_amd/glm.py):
         ℓπ(θ) = Σ_i ℓ(y_i, (Xθ + offset)_i) − ½ Σ_d p_d θ_d²,    X (n_obs, D), D = X.shape[1]
-    with `family` "bernoulli_logit" (0 <= y <= 1), "poisson_log" (y >= 0) or "gaussian_identity" (scale = 1/σ²).  The prior is
+    with `family` "bernoulli_logit" (0 <= y <= 1), "poisson_log" (y >= 0) or "gaussian_identity" (scale = 1/σ²); or a family whose
+    dispersion is sampled (include/ahmc_glm_aux.h): "gaussian_identity_sigma" (unknown noise σ) or "negbinomial_log" (NB2 counts,
+    variance μ + μ²/φ).  θ then has one more row, LAST: s = log σ or log φ, with the prior s ~ Normal(*aux_prior) = (loc, scale),
+    default (0, 1), and `.D` counts it; `.dispersion(θ)` gives σ or φ of draws.  The prior of the coefficients is
     N(0, prior_scale²) per coefficient — `prior_scale` a scalar or (D,) — or given as its precision `prior_prec`; neither: flat.
     The engine evaluates all chains at once, X·Θ and Xᵀ·U on the MFMA units.  HIP engine only (the CPU checker takes the same
     density as `ExternalTarget(D, lambda th: glm.logdensity(...))` or a host KernelTarget)."""
     kind = capi.TARGET_GLM
     params = None
 
-    def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0):
+    def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None):
         X = np.asarray(X, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64).ravel()
         if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.size != X.shape[0]:
@@ -322,13 +325,23 @@ class GLMTarget:
             raise ArgumentError(capi.ERR_ARGUMENT, str(e))
         if prior_scale is not None and prior_prec is not None:
             raise ArgumentError(capi.ERR_ARGUMENT, "GLMTarget: give prior_scale or prior_prec, not both")
+        self.aux = self.family in _glm.AUX_FAMILIES
+        if aux_prior is not None and not self.aux:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"GLMTarget: aux_prior belongs to the families with a sampled dispersion, not to family {self.family}")
+        if self.aux and scale != 1.0:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"GLMTarget: family {self.family} samples its dispersion; scale does not apply")
+        try:
+            self.aux_prior = _glm.check_aux_prior(aux_prior) if self.aux else None
+        except (ValueError, TypeError) as e:
+            raise ArgumentError(capi.ERR_ARGUMENT, str(e))
         self.X = np.asfortranarray(X)
         self.y = y
-        self.D = X.shape[1]
+        self.P = X.shape[1]
+        self.D = self.P + (1 if self.aux else 0)
         self.n_obs = X.shape[0]
         if prior_scale is not None:
             prior_prec = 1.0 / np.square(np.asarray(prior_scale, dtype=np.float64))
-        self.prior_prec = None if prior_prec is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prior_prec, dtype=np.float64), (self.D,)))
+        self.prior_prec = None if prior_prec is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prior_prec, dtype=np.float64), (self.P,)))
         self.offset = None if offset is None else np.asarray(offset, dtype=np.float64).ravel()
         if self.offset is not None and self.offset.size != self.n_obs:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: offset {self.offset.shape}, n_obs {self.n_obs}")
@@ -336,7 +349,13 @@ class GLMTarget:
 
     def logdensity(self, theta):
         """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
-        return _glm.logdensity(self.family, self.X, self.y, theta, self.offset, self.prior_prec, self.scale)
+        return _glm.logdensity(self.family, self.X, self.y, theta, self.offset, self.prior_prec, self.scale, self.aux_prior)
+
+    def dispersion(self, theta):
+        """σ or φ = exp(s) of draws θ (D, n) by the numpy mirror (a family with a sampled dispersion)"""
+        if not self.aux:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"dispersion: family {self.family} has no sampled dispersion")
+        return _glm.dispersion(theta)
 
     def __repr__(self):
         return f"GLMTarget(n_obs={self.n_obs}, D={self.D}, family={self.family})"
@@ -359,8 +378,8 @@ class HierGLMTarget(GLMTarget):
     then log τ of each group.  `prior_scale` / `prior_prec` cover the coefficients in no group; on members they are forced to 0.
     `.coefficients(θ)` gives (β, τ) on the model's own scale.  HIP engine only."""
 
-    def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0):
-        super().__init__(X, y, family=family, prior_scale=prior_scale, prior_prec=prior_prec, offset=offset, scale=scale)
+    def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None):
+        super().__init__(X, y, family=family, prior_scale=prior_scale, prior_prec=prior_prec, offset=offset, scale=scale, aux_prior=aux_prior)
         self.P = self.X.shape[1]
         groups = [g if isinstance(g, CoefGroup) else CoefGroup(*g) for g in groups]
         try:
@@ -368,7 +387,7 @@ class HierGLMTarget(GLMTarget):
         except (ValueError, TypeError) as e:
             raise ArgumentError(capi.ERR_ARGUMENT, str(e))
         self.groups = tuple(CoefGroup(int(g.start), int(g.stop), bool(g.centered), float(g.scale)) for g in groups)
-        self.D = self.P + len(self.groups)
+        self.D = self.P + len(self.groups) + (1 if self.aux else 0)
         if self.prior_prec is not None:
             self.prior_prec = self.prior_prec.copy()
             for g in self.groups:
@@ -376,11 +395,12 @@ class HierGLMTarget(GLMTarget):
 
     def logdensity(self, theta):
         """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
-        return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale)
+        return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale, self.aux_prior)
 
     def coefficients(self, theta):
         """(β (P, n), τ (G, n)) of draws θ (D, n) by the numpy mirror"""
-        return _glm.hier_coefficients(theta, self.P, self.groups)
+        th = np.asarray(theta, dtype=np.float64)
+        return _glm.hier_coefficients(th[:-1] if self.aux else th, self.P, self.groups)
 
     def __repr__(self):
         return f"HierGLMTarget(n_obs={self.n_obs}, P={self.P}, groups={len(self.groups)}, family={self.family})"
@@ -718,6 +738,9 @@ class Engine:
                                                  n_params=-1 if p is None else p.size)
             self._call("ahmc_set_target_plugin", so.encode(), capi.as_ptr(p), 0 if p is None else p.size)
             return
+        if isinstance(target, GLMTarget) and target.aux:
+            self._set_glm_aux(target)
+            return
         if isinstance(target, HierGLMTarget):
             self._set_hglm(target)
             return
@@ -767,6 +790,47 @@ class Engine:
         self._call("ahmc_hglm_set_target", int(t.family), int(t.n_obs), int(t.P), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p),
                    float(t.scale), G, lo, hi, cen, A)
 
+    def _need_glm_aux(self, what):
+        if not getattr(self.lib, "has_glm_aux", False):
+            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_glm_aux.h")
+
+    def _set_glm_aux(self, t):
+        self._need_glm_aux(f"GLMTarget(family={t.family})")
+        groups = getattr(t, "groups", ())
+        if t.D != self.D:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: the model has P + G + 1 = {t.P} + {len(groups)} + 1 parameters, the context has D = {self.D}")
+        X = np.asfortranarray(t.X, dtype=self.dtype)
+        y = np.ascontiguousarray(t.y, dtype=self.dtype)
+        off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
+        p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
+        G = len(groups)
+        lo = (C.c_int32 * max(G, 1))(*[g.start for g in groups])
+        hi = (C.c_int32 * max(G, 1))(*[g.stop for g in groups])
+        cen = (C.c_int32 * max(G, 1))(*[int(g.centered) for g in groups])
+        A = (C.c_double * max(G, 1))(*[g.scale for g in groups])
+        self._call("ahmc_glm_aux_set_target", int(t.family), int(t.n_obs), int(t.P), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p),
+                   G, lo, hi, cen, A, float(t.aux_prior[0]), float(t.aux_prior[1]))
+
+    def glm_dispersion(self, theta=None, n_cols=None):
+        """σ or φ = exp(s) (n_cols,) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer (an
+        int) together with `n_cols`: ahmc_glm_dispersion"""
+        self._need_glm_aux("glm_dispersion")
+        if isinstance(theta, (int, C.c_void_p)):
+            if n_cols is None:
+                raise ArgumentError(capi.ERR_ARGUMENT, "glm_dispersion: a pointer needs n_cols")
+            ptr, n = (C.c_void_p(theta) if isinstance(theta, int) else theta), int(n_cols)
+        else:
+            th = np.asarray(self.theta() if theta is None else theta)
+            if th.ndim == 1:
+                th = th.reshape(-1, 1)
+            if th.ndim != 2 or th.shape[0] != self.D or (n_cols is not None and n_cols != th.shape[1]):
+                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({self.D}, {n_cols if n_cols is not None else 'n'})")
+            th = np.asfortranarray(th, dtype=self.dtype)
+            ptr, n = capi.as_ptr(th), th.shape[1]
+        out = np.empty(n, dtype=self.dtype)
+        self._call("ahmc_glm_dispersion", ptr, n, capi.as_ptr(out) if n else None)
+        return out
+
     def hglm_coefficients(self, theta=None, n_cols=None):
         """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer
         (an int) together with `n_cols`: ahmc_hglm_coefficients"""
@@ -781,8 +845,8 @@ class Engine:
             th = np.asarray(self.theta() if theta is None else theta)
             if th.ndim == 1:
                 th = th.reshape(-1, 1)
-            if th.ndim != 2 or th.shape[0] != P.value + G.value or (n_cols is not None and n_cols != th.shape[1]):
-                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({P.value + G.value}, {n_cols if n_cols is not None else 'n'})")
+            if th.ndim != 2 or th.shape[0] != self.D or (n_cols is not None and n_cols != th.shape[1]):
+                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({self.D}, {n_cols if n_cols is not None else 'n'})")
             th = np.asfortranarray(th, dtype=self.dtype)
             ptr, n = capi.as_ptr(th), th.shape[1]
         beta = np.empty((P.value, n), dtype=self.dtype, order="F")

@@ -7,6 +7,7 @@
 #include "ahmc_rank_update.h"
 #include "ahmc_glm.h"
 #include "ahmc_glm_hier.h"
+#include "ahmc_glm_aux.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -243,9 +244,12 @@ struct Ctx : CtxBase {
   int64_t ru_off[7] = {0, 0, 0, 0, 0, 0, 0};
   int ru_k = 0;
   // AHMC_TARGET_GLM (ahmc_glm_host.hpp): one slab of X, Xᵀ, y, offset, p, U, partial, gs at glm_off[0..7]; with coefficient groups
-  // (ahmc_glm_hier.h) also W, R, a zero precision and the group table at glm_off[8..11]
+  // (ahmc_glm_hier.h) also W, R, a zero precision and the group table at glm_off[8..11]; with a sampled dispersion (ahmc_glm_aux.h)
+  // also partial_s at glm_off[12]
   T* glm_buf = nullptr;
-  int64_t glm_off[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t glm_off[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  bool glm_aux = false;  // θ ends with s, the log dispersion; its prior Normal(glm_aux_loc, glm_aux_scale²)
+  double glm_aux_loc = 0, glm_aux_scale = 1;
   bool hglm_bound = false;  // bound through ahmc_hglm_set_target (n_groups = 0 included)
   int64_t hglm_P = 0;
   int hglm_G = 0;
@@ -2222,7 +2226,7 @@ int32_t ahmc_hglm_get_target(ahmc_ctx* ctx, int64_t* n_coef, int32_t* n_groups, 
   FOR_CTX(ctx, {
     if (c->target_kind != AHMC_TARGET_GLM || !c->hglm_bound)
       return fail(c, AHMC_ERR_ARGUMENT, "hglm_get_target: no hierarchical GLM is bound (ahmc_hglm_set_target)");
-    if (n_coef) *n_coef = c->D - c->hglm_G;
+    if (n_coef) *n_coef = c->D - c->hglm_G - (c->glm_aux ? 1 : 0);
     if (n_groups) *n_groups = c->hglm_G;
     for (int k = 0; k < c->hglm_G; ++k) {
       if (lo) lo[k] = c->hglm_lo[k];
@@ -2236,6 +2240,34 @@ int32_t ahmc_hglm_get_target(ahmc_ctx* ctx, int64_t* n_coef, int32_t* n_groups, 
 
 int32_t ahmc_hglm_coefficients(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* beta_out, void* tau_out) {
   FOR_CTX_MUT(ctx, { return hglm_coefficients(c, theta, n_cols, beta_out, tau_out); });
+}
+
+// ---- include/ahmc_glm_aux.h: families whose dispersion is sampled ---------------------------------------------------------------------
+int32_t ahmc_glm_aux_version(void) { return AHMC_GLM_AUX_VERSION; }
+
+int32_t ahmc_glm_aux_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset,
+                                const void* prior_prec, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
+                                const double* hyper_scale, double aux_loc, double aux_scale) {
+  FOR_CTX_MUT(ctx, {
+    int rc = hglm_set(c, (int)family, n_obs, n_coef, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset),
+                      static_cast<const T*>(prior_prec), 1.0, (int)n_groups, lo, hi, centered, hyper_scale, true, aux_loc, aux_scale);
+    if (rc) return rc;
+    return dn_refresh_fused(c);
+  });
+}
+
+int32_t ahmc_glm_aux_get_target(ahmc_ctx* ctx, double* aux_loc, double* aux_scale) {
+  FOR_CTX(ctx, {
+    if (c->target_kind != AHMC_TARGET_GLM || !c->glm_aux)
+      return fail(c, AHMC_ERR_ARGUMENT, "glm_aux_get_target: no model with a sampled dispersion is bound (ahmc_glm_aux_set_target)");
+    if (aux_loc) *aux_loc = c->glm_aux_loc;
+    if (aux_scale) *aux_scale = c->glm_aux_scale;
+    return AHMC_OK;
+  });
+}
+
+int32_t ahmc_glm_dispersion(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* out) {
+  FOR_CTX_MUT(ctx, { return glm_dispersion(c, theta, n_cols, out); });
 }
 
 }  // extern "C"

@@ -140,14 +140,81 @@ __device__ __forceinline__ void glm_link(T y, T eta, T scale, T& ll, T& u) {
   }
 }
 
+// ---- include/ahmc_glm_aux.h: families whose dispersion is sampled (FAM >= 3) -----------------------------------------------------------
+// (L, Ψ) = (lgamma(y + φ) − lgamma(φ), ψ(y + φ) − ψ(φ)) as differences (glm.py: gamma_diffs): both arguments shifted by 8 with the
+// recurrence, then Stirling's series, eight terms by Horner's rule in 1/x².  y = 0 gives exact zeros for a finite φ > 0; φ = 0 or
+// φ = ∞ gives a non-finite L (ℓπ is then sanitised).  The recurrence loop stays rolled: one log1p and two divisions of code.
+template <class T>
+__device__ __forceinline__ T glm_stirling(const T (&c)[8], T z2) {
+  T a = c[7];
+#pragma unroll
+  for (int k = 6; k >= 0; --k) a = fma(a, z2, c[k]);
+  return a;
+}
+
+template <class T>
+__device__ __forceinline__ void glm_gamma_diffs(T y, T phi, T& L, T& Psi) {
+  const T cs[8] = {T(1.0 / 12), T(-1.0 / 360), T(1.0 / 1260), T(-1.0 / 1680), T(1.0 / 1188), T(-691.0 / 360360), T(1.0 / 156), T(-3617.0 / 122400)};
+  const T ct[8] = {T(1.0 / 12), T(-1.0 / 120), T(1.0 / 252), T(-1.0 / 240), T(1.0 / 132), T(-691.0 / 32760), T(1.0 / 12), T(-3617.0 / 8160)};
+  const T A = phi + T(8), B = A + y;
+  const T z = y / A, lz = log1p(z);
+  const T za = T(1) / A, zb = T(1) / B;
+  const T za2 = za * za, zb2 = zb * zb;
+  // (each product a statement of its own: written as one expression the difference contracts into fma(zb, S(B), −(za·S(A))), which
+  // is not 0 at y = 0, where B = A)
+  const T sb = zb * glm_stirling(cs, zb2), sa = za * glm_stirling(cs, za2);
+  const T tb = zb2 * glm_stirling(ct, zb2), ta = za2 * glm_stirling(ct, za2);
+  const T dS = sb - sa, dT = tb - ta;
+  T sl = T(0), sp = T(0), pj = phi;
+#pragma unroll 1
+  for (int j = 0; j < 8; ++j) {
+    const T t = y / pj;
+    sl += log1p(t);
+    sp += t / (y + pj);
+    pj += T(1);  // (φ + j: exact steps whenever φ + j is, as in the mirror's phi + j, for φ < 2^p)
+  }
+  L = (fma(A - T(0.5), lz, y * (log(B) - T(1))) + dS) - sl;
+  Psi = ((sp + lz) + (T(0.5) * z) / B) - dT;
+}
+
+// (ℓ, u = ∂ℓ/∂η, ∂ℓ/∂s) of one observation; s = the chain's log dispersion, cs = exp(−2s) (FAM 3) or φ = exp(s) (FAM 4), made
+// once per tile column.  AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA (3), AHMC_GLM_NEGBINOMIAL_LOG (4).
+template <class T, int FAM>
+__device__ __forceinline__ void glm_link_aux(T y, T eta, T s, T cs, T& ll, T& u, T& ds) {
+  if constexpr (FAM == 3) {
+    const T r = y - eta;
+    u = cs * r;
+    ll = fma(T(-0.5) * u, r, -s);
+    ds = fma(u, r, T(-1));
+  } else {
+    const T d = eta - s;
+    const T e = exp(-fabs(d));
+    const T l = log1p(e);
+    const T dd = T(1) + e;
+    const T sig = d >= T(0) ? T(1) / dd : e / dd;    // σ(d) and 1 − σ(d) from the same exp(−|d|)
+    const T nsig = d >= T(0) ? e / dd : T(1) / dd;
+    const T sp = (d > T(0) ? d : T(0)) + l;          // log(μ + φ) − s
+    const T sn = (d < T(0) ? -d : T(0)) + l;         // log(μ + φ) − η
+    const T yp = y + cs;
+    T L, Psi;
+    glm_gamma_diffs(y, cs, L, Psi);
+    ll = fma(-y, sn, fma(-cs, sp, L));
+    u = fma(-yp, sig, y);
+    ds = fma(cs, Psi - sp, fma(-yp, nsig, cs));
+  }
+}
+
 // η = X·Θ + offset for the listed chains, and from it in registers u → U (n_obs, N) and the tile's Σ_rows ℓ → partial[row block][chain].
 // Tile rows are observations, tile columns chains, K = D.  η itself is stored only on request (ahmc_glm_pointwise: eta_out / ll_out,
 // (n_obs, N) arrays).  U leaves through LDS so that a wave writes 64 consecutive observations of one chain; ℓ is summed over the
 // tile's 64 rows in ascending row order by one thread per column (rows past n_obs contribute +0).
+// FAM >= 3: the chain's log dispersion s is read from aux[col·aux_ld] (row D_θ − 1 of the chain's own θ, not of `th`, which holds the
+// effective coefficients), once per tile column, and Σ_rows ∂ℓ/∂s goes to partial_s[row block][chain] by the same column sum.
 template <class T, int FAM, int BN>
 __global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const T* __restrict__ y, const T* __restrict__ off, T scale, const T* __restrict__ th,
                                                  T* __restrict__ U, T* __restrict__ partial, int n_obs, int D, int64_t ncols, int64_t N,
-                                                 const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out) {
+                                                 const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out, const T* __restrict__ aux,
+                                                 int64_t aux_ld, T* __restrict__ partial_s) {
   using S = GlmShape<BN>;
   using Mf = Mfma<T>;
   __shared__ T smem[S::SMEM];
@@ -171,6 +238,18 @@ __global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const 
   }
   const int wm = (w % S::WR) * 16 * S::MI, wn = (w / S::WR) * 16 * S::MI;
   T ll[S::MI][S::MI][4];
+  constexpr int AM = FAM >= 3 ? S::MI : 1;          // (the legacy families carry none of the three)
+  [[maybe_unused]] T ds[AM][AM][4];                 // ∂ℓ/∂s
+  [[maybe_unused]] T sv[AM], cv[AM];                // s and exp(−2s) / exp(s) of this thread's tile columns
+  if constexpr (FAM >= 3) {
+#pragma unroll
+    for (int tj = 0; tj < S::MI; ++tj) {
+      const int64_t j = n0 + wn + tj * 16 + (lane & 15);
+      const T sj = j < ncols ? aux[(idx ? (int64_t)idx[j] : j) * aux_ld] : T(0);
+      sv[tj] = sj;
+      cv[tj] = FAM == 3 ? exp(T(-2) * sj) : exp(sj);
+    }
+  }
   // u → smem[column][row]
 #pragma unroll
   for (int ti = 0; ti < S::MI; ++ti)
@@ -184,12 +263,15 @@ __global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const 
         const int rl = wm + ti * 16 + Mf::row(lane, v);
         const int row = m0 + rl;
         T l = T(0), u = T(0);
+        [[maybe_unused]] T dl = T(0);
         if (row < n_obs && col >= 0) {
           const T eta = off ? acc[ti][tj][v] + off[row] : acc[ti][tj][v];
-          glm_link<T, FAM>(y[row], eta, scale, l, u);
+          if constexpr (FAM >= 3) glm_link_aux<T, FAM>(y[row], eta, sv[tj], cv[tj], l, u, dl);
+          else glm_link<T, FAM>(y[row], eta, scale, l, u);
           if (eta_out) eta_out[row + col * n_obs] = eta;
           if (ll_out) ll_out[row + col * n_obs] = l;
         }
+        if constexpr (FAM >= 3) ds[ti][tj][v] = dl;
         ll[ti][tj][v] = l;
         smem[cl * S::LDE + rl] = u;
       }
@@ -216,6 +298,23 @@ __global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const 
     T s = T(0);
     for (int r = 0; r < GB_M; ++r) s += smem[r * (BN + 1) + tid];
     partial[(int64_t)rblk * N + col] = s;
+  }
+  if constexpr (FAM >= 3) {
+    // ∂ℓ/∂s → smem[row][column], the same column sums
+    __syncthreads();
+#pragma unroll
+    for (int ti = 0; ti < S::MI; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < S::MI; ++tj)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) smem[(wm + ti * 16 + Mf::row(lane, v)) * (BN + 1) + wn + tj * 16 + (lane & 15)] = ds[ti][tj][v];
+    __syncthreads();
+    if (tid < BN && n0 + tid < ncols) {
+      const int64_t col = idx ? (int64_t)idx[n0 + tid] : n0 + tid;
+      T s = T(0);
+      for (int r = 0; r < GB_M; ++r) s += smem[r * (BN + 1) + tid];
+      partial_s[(int64_t)rblk * N + col] = s;
+    }
   }
 }
 
@@ -342,21 +441,36 @@ __global__ __launch_bounds__(256) void k_hglm_coef(const T* __restrict__ th, con
   }
 }
 
+// dst (nr, n) = rows r0 .. r0 + nr − 1 of src (ld, n): the group scales, or the dispersion, out of k_hglm_coef's τ when the table
+// carries the dispersion's empty group
+template <class T>
+__global__ __launch_bounds__(256) void k_glm_rows(const T* __restrict__ src, int ld, int r0, int nr, int64_t n, T* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * nr) return;
+  dst[i] = src[(i / nr) * ld + r0 + (int)(i % nr)];
+}
+
 // ℓπ and g of the listed chains from partial (Σℓ per row block), R = −Xᵀu, W and θ.  k_glm_lp's sums first (Σ partial, Σ p_d θ_d² over
 // d < P: members have p_d = 0), then per group, ascending: (S_k, T_k) lane-strided from lo_k and wave_allsum2, the hyperprior, the
 // members' rows of g and the row of s_k; the coefficients in no group last.  No LDS, no atomics.
-template <class T>
-__global__ __launch_bounds__(256) void k_hglm_finish(const T* __restrict__ partial, const T* __restrict__ R, const T* __restrict__ W, const T* __restrict__ prec,
-                                                     const T* __restrict__ th, const HglmTab<T>* __restrict__ tab, T* __restrict__ lp, T* __restrict__ g, int nrb,
-                                                     int P, int G, int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp) {
+//
+// AUX (include/ahmc_glm_aux.h): θ has one more row, s = the log of the family's dispersion, after the G log-scales.  Σ_row blocks
+// partial_s (= Σ_i ∂ℓ/∂s) is summed beside Σ partial in the same lane-strided order and by a butterfly of its own; after the groups
+// the prior s ~ Normal(m, A²) is added: r = s − m, ℓπ = fma((−½/A²)·r, r, ℓπ), g[D−1] = fma(r, 1/A², −Σ ∂ℓ/∂s).
+template <class T, bool AUX>
+__device__ __forceinline__ void hglm_finish_body(const T* __restrict__ partial, const T* __restrict__ R, const T* __restrict__ W, const T* __restrict__ prec,
+                                                 const T* __restrict__ th, const HglmTab<T>* __restrict__ tab, T* __restrict__ lp, T* __restrict__ g, int nrb, int P,
+                                                 int G, int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp, const T* __restrict__ partial_s,
+                                                 T aux_loc, T aux_ia2) {
+  const int64_t ldt = (int64_t)P + G + (AUX ? 1 : 0);
   const int lane = threadIdx.x & 63;
   const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= ncols) return;
   const int64_t c = idx ? (int64_t)idx[j] : j;
-  const T* t = th + c * ((int64_t)P + G);
+  const T* t = th + c * ldt;
   const T* r = R + c * P;
   const T* w = W + c * P;
-  T* gc = g + c * ((int64_t)P + G);
+  T* gc = g + c * ldt;
   T s[2] = {0, 0};
   for (int rb = lane; rb < nrb; rb += 64) s[0] += partial[(int64_t)rb * N + c];
   for (int d = lane; d < P; d += 64) {
@@ -364,6 +478,11 @@ __global__ __launch_bounds__(256) void k_hglm_finish(const T* __restrict__ parti
     s[1] = fma(prec[d] * td, td, s[1]);
   }
   wave_allsum2<64>(s[0], s[1]);
+  T dsum[2] = {0, 0};
+  if constexpr (AUX) {
+    for (int rb = lane; rb < nrb; rb += 64) dsum[0] += partial_s[(int64_t)rb * N + c];
+    wave_allsum2<64>(dsum[0], dsum[1]);
+  }
   T v = fma(T(-0.5), s[1], s[0]);
   int prev = 0;
   for (int k = 0; k <= G; ++k) {
@@ -398,7 +517,27 @@ __global__ __launch_bounds__(256) void k_hglm_finish(const T* __restrict__ parti
     if (lane == 0) gc[P + k] = gs;
     prev = hi;
   }
+  if constexpr (AUX) {
+    const T ra = t[P + G] - aux_loc;
+    v = fma((T(-0.5) * aux_ia2) * ra, ra, v);
+    if (lane == 0) gc[P + G] = fma(ra, aux_ia2, -dsum[0]);
+  }
   if (lane == 0) lp[c] = sanitize_lp ? sanitize(v) : v;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_hglm_finish(const T* __restrict__ partial, const T* __restrict__ R, const T* __restrict__ W, const T* __restrict__ prec,
+                                                     const T* __restrict__ th, const HglmTab<T>* __restrict__ tab, T* __restrict__ lp, T* __restrict__ g, int nrb,
+                                                     int P, int G, int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp) {
+  hglm_finish_body<T, false>(partial, R, W, prec, th, tab, lp, g, nrb, P, G, ncols, N, idx, sanitize_lp, (const T*)nullptr, T(0), T(0));
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_hglm_finish_aux(const T* __restrict__ partial, const T* __restrict__ partial_s, const T* __restrict__ R,
+                                                         const T* __restrict__ W, const T* __restrict__ prec, const T* __restrict__ th,
+                                                         const HglmTab<T>* __restrict__ tab, T* __restrict__ lp, T* __restrict__ g, int nrb, int P, int G,
+                                                         int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp, T aux_loc, T aux_ia2) {
+  hglm_finish_body<T, true>(partial, R, W, prec, th, tab, lp, g, nrb, P, G, ncols, N, idx, sanitize_lp, partial_s, aux_loc, aux_ia2);
 }
 
 }  // namespace ahmc

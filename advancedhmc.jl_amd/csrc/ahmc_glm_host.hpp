@@ -1,5 +1,6 @@
 // ahmc_glm_host.hpp — host side of the generalised-linear-model target (include/ahmc_glm.h; kernels: ahmc_glm.hpp) and of its
-// hierarchical form (include/ahmc_glm_hier.h: coefficient groups whose prior scale is sampled).  Included by ahmc_api.hip after the
+// hierarchical form (include/ahmc_glm_hier.h: coefficient groups whose prior scale is sampled) and of the families with a sampled
+// dispersion (include/ahmc_glm_aux.h).  Included by ahmc_api.hip after the
 // context, before ahmc_dense_host.hpp, whose dn_other_target routes to glm_target.
 #pragma once
 
@@ -9,7 +10,7 @@ bool listed_target(const Ctx<T>* c) {
   return c->target_kind == AHMC_TARGET_KERNEL || c->target_kind == AHMC_TARGET_GLM;
 }
 
-enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PARTS };
+enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PART_S, GLM_PARTS };
 
 // a hierarchical model's groups as ahmc_hglm_set_target received them (n_groups may be 0: the plain model)
 struct HglmSpec {
@@ -17,12 +18,29 @@ struct HglmSpec {
   int G;
   const int32_t *lo, *hi, *centered;
   const double* A;
+  bool aux = false;  // ahmc_glm_aux_set_target: θ ends with s, the log dispersion, with the prior Normal(aux_loc, aux_scale²)
+  double aux_loc = 0, aux_scale = 1;
 };
 
-// the columns of X: D, or P when groups are bound (θ then carries the G log-scales after the P coefficient parameters)
+inline bool glm_aux_family(int family) { return family == AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA || family == AHMC_GLM_NEGBINOMIAL_LOG; }
+
+// the model runs on the effective coefficients W: groups are bound, or θ carries the dispersion's row after the coefficients
+template <class T>
+bool glm_on_w(const Ctx<T>* c) {
+  return c->hglm_G > 0 || c->glm_aux;
+}
+
+// the entries of the group table that k_hglm_coef walks: with a dispersion row one more, an EMPTY group [P, P) whose "scale" is
+// exp(s) — the kernel then strides θ by P + G + 1 and runs unedited
+template <class T>
+int glm_tab_groups(const Ctx<T>* c) {
+  return c->hglm_G + (c->glm_aux ? 1 : 0);
+}
+
+// the columns of X: D, or P when groups or a dispersion are bound (θ then carries the G log-scales [and s] after the P coefficient parameters)
 template <class T>
 int64_t glm_ncoef(const Ctx<T>* c) {
-  return c->hglm_G > 0 ? c->hglm_P : c->D;
+  return glm_on_w(c) ? c->hglm_P : c->D;
 }
 
 template <class T>
@@ -41,6 +59,7 @@ int glm_release(Ctx<T>* c) {
   c->hglm_bound = false;
   c->hglm_P = 0;
   c->hglm_G = 0;
+  c->glm_aux = false;
   return AHMC_OK;
 }
 
@@ -55,9 +74,13 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
   const T* off = c->glm_has_offset ? b + c->glm_off[GLM_OFF] : nullptr;
   T* U = c->glm_buf + c->glm_off[GLM_U];
   T* part = c->glm_buf + c->glm_off[GLM_PART];
+  // a sampled dispersion: s is row D − 1 of the chain's own θ (th holds W); Σ ∂ℓ/∂s per row block
+  const T* aux = c->glm_aux ? c->th + (c->D - 1) : nullptr;
+  T* part_s = c->glm_aux ? c->glm_buf + c->glm_off[GLM_PART_S] : nullptr;
+  if (glm_aux_family(c->glm_family) != c->glm_aux) return fail(c, AHMC_ERR_STATE, "glm: the family and the dispersion row disagree in the context");
   const dim3 grid = small ? dim3((unsigned)nrb, (unsigned)((ncols + 15) / 16)) : dim3((unsigned)(nrb * (((ncols + GB_N - 1) / GB_N + 7) / 8 * 8)));
 #define AHMC_GLM_ETA(FAM, BN) \
-  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)c->glm_scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out)
+  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)c->glm_scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out, aux, (int64_t)c->D, part_s)
   switch (c->glm_family * 2 + (small ? 1 : 0)) {
     case 0: AHMC_GLM_ETA(0, 64); break;
     case 1: AHMC_GLM_ETA(0, 16); break;
@@ -65,6 +88,10 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
     case 3: AHMC_GLM_ETA(1, 16); break;
     case 4: AHMC_GLM_ETA(2, 64); break;
     case 5: AHMC_GLM_ETA(2, 16); break;
+    case 6: AHMC_GLM_ETA(3, 64); break;
+    case 7: AHMC_GLM_ETA(3, 16); break;
+    case 8: AHMC_GLM_ETA(4, 64); break;
+    case 9: AHMC_GLM_ETA(4, 16); break;
     default: return fail(c, AHMC_ERR_STATE, "glm: unknown family in the context");
   }
 #undef AHMC_GLM_ETA
@@ -91,7 +118,7 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   if (!c->glm_buf) return fail(c, AHMC_ERR_STATE, "AHMC_TARGET_GLM without a model (ahmc_set_target_glm)");
   // groups bound: the products run on the effective coefficients W (P, N) with a zero precision and leave R = −Xᵀu;
   // k_hglm_coef before them and k_hglm_finish after them are the model (ahmc_glm.hpp)
-  const bool hier = c->hglm_G > 0;
+  const bool hier = glm_on_w(c);
   const int n_obs = (int)c->glm_nobs, D = (int)glm_ncoef(c), G = c->hglm_G, ns = glm_slices(c);
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, nrbD = (int64_t)(D + GB_M - 1) / GB_M * ns;
   const T* b = c->glm_buf;
@@ -99,7 +126,7 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   const T* prec = b + c->glm_off[hier ? GLM_ZERO : GLM_PREC];
   T* g = hier ? c->glm_buf + c->glm_off[GLM_R] : c->g;
   const HglmTab<T>* tab = reinterpret_cast<const HglmTab<T>*>(b + c->glm_off[GLM_TAB]);
-  if (hier) hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, tab, c->glm_buf + c->glm_off[GLM_W], (T*)nullptr, D, G, n, list);
+  if (hier) hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, tab, c->glm_buf + c->glm_off[GLM_W], (T*)nullptr, D, glm_tab_groups(c), n, list);
   int rc = glm_launch_eta(c, th, D, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr);
   if (rc) return rc;
   const T* Xt = b + c->glm_off[GLM_XT];
@@ -113,7 +140,11 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
                        n_obs, D, n, c->N, list, ns);
   if (ns > 1)
     hipLaunchKernelGGL((k_glm_gsum<T>), dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, th, g, D, n, c->N, list, ns);
-  if (hier)
+  if (c->glm_aux)
+    hipLaunchKernelGGL((k_hglm_finish_aux<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], b + c->glm_off[GLM_PART_S],
+                       (const T*)g, th, b + c->glm_off[GLM_PREC], (const T*)c->th, tab, c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0,
+                       (T)c->glm_aux_loc, (T)(1.0 / (c->glm_aux_scale * c->glm_aux_scale)));
+  else if (hier)
     hipLaunchKernelGGL((k_hglm_finish<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], (const T*)g, th,
                        b + c->glm_off[GLM_PREC], (const T*)c->th, tab, c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0);
   else
@@ -126,8 +157,15 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
 template <class T>
 int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, const HglmSpec* hs = nullptr) {
   const int G = hs ? hs->G : 0;
+  const bool aux = hs && hs->aux, on_w = G > 0 || aux;
   const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the columns of X)
-  if (family != AHMC_GLM_BERNOULLI_LOGIT && family != AHMC_GLM_POISSON_LOG && family != AHMC_GLM_GAUSSIAN_IDENTITY)
+  if (glm_aux_family(family) && !aux)
+    return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family) +
+                                          " at this entry point: it samples its dispersion and is bound through ahmc_glm_aux_set_target (include/ahmc_glm_aux.h)");
+  if (aux && !glm_aux_family(family))
+    return fail(c, AHMC_ERR_ARGUMENT, "glm_aux_set_target: family " + std::to_string(family) +
+                                          " has no sampled dispersion (AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA, AHMC_GLM_NEGBINOMIAL_LOG)");
+  if (!aux && family != AHMC_GLM_BERNOULLI_LOGIT && family != AHMC_GLM_POISSON_LOG && family != AHMC_GLM_GAUSSIAN_IDENTITY)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family));
   if (n_obs < 1) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: n_obs must be >= 1; got " + std::to_string(n_obs));
   if (n_obs > AHMC_GLM_MAX_OBS)
@@ -135,16 +173,16 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
                                              std::to_string((long long)AHMC_GLM_MAX_OBS));
   if (!X || !y) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: X or y is NULL");
   if (!(std::isfinite(scale) && scale > 0)) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: scale must be finite and > 0; got " + std::to_string(scale));
-  // the slab: X, Xᵀ, y, offset, p [, a zero precision, the group table], then the workspaces U, partial, gs [, W, R]
+  // the slab: X, Xᵀ, y, offset, p [, a zero precision, the group table], then the workspaces U, partial [, partial_s], gs [, W, R]
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, ns = (n_obs + GLM_K_SLICE - 1) / GLM_K_SLICE;
   const int64_t tab_elems = (int64_t)((sizeof(HglmTab<T>) + sizeof(T) - 1) / sizeof(T));
-  int64_t sizes[GLM_PARTS] = {n_obs * D, n_obs * D, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * D * N : 0, 0, 0, 0, 0};
-  if (G > 0) {
+  int64_t sizes[GLM_PARTS] = {n_obs * D, n_obs * D, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * D * N : 0, 0, 0, 0, 0, aux ? nrb * N : 0};
+  if (on_w) {
     sizes[GLM_W] = sizes[GLM_R] = D * N;
     sizes[GLM_ZERO] = D;
     sizes[GLM_TAB] = tab_elems;
   }
-  const int layout[GLM_PARTS] = {GLM_X, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_ZERO, GLM_TAB, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R};
+  const int layout[GLM_PARTS] = {GLM_X, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_ZERO, GLM_TAB, GLM_U, GLM_PART, GLM_PART_S, GLM_GS, GLM_W, GLM_R};
   int64_t off[GLM_PARTS], total = 0;
   for (int i : layout) {
     off[i] = total;
@@ -162,17 +200,18 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   for (int64_t i = 0; i < n_obs; ++i) {
     const double yi = (double)h[off[GLM_Y] + i];
     if (!std::isfinite((double)h[off[GLM_OFF] + i])) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: offset holds a non-finite value");
-    const bool ok = family == AHMC_GLM_BERNOULLI_LOGIT ? (yi >= 0 && yi <= 1) : family == AHMC_GLM_POISSON_LOG ? (std::isfinite(yi) && yi >= 0) : std::isfinite(yi);
+    const bool counts = family == AHMC_GLM_POISSON_LOG || family == AHMC_GLM_NEGBINOMIAL_LOG;
+    const bool ok = family == AHMC_GLM_BERNOULLI_LOGIT ? (yi >= 0 && yi <= 1) : counts ? (std::isfinite(yi) && yi >= 0) : std::isfinite(yi);
     if (!ok)
       return fail(c, AHMC_ERR_ARGUMENT, "DomainError: y[" + std::to_string(i + 1) + "] = " + std::to_string(yi) + " is outside the family's domain (" +
-                                            (family == AHMC_GLM_BERNOULLI_LOGIT ? "0 <= y <= 1" : family == AHMC_GLM_POISSON_LOG ? "y >= 0, finite" : "finite") + ")");
+                                            (family == AHMC_GLM_BERNOULLI_LOGIT ? "0 <= y <= 1" : counts ? "y >= 0, finite" : "finite") + ")");
   }
   for (int64_t d = 0; d < D; ++d) {
     const double pd = (double)h[off[GLM_PREC] + d];
     if (!std::isfinite(pd)) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: prior_prec holds a non-finite value");
     if (pd < 0) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: prior_prec[" + std::to_string(d + 1) + "] = " + std::to_string(pd) + " is negative");
   }
-  if (G > 0) {
+  if (on_w) {
     HglmTab<T> tab{};
     for (int k = 0; k < G; ++k) {
       for (int64_t d = hs->lo[k]; d < hs->hi[k]; ++d)
@@ -182,6 +221,11 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
       tab.hi[k] = hs->hi[k];
       tab.centered[k] = hs->centered && hs->centered[k] ? 1 : 0;
       tab.inv_a2[k] = (T)(1.0 / (hs->A[k] * hs->A[k]));
+    }
+    if (aux) {  // the dispersion's row as an empty group: what k_hglm_coef needs to stride θ by P + G + 1 (glm_tab_groups)
+      tab.lo[G] = tab.hi[G] = (int)D;
+      tab.centered[G] = 1;
+      tab.inv_a2[G] = T(0);
     }
     memcpy(h.data() + off[GLM_TAB], &tab, sizeof(tab));
   }
@@ -194,7 +238,7 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
     (void)hipGetLastError();
     return fail(c, AHMC_ERR_RUNTIME, "set_target_glm: cannot allocate " + std::to_string((long long)(sizeof(T) * (size_t)total)) + " bytes for the model (" +
                                          std::to_string((long long)(sizeof(T) * (size_t)n_data)) + ") and its workspaces U (n_obs × N), partial and the slice sums" +
-                                         (G > 0 ? ", W and R (n_coef × N)" : ""));
+                                         (on_w ? ", W and R (n_coef × N)" : "") + (aux ? ", partial_s" : ""));
   }
   if (hipMemcpy(buf, h.data(), sizeof(T) * (size_t)n_data, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
     (void)hipFree(buf);
@@ -207,6 +251,9 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   c->hglm_bound = hs != nullptr;
   c->hglm_P = hs ? hs->P : 0;
   c->hglm_G = G;
+  c->glm_aux = aux;
+  c->glm_aux_loc = aux ? hs->aux_loc : 0;
+  c->glm_aux_scale = aux ? hs->aux_scale : 1;
   for (int k = 0; k < G; ++k) {
     c->hglm_lo[k] = hs->lo[k];
     c->hglm_hi[k] = hs->hi[k];
@@ -235,10 +282,10 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
   }
   const int64_t nrb = (c->glm_nobs + GB_M - 1) / GB_M;
   const T* th = c->th;
-  if (c->hglm_G > 0) {  // the effective coefficients first
+  if (glm_on_w(c)) {  // the effective coefficients first
     T* W = c->glm_buf + c->glm_off[GLM_W];
     hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th,
-                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, (T*)nullptr, (int)c->hglm_P, c->hglm_G, c->N, (const int*)nullptr);
+                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, (T*)nullptr, (int)c->hglm_P, glm_tab_groups(c), c->N, (const int*)nullptr);
     th = W;
   }
   int rc = glm_launch_eta(c, th, (int)glm_ncoef(c), (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_out ? tmp : (T*)nullptr, ll_out ? tmp + n : (T*)nullptr);
@@ -255,14 +302,20 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
 // ---- include/ahmc_glm_hier.h ----
 template <class T>
 int hglm_set(Ctx<T>* c, int family, int64_t n_obs, int64_t n_coef, const T* X, const T* y, const T* offset, const T* prec, double scale, int n_groups,
-             const int32_t* lo, const int32_t* hi, const int32_t* centered, const double* A) {
+             const int32_t* lo, const int32_t* hi, const int32_t* centered, const double* A, bool aux = false, double aux_loc = 0, double aux_scale = 1) {
   if (n_groups < 0) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: n_groups must be >= 0; got " + std::to_string(n_groups));
+  if (aux && n_groups > AHMC_GLM_AUX_MAX_GROUPS)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "glm_aux_set_target: n_groups = " + std::to_string(n_groups) + " is beyond the engine's limit AHMC_GLM_AUX_MAX_GROUPS = " +
+                                             std::to_string(AHMC_GLM_AUX_MAX_GROUPS));
   if (n_groups > AHMC_HGLM_MAX_GROUPS)
     return fail(c, AHMC_ERR_UNSUPPORTED, "hglm_set_target: n_groups = " + std::to_string(n_groups) + " is beyond the engine's limit AHMC_HGLM_MAX_GROUPS = " +
                                              std::to_string(AHMC_HGLM_MAX_GROUPS));
-  if (n_coef < 1 || c->D != n_coef + n_groups)
+  if (n_coef < 1 || c->D != n_coef + n_groups + (aux ? 1 : 0))
     return fail(c, AHMC_ERR_ARGUMENT, "DimensionMismatch: the context has D = " + std::to_string((long long)c->D) + ", the model n_coef + n_groups = " +
-                                          std::to_string((long long)n_coef) + " + " + std::to_string(n_groups));
+                                          std::to_string((long long)n_coef) + " + " + std::to_string(n_groups) + (aux ? " (+ 1: the dispersion's row)" : ""));
+  if (aux && !std::isfinite(aux_loc)) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_loc = " + std::to_string(aux_loc) + " must be finite");
+  if (aux && !(std::isfinite(aux_scale) && aux_scale > 0))
+    return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_scale = " + std::to_string(aux_scale) + " must be finite and > 0");
   if (n_groups > 0 && (!lo || !hi || !A)) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: lo, hi or hyper_scale is NULL");
   int64_t prev = 0;
   for (int k = 0; k < n_groups; ++k) {
@@ -274,7 +327,7 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, int64_t n_coef, const T* X, c
       return fail(c, AHMC_ERR_ARGUMENT, "DomainError: hyper_scale[" + std::to_string(k + 1) + "] = " + std::to_string(A[k]) + " must be finite and > 0");
     prev = hi[k];
   }
-  const HglmSpec hs{n_coef, n_groups, lo, hi, centered, A};
+  const HglmSpec hs{n_coef, n_groups, lo, hi, centered, A, aux, aux_loc, aux_scale};
   return glm_set(c, family, n_obs, X, y, offset, prec, scale, &hs);
 }
 
@@ -286,14 +339,14 @@ int hglm_coefficients(Ctx<T>* c, const void* theta, int64_t n_cols, void* beta_o
   if (n_cols < 0 || (n_cols > 0 && !theta)) return fail(c, AHMC_ERR_ARGUMENT, "hglm_coefficients: theta is NULL or n_cols < 0");
   if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, "hglm_coefficients: n_cols beyond 2^31 - 1");
   if (n_cols == 0 || (!beta_out && !tau_out)) return AHMC_OK;
-  const int64_t P = glm_ncoef(c), G = c->hglm_G, D = P + G;
-  if (G == 0) {  // the plain model: β = θ
+  const int64_t P = glm_ncoef(c), G = c->hglm_G, GT = glm_tab_groups(c), D = P + GT;  // (GT: with the dispersion's row, an empty group)
+  if (GT == 0) {  // the plain model: β = θ
     if (beta_out) HIPCHK(hipMemcpyAsync(beta_out, theta, sizeof(T) * (size_t)(P * n_cols), hipMemcpyDefault, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return AHMC_OK;
   }
   T* tmp = nullptr;
-  const size_t total = (size_t)((D + P + G) * n_cols);
+  const size_t total = (size_t)((D + P + GT + G) * n_cols);
   if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * total) != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, AHMC_ERR_RUNTIME, "hglm_coefficients: cannot allocate " + std::to_string((long long)(sizeof(T) * total)) + " bytes");
@@ -302,13 +355,57 @@ int hglm_coefficients(Ctx<T>* c, const void* theta, int64_t n_cols, void* beta_o
   hipError_t e = hipMemcpyAsync(th, theta, sizeof(T) * (size_t)(D * n_cols), hipMemcpyDefault, c->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, c->stream, (const T*)th,
-                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, tau, (int)P, (int)G, n_cols, (const int*)nullptr);
+                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, tau, (int)P, (int)GT, n_cols, (const int*)nullptr);
     e = hipGetLastError();
   }
   if (e == hipSuccess && beta_out) e = hipMemcpyAsync(beta_out, W, sizeof(T) * (size_t)(P * n_cols), hipMemcpyDefault, c->stream);
-  if (e == hipSuccess && tau_out) e = hipMemcpyAsync(tau_out, tau, sizeof(T) * (size_t)(G * n_cols), hipMemcpyDefault, c->stream);
+  if (e == hipSuccess && tau_out && G > 0) {
+    const T* src = tau;
+    if (GT != G) {  // (rows 0 .. G − 1 of each column's GT: the last is the dispersion)
+      T* packed = tau + GT * n_cols;
+      hipLaunchKernelGGL((k_glm_rows<T>), dim3((unsigned)((G * n_cols + 255) / 256)), dim3(256), 0, c->stream, (const T*)tau, (int)GT, 0, (int)G, n_cols, packed);
+      e = hipGetLastError();
+      src = packed;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(tau_out, src, sizeof(T) * (size_t)(G * n_cols), hipMemcpyDefault, c->stream);
+  }
   const hipError_t es = hipStreamSynchronize(c->stream);
   (void)hipFree(tmp);
   if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("hglm_coefficients: ") + hipGetErrorString(e != hipSuccess ? e : es));
+  return AHMC_OK;
+}
+
+// ---- include/ahmc_glm_aux.h ----
+// exp(s) of any (D, n_cols) array of draws, host or device pointers: k_hglm_coef's τ of the table's last (empty) group
+template <class T>
+int glm_dispersion(Ctx<T>* c, const void* theta, int64_t n_cols, void* out) {
+  if (c->target_kind != AHMC_TARGET_GLM || !c->glm_buf || !c->glm_aux)
+    return fail(c, AHMC_ERR_ARGUMENT, "glm_dispersion: no model with a sampled dispersion is bound (ahmc_glm_aux_set_target)");
+  if (n_cols < 0 || (n_cols > 0 && (!theta || !out))) return fail(c, AHMC_ERR_ARGUMENT, "glm_dispersion: theta or out is NULL, or n_cols < 0");
+  if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, "glm_dispersion: n_cols beyond 2^31 - 1");
+  if (n_cols == 0) return AHMC_OK;
+  const int64_t P = glm_ncoef(c), GT = glm_tab_groups(c), D = P + GT;
+  T* tmp = nullptr;
+  const size_t total = (size_t)((D + GT + 1) * n_cols);
+  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * total) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, AHMC_ERR_RUNTIME, "glm_dispersion: cannot allocate " + std::to_string((long long)(sizeof(T) * total)) + " bytes");
+  }
+  T *th = tmp, *tau = tmp + D * n_cols;
+  hipError_t e = hipMemcpyAsync(th, theta, sizeof(T) * (size_t)(D * n_cols), hipMemcpyDefault, c->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, c->stream, (const T*)th,
+                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), (T*)nullptr, tau, (int)P, (int)GT, n_cols, (const int*)nullptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    T* packed = tau + GT * n_cols;
+    hipLaunchKernelGGL((k_glm_rows<T>), dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, c->stream, (const T*)tau, (int)GT, (int)(GT - 1), 1, n_cols, packed);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, packed, sizeof(T) * (size_t)n_cols, hipMemcpyDefault, c->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  (void)hipFree(tmp);
+  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("glm_dispersion: ") + hipGetErrorString(e != hipSuccess ? e : es));
   return AHMC_OK;
 }

@@ -22,7 +22,10 @@ The functions below follow the block and slice structure; numpy's own dot produc
 import numpy as np
 
 BERNOULLI_LOGIT, POISSON_LOG, GAUSSIAN_IDENTITY = 0, 1, 2
-FAMILIES = {"bernoulli_logit": BERNOULLI_LOGIT, "poisson_log": POISSON_LOG, "gaussian_identity": GAUSSIAN_IDENTITY}
+GAUSSIAN_IDENTITY_SIGMA, NEGBINOMIAL_LOG = 3, 4   # include/ahmc_glm_aux.h: a sampled dispersion (the section at the end)
+FAMILIES = {"bernoulli_logit": BERNOULLI_LOGIT, "poisson_log": POISSON_LOG, "gaussian_identity": GAUSSIAN_IDENTITY,
+            "gaussian_identity_sigma": GAUSSIAN_IDENTITY_SIGMA, "negbinomial_log": NEGBINOMIAL_LOG}
+AUX_FAMILIES = (GAUSSIAN_IDENTITY_SIGMA, NEGBINOMIAL_LOG)
 ROW_BLOCK = 64    # observations whose ℓ one workgroup sums (GB_M of csrc/ahmc_dense.hpp)
 K_SLICE = 1024    # observations per slice of Xᵀu (GLM_K_SLICE of csrc/ahmc_glm.hpp)
 
@@ -37,11 +40,16 @@ def family_code(family):
     return int(family)
 
 
-def link(family, y, eta, scale=1.0):
-    """(ℓ(y, η), u = ∂ℓ/∂η) elementwise; y broadcasts against η"""
+def link(family, y, eta, scale=1.0, s=None):
+    """(ℓ(y, η), u = ∂ℓ/∂η) elementwise; y broadcasts against η.  The families with a sampled dispersion take its log `s`
+    (broadcast against η: one value per chain) and return a third value, ∂ℓ/∂s."""
     fam = family_code(family)
     eta = np.asarray(eta, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
+    if fam in AUX_FAMILIES:
+        if s is None:
+            raise ValueError(f"ArgumentError: family {fam} needs s, the log of its dispersion")
+        return _aux_link(fam, y, eta, np.asarray(s, dtype=np.float64))
     with np.errstate(over="ignore", invalid="ignore"):
         if fam == BERNOULLI_LOGIT:
             e = np.exp(-np.abs(eta))
@@ -77,7 +85,10 @@ def linear_predictor(X, theta, offset=None):
 
 
 def pointwise(family, X, y, theta, offset=None, scale=1.0):
-    """(η, ℓ(y_i, η_i)), each (n_obs, N): the mirror of ahmc_glm_pointwise"""
+    """(η, ℓ(y_i, η_i)), each (n_obs, N): the mirror of ahmc_glm_pointwise.  A family with a sampled dispersion takes it from θ's
+    last row (θ then has one row more than X has columns)."""
+    if family_code(family) in AUX_FAMILIES:
+        return hier_pointwise(family, X, y, theta, (), offset, scale)
     eta = linear_predictor(X, theta, offset)
     ll, _ = link(family, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, scale)
     return eta, ll
@@ -98,9 +109,12 @@ def sanitize(lp):
     return np.where(np.isfinite(lp), lp, -np.inf)
 
 
-def logdensity(family, X, y, theta, offset=None, prior_prec=None, scale=1.0):
+def logdensity(family, X, y, theta, offset=None, prior_prec=None, scale=1.0, aux_prior=None):
     """(ℓπ (N,), ∇ℓπ (D, N)) at θ (D, N) — with the model bound (functools.partial, a lambda) the callback of an ExternalTarget.
-    ℓπ is returned as computed: an overflowing Poisson gives a non-finite value, which the engine sanitises (`sanitize`)."""
+    ℓπ is returned as computed: an overflowing Poisson gives a non-finite value, which the engine sanitises (`sanitize`).
+    `aux_prior` = (loc, scale) belongs to the families with a sampled dispersion (θ then has D + 1 rows)."""
+    if family_code(family) in AUX_FAMILIES or aux_prior is not None:
+        return aux_logdensity(family, X, y, theta, (), offset, prior_prec, aux_prior)
     X, th, _ = _theta(X, theta)
     p = np.zeros(X.shape[1]) if prior_prec is None else np.asarray(prior_prec, dtype=np.float64).ravel()
     eta = linear_predictor(X, th, offset)
@@ -187,15 +201,25 @@ def hier_coefficients(theta, P, groups):
 
 
 def hier_pointwise(family, X, y, theta, groups, offset=None, scale=1.0):
-    """(η, ℓ(y_i, η_i)), each (n_obs, N): `pointwise` at the effective coefficients W"""
+    """(η, ℓ(y_i, η_i)), each (n_obs, N): `pointwise` at the effective coefficients W; the dispersion of a family that samples it
+    comes from θ's last row"""
     X = np.asarray(X, dtype=np.float64)
+    if family_code(family) in AUX_FAMILIES:
+        th = np.asarray(theta, dtype=np.float64)
+        th = th.reshape(-1, 1) if th.ndim == 1 else th
+        W, _ = hier_coefficients(th[:-1], X.shape[1], groups)
+        eta = linear_predictor(X, W, offset)
+        return eta, link(family, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, s=th[-1:])[0]
     W, _ = hier_coefficients(theta, X.shape[1], groups)
     return pointwise(family, X, y, W, offset, scale)
 
 
-def hier_logdensity(family, X, y, theta, groups, offset=None, prior_prec=None, scale=1.0):
+def hier_logdensity(family, X, y, theta, groups, offset=None, prior_prec=None, scale=1.0, aux_prior=None):
     """(ℓπ (N,), ∇ℓπ (P + G, N)) at θ (P + G, N).  `prior_prec` (P) covers the coefficients in no group and must be 0 on members.
-    ℓπ is returned as computed (`sanitize` makes a non-finite value −Inf, as the engine does)."""
+    ℓπ is returned as computed (`sanitize` makes a non-finite value −Inf, as the engine does).  A family with a sampled dispersion
+    has one more row, s, with the prior `aux_prior` = (loc, scale): `aux_logdensity`."""
+    if family_code(family) in AUX_FAMILIES or aux_prior is not None:
+        return aux_logdensity(family, X, y, theta, groups, offset, prior_prec, aux_prior)
     X = np.asarray(X, dtype=np.float64)
     P = X.shape[1]
     th, groups = _hier_theta(theta, P, groups)
@@ -213,7 +237,14 @@ def hier_logdensity(family, X, y, theta, groups, offset=None, prior_prec=None, s
         xtu = np.zeros_like(W)
         for k0 in range(0, X.shape[0], K_SLICE):
             xtu = xtu + X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
-        R = -xtu
+        lp, g = _hier_finish(th, W, tau, -xtu, lsum, p, groups)
+    return lp, -g
+
+
+def _hier_finish(th, W, tau, R, lsum, p, groups):
+    """(ℓπ, g = −∇ℓπ) over the P + G rows of th from Σℓ and R = −Xᵀu: the arithmetic of k_hglm_finish"""
+    P = W.shape[0]
+    with np.errstate(over="ignore", invalid="ignore"):
         b = th[:P]
         pt = p.reshape(-1, 1) * b
         lp = lsum - 0.5 * (pt * b).sum(axis=0)
@@ -236,4 +267,156 @@ def hier_logdensity(family, X, y, theta, groups, offset=None, prior_prec=None, s
                 g[lo:hi] = tau[k] * R[lo:hi] + b[lo:hi]
                 g[P + k] = (R[lo:hi] * W[lo:hi]).sum(axis=0) - hp
             lp = lp + (h + bk)
+    return lp, g
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# include/ahmc_glm_aux.h: families whose dispersion is sampled (csrc/ahmc_glm.hpp: glm_link_aux, glm_gamma_diffs, k_hglm_finish<T, true>)
+# ------------------------------------------------------------------------------------------------------------------------------
+__doc__ += """
+Families with a sampled dispersion (aux_logdensity; `link` with s; lgamma_diff, digamma_diff):
+    θ (D, N), D = P + G + 1:  the P coefficient parameters, the G log group scales (G may be 0), and LAST s, the log of the family's
+    dispersion parameter, with the prior s ~ Normal(m, A²) (a log-normal on σ or φ: no Jacobian term).
+    "gaussian_identity_sigma"  σ = e^s:  r = y − η, q = exp(−2s), u = q·r, ℓ = fma(−½·u, r, −s), ∂ℓ/∂s = fma(u, r, −1)
+    "negbinomial_log"          NB2, mean μ = e^η, variance μ + μ²/φ, φ = e^s, y >= 0 finite (not necessarily an integer):
+        d = η − s, e = exp(−|d|), l = log1p(e), σ(d) and 1 − σ(d) both from the same e (1/(1+e), e/(1+e): no subtraction)
+        sp = max(d, 0) + l = log(μ + φ) − s,   sn = max(−d, 0) + l = log(μ + φ) − η
+        ℓ = fma(−y, sn, fma(−φ, sp, L)),  u = fma(−(y + φ), σ, y),  ∂ℓ/∂s = fma(φ, Ψ − sp, fma(−(y + φ), 1 − σ, φ))
+        L = lgamma(y + φ) − lgamma(φ) (`lgamma_diff`),  Ψ = ψ(y + φ) − ψ(φ) (`digamma_diff`);  −lgamma(y + 1) is dropped.
+    ℓπ = [the hierarchical ℓπ over the first P + G rows] − ½((s − m)/A)²,   g[D−1] = −Σ_i ∂ℓ/∂s + (s − m)/A²
+L and Ψ are computed as differences (shift both arguments by 8 with the recurrence, then Stirling's series): with A = φ + 8,
+B = A + y, z = y/A:
+    L = fma(A − ½, log1p(z), y·(log B − 1)) + (S(B) − S(A)) − Σ_{j<8} log1p(y/(φ + j))
+    Ψ = Σ_{j<8} (y/(φ + j))/(y + φ + j) + log1p(z) + (½·z)/B − (T(B) − T(A))
+S(x) = Σ_k B_2k/(2k(2k−1)) x^{1−2k} and T(x) = Σ_k B_2k/(2k) x^{−2k}, eight terms each, by Horner's rule in 1/x² (fma); the sums over
+j ascending.  y = 0 gives L = Ψ = 0 exactly for every finite φ > 0.  A φ that underflows to 0 makes y/φ infinite or NaN and one that
+overflows makes (A − ½)·log1p(0) = ∞·0: either way ℓ is non-finite and ℓπ is sanitised to −Inf (a divergence).
+Order of the new sums: Σ_i ∂ℓ/∂s exactly as Σ_i ℓ (`block_sums`, then lane-strided over the row blocks and the butterfly); the prior
+of s is added to ℓπ after the groups' terms:  r = s − m, ℓπ = fma((−½/A²)·r, r, ℓπ), g[D−1] = fma(r, 1/A², −Σ ∂ℓ/∂s).
+"""
+
+_STIRLING_S = (1.0 / 12, -1.0 / 360, 1.0 / 1260, -1.0 / 1680, 1.0 / 1188, -691.0 / 360360, 1.0 / 156, -3617.0 / 122400)
+_STIRLING_T = (1.0 / 12, -1.0 / 120, 1.0 / 252, -1.0 / 240, 1.0 / 132, -691.0 / 32760, 1.0 / 12, -3617.0 / 8160)
+GAMMA_SHIFT = 8
+
+
+def _horner(c, z2):
+    acc = np.full_like(z2, c[-1])
+    for ck in c[-2::-1]:
+        acc = acc * z2 + z2.dtype.type(ck)
+    return acc
+
+
+def gamma_diffs(y, phi, dtype=np.float64):
+    """(L, Ψ) = (lgamma(y + φ) − lgamma(φ), ψ(y + φ) − ψ(φ)) elementwise, y >= 0 and φ > 0 broadcast against each other; every
+    operation in `dtype` (float64 defines the model; float32 is what a Float32 context's kernels are compared with)"""
+    dt = np.dtype(dtype).type
+    y, phi = np.broadcast_arrays(np.asarray(y, dtype=dt), np.asarray(phi, dtype=dt))
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        A = phi + dt(GAMMA_SHIFT)
+        B = A + y
+        z = y / A
+        lz = np.log1p(z)
+        za, zb = dt(1) / A, dt(1) / B
+        za2, zb2 = za * za, zb * zb
+        dS = zb * _horner(_STIRLING_S, zb2) - za * _horner(_STIRLING_S, za2)
+        dT = zb2 * _horner(_STIRLING_T, zb2) - za2 * _horner(_STIRLING_T, za2)
+        sl = np.zeros_like(z)
+        sp = np.zeros_like(z)
+        pj = phi.copy()
+        for j in range(GAMMA_SHIFT):
+            t = y / pj
+            sl = sl + np.log1p(t)
+            sp = sp + t / (y + pj)
+            pj = pj + dt(1)
+        L = ((A - dt(0.5)) * lz + y * (np.log(B) - dt(1))) + dS - sl
+        Psi = ((sp + lz) + (dt(0.5) * z) / B) - dT
+    return L, Psi
+
+
+def lgamma_diff(y, phi):
+    """lgamma(y + φ) − lgamma(φ), computed as a difference: accurate when φ is large and exact 0 at y = 0"""
+    return gamma_diffs(y, phi)[0]
+
+
+def digamma_diff(y, phi):
+    """ψ(y + φ) − ψ(φ), computed as a difference"""
+    return gamma_diffs(y, phi)[1]
+
+
+def _aux_link(fam, y, eta, s):
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        if fam == GAUSSIAN_IDENTITY_SIGMA:
+            r = y - eta
+            u = np.exp(-2.0 * s) * r
+            return (-0.5 * u) * r - s, u, u * r - 1.0
+        phi = np.exp(s)
+        d = eta - s
+        e = np.exp(-np.abs(d))
+        l = np.log1p(e)
+        dd = 1.0 + e
+        sig = np.where(d >= 0, 1.0 / dd, e / dd)
+        nsig = np.where(d >= 0, e / dd, 1.0 / dd)
+        sp = np.where(d > 0, d, 0.0) + l
+        sn = np.where(d < 0, -d, 0.0) + l
+        yp = y + phi
+        L, Psi = gamma_diffs(y, phi)
+        ll = -y * sn + (-phi * sp + L)
+        u = -yp * sig + y
+        ds = phi * (Psi - sp) + (-yp * nsig + phi)
+        return ll, u, ds
+
+
+def check_aux_prior(aux_prior):
+    """(loc, scale) of the prior on s; scale finite and > 0.  None: the default (0, 1)"""
+    loc, scale = (0.0, 1.0) if aux_prior is None else aux_prior
+    loc, scale = float(loc), float(scale)
+    if not np.isfinite(loc):
+        raise ValueError(f"DomainError: aux_prior location {loc} must be finite")
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"DomainError: aux_prior scale {scale} must be finite and > 0")
+    return loc, scale
+
+
+def dispersion(theta):
+    """exp of the last row of draws θ (D, n): σ or φ — the mirror of ahmc_glm_dispersion"""
+    th = np.asarray(theta, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        return np.exp(th[-1])
+
+
+def aux_logdensity(family, X, y, theta, groups=(), offset=None, prior_prec=None, aux_prior=None):
+    """(ℓπ (N,), ∇ℓπ (D, N)) at θ (D, N), D = P + G + 1, of a family with a sampled dispersion"""
+    fam = family_code(family)
+    if fam not in AUX_FAMILIES:
+        raise ValueError(f"ArgumentError: family {fam} has no sampled dispersion (aux_prior belongs to {sorted(f for f in FAMILIES if FAMILIES[f] in AUX_FAMILIES)})")
+    m, A = check_aux_prior(aux_prior)
+    X = np.asarray(X, dtype=np.float64)
+    P = X.shape[1]
+    th = np.asarray(theta, dtype=np.float64)
+    if th.ndim == 1:
+        th = th.reshape(-1, 1)
+    groups = check_groups(groups, P)
+    if th.shape[0] != P + len(groups) + 1:
+        raise ValueError(f"DimensionMismatch: θ {th.shape}, P + G + 1 = {P} + {len(groups)} + 1")
+    p = np.zeros(P) if prior_prec is None else np.asarray(prior_prec, dtype=np.float64).ravel()
+    for lo, hi, _, _ in groups:
+        if np.any(p[lo:hi] != 0):
+            raise ValueError(f"ArgumentError: prior_prec must be 0 on the members of a group ([{lo}, {hi}))")
+    s = th[-1]
+    W, tau = hier_coefficients(th[:-1], P, groups)
+    eta = linear_predictor(X, W, offset)
+    ll, u, ds = link(fam, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, s=s.reshape(1, -1))
+    with np.errstate(over="ignore", invalid="ignore"):
+        lsum = block_sums(ll).sum(axis=0)
+        dsum = block_sums(ds).sum(axis=0)
+        xtu = np.zeros_like(W)
+        for k0 in range(0, X.shape[0], K_SLICE):
+            xtu = xtu + X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
+        g = np.empty_like(th)
+        lp, g[:-1] = _hier_finish(th[:-1], W, tau, -xtu, lsum, p, groups)
+        ia2 = 1.0 / (A * A)
+        r = s - m
+        lp = lp + ((-0.5 * ia2) * r) * r
+        g[-1] = r * ia2 - dsum
     return lp, -g

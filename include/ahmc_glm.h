@@ -37,6 +37,8 @@ extern "C" {
 #define AHMC_GLM_MAX_OBS 16777216 /* an engine limit: a larger n_obs is AHMC_ERR_UNSUPPORTED */
 
 enum { AHMC_GLM_BERNOULLI_LOGIT = 0, AHMC_GLM_POISSON_LOG = 1, AHMC_GLM_GAUSSIAN_IDENTITY = 2 };
+/* families whose dispersion is sampled: bound through ahmc_glm_aux_set_target (ahmc_glm_aux.h) only */
+enum { AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA = 3, AHMC_GLM_NEGBINOMIAL_LOG = 4 };
 
 int32_t ahmc_glm_version(void);
 

@@ -517,5 +517,6 @@ include("AdvancedHMCMI355XRankUpdate.jl")  # set_metric!(z, ::RankUpdateEuclidea
 include("AdvancedHMCMI355XLowRankAdapt.jl")  # lowrank_adaptor_init!: include/ahmc_lowrank_adapt.h
 include("AdvancedHMCMI355XGLM.jl")  # set_target!(z, ::GLMTarget), glm_pointwise: include/ahmc_glm.h
 include("AdvancedHMCMI355XGLMHier.jl")  # set_target!(z, ::HierGLMTarget), hglm_coefficients: include/ahmc_glm_hier.h
+include("AdvancedHMCMI355XGLMAux.jl")  # set_target!(z, ::AuxGLMTarget), glm_dispersion: include/ahmc_glm_aux.h
 
 end # module
