@@ -313,6 +313,7 @@ class GLMTarget:
     density as `ExternalTarget(D, lambda th: glm.logdensity(...))` or a host KernelTarget)."""
     kind = capi.TARGET_GLM
     params = None
+    groups = ()
 
     def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None):
         X = np.asarray(X, dtype=np.float64)
@@ -349,7 +350,7 @@ class GLMTarget:
 
     def logdensity(self, theta):
         """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
-        return _glm.logdensity(self.family, self.X, self.y, theta, self.offset, self.prior_prec, self.scale, self.aux_prior)
+        return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale, self.aux_prior)
 
     def dispersion(self, theta):
         """σ or φ = exp(s) of draws θ (D, n) by the numpy mirror (a family with a sampled dispersion)"""
@@ -380,7 +381,6 @@ class HierGLMTarget(GLMTarget):
 
     def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None):
         super().__init__(X, y, family=family, prior_scale=prior_scale, prior_prec=prior_prec, offset=offset, scale=scale, aux_prior=aux_prior)
-        self.P = self.X.shape[1]
         groups = [g if isinstance(g, CoefGroup) else CoefGroup(*g) for g in groups]
         try:
             _glm.check_groups(groups, self.P)
@@ -392,10 +392,6 @@ class HierGLMTarget(GLMTarget):
             self.prior_prec = self.prior_prec.copy()
             for g in self.groups:
                 self.prior_prec[g.start:g.stop] = 0.0
-
-    def logdensity(self, theta):
-        """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
-        return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale, self.aux_prior)
 
     def coefficients(self, theta):
         """(β (P, n), τ (G, n)) of draws θ (D, n) by the numpy mirror"""
@@ -738,12 +734,6 @@ class Engine:
                                                  n_params=-1 if p is None else p.size)
             self._call("ahmc_set_target_plugin", so.encode(), capi.as_ptr(p), 0 if p is None else p.size)
             return
-        if isinstance(target, GLMTarget) and target.aux:
-            self._set_glm_aux(target)
-            return
-        if isinstance(target, HierGLMTarget):
-            self._set_hglm(target)
-            return
         if isinstance(target, GLMTarget):
             self._set_glm(target)
             return
@@ -756,77 +746,56 @@ class Engine:
             return
         self._call("ahmc_set_target", target.kind, capi.as_ptr(p), 0 if p is None else p.size)
 
-    def _need_glm(self, what):
-        if not getattr(self.lib, "has_glm", False):
-            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_glm.h")
+    def _need(self, flag, header, what):
+        if not getattr(self.lib, flag, False):
+            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/{header}")
 
     def _set_glm(self, t):
-        self._need_glm("GLMTarget")
+        """bind a GLMTarget through the entry point of its kind: a sampled dispersion first, then coefficient groups, then the plain model"""
+        hier, G = isinstance(t, HierGLMTarget), len(t.groups)
+        if t.aux:
+            self._need("has_glm_aux", "ahmc_glm_aux.h", f"GLMTarget(family={t.family})")
+            model = f"the model has P + G + 1 = {t.P} + {G} + 1 parameters"
+        elif hier:
+            self._need("has_hglm", "ahmc_glm_hier.h", "HierGLMTarget")
+            model = f"the model has P + G = {t.P} + {G} parameters"
+        else:
+            self._need("has_glm", "ahmc_glm.h", "GLMTarget")
+            model = f"X has {t.D} columns"
         if t.D != self.D:
-            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: X has {t.D} columns, the context has D = {self.D}")
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: {model}, the context has D = {self.D}")
         X = np.asfortranarray(t.X, dtype=self.dtype)
         y = np.ascontiguousarray(t.y, dtype=self.dtype)
         off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
         p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
-        self._call("ahmc_set_target_glm", int(t.family), int(t.n_obs), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p), float(t.scale))
+        data = (capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p))
+        table = (G, (C.c_int32 * max(G, 1))(*[g.start for g in t.groups]), (C.c_int32 * max(G, 1))(*[g.stop for g in t.groups]),
+                 (C.c_int32 * max(G, 1))(*[int(g.centered) for g in t.groups]), (C.c_double * max(G, 1))(*[g.scale for g in t.groups]))
+        if t.aux:
+            self._call("ahmc_glm_aux_set_target", int(t.family), int(t.n_obs), int(t.P), *data, *table, float(t.aux_prior[0]), float(t.aux_prior[1]))
+        elif hier:
+            self._call("ahmc_hglm_set_target", int(t.family), int(t.n_obs), int(t.P), *data, float(t.scale), *table)
+        else:
+            self._call("ahmc_set_target_glm", int(t.family), int(t.n_obs), *data, float(t.scale))
 
-    def _need_hglm(self, what):
-        if not getattr(self.lib, "has_hglm", False):
-            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_glm_hier.h")
-
-    def _set_hglm(self, t):
-        self._need_hglm("HierGLMTarget")
-        if t.D != self.D:
-            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: the model has P + G = {t.P} + {len(t.groups)} parameters, the context has D = {self.D}")
-        X = np.asfortranarray(t.X, dtype=self.dtype)
-        y = np.ascontiguousarray(t.y, dtype=self.dtype)
-        off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
-        p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
-        G = len(t.groups)
-        lo = (C.c_int32 * max(G, 1))(*[g.start for g in t.groups])
-        hi = (C.c_int32 * max(G, 1))(*[g.stop for g in t.groups])
-        cen = (C.c_int32 * max(G, 1))(*[int(g.centered) for g in t.groups])
-        A = (C.c_double * max(G, 1))(*[g.scale for g in t.groups])
-        self._call("ahmc_hglm_set_target", int(t.family), int(t.n_obs), int(t.P), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p),
-                   float(t.scale), G, lo, hi, cen, A)
-
-    def _need_glm_aux(self, what):
-        if not getattr(self.lib, "has_glm_aux", False):
-            raise capi.UnsupportedError(capi.ERR_UNSUPPORTED, f"{what}: {self.lib.path} does not implement include/ahmc_glm_aux.h")
-
-    def _set_glm_aux(self, t):
-        self._need_glm_aux(f"GLMTarget(family={t.family})")
-        groups = getattr(t, "groups", ())
-        if t.D != self.D:
-            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: the model has P + G + 1 = {t.P} + {len(groups)} + 1 parameters, the context has D = {self.D}")
-        X = np.asfortranarray(t.X, dtype=self.dtype)
-        y = np.ascontiguousarray(t.y, dtype=self.dtype)
-        off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
-        p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
-        G = len(groups)
-        lo = (C.c_int32 * max(G, 1))(*[g.start for g in groups])
-        hi = (C.c_int32 * max(G, 1))(*[g.stop for g in groups])
-        cen = (C.c_int32 * max(G, 1))(*[int(g.centered) for g in groups])
-        A = (C.c_double * max(G, 1))(*[g.scale for g in groups])
-        self._call("ahmc_glm_aux_set_target", int(t.family), int(t.n_obs), int(t.P), capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p),
-                   G, lo, hi, cen, A, float(t.aux_prior[0]), float(t.aux_prior[1]))
+    def _draws(self, who, theta, n_cols):
+        """(pointer, n) of draws θ (D, n): an array (default: the context's current θ), or a device pointer (an int) together with `n_cols`"""
+        if isinstance(theta, (int, C.c_void_p)):
+            if n_cols is None:
+                raise ArgumentError(capi.ERR_ARGUMENT, f"{who}: a pointer needs n_cols")
+            return (C.c_void_p(theta) if isinstance(theta, int) else theta), int(n_cols)
+        th = np.asarray(self.theta() if theta is None else theta)
+        if th.ndim == 1:
+            th = th.reshape(-1, 1)
+        if th.ndim != 2 or th.shape[0] != self.D or (n_cols is not None and n_cols != th.shape[1]):
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({self.D}, {n_cols if n_cols is not None else 'n'})")
+        return capi.as_ptr(np.asfortranarray(th, dtype=self.dtype)), th.shape[1]   # (the pointer owns the array)
 
     def glm_dispersion(self, theta=None, n_cols=None):
         """σ or φ = exp(s) (n_cols,) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer (an
         int) together with `n_cols`: ahmc_glm_dispersion"""
-        self._need_glm_aux("glm_dispersion")
-        if isinstance(theta, (int, C.c_void_p)):
-            if n_cols is None:
-                raise ArgumentError(capi.ERR_ARGUMENT, "glm_dispersion: a pointer needs n_cols")
-            ptr, n = (C.c_void_p(theta) if isinstance(theta, int) else theta), int(n_cols)
-        else:
-            th = np.asarray(self.theta() if theta is None else theta)
-            if th.ndim == 1:
-                th = th.reshape(-1, 1)
-            if th.ndim != 2 or th.shape[0] != self.D or (n_cols is not None and n_cols != th.shape[1]):
-                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({self.D}, {n_cols if n_cols is not None else 'n'})")
-            th = np.asfortranarray(th, dtype=self.dtype)
-            ptr, n = capi.as_ptr(th), th.shape[1]
+        self._need("has_glm_aux", "ahmc_glm_aux.h", "glm_dispersion")
+        ptr, n = self._draws("glm_dispersion", theta, n_cols)
         out = np.empty(n, dtype=self.dtype)
         self._call("ahmc_glm_dispersion", ptr, n, capi.as_ptr(out) if n else None)
         return out
@@ -834,21 +803,10 @@ class Engine:
     def hglm_coefficients(self, theta=None, n_cols=None):
         """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer
         (an int) together with `n_cols`: ahmc_hglm_coefficients"""
-        self._need_hglm("hglm_coefficients")
+        self._need("has_hglm", "ahmc_glm_hier.h", "hglm_coefficients")
         P, G = C.c_int64(), C.c_int32()
         self._call("ahmc_hglm_get_target", C.byref(P), C.byref(G), None, None, None, None)
-        if isinstance(theta, (int, C.c_void_p)):
-            if n_cols is None:
-                raise ArgumentError(capi.ERR_ARGUMENT, "hglm_coefficients: a pointer needs n_cols")
-            ptr, n = (C.c_void_p(theta) if isinstance(theta, int) else theta), int(n_cols)
-        else:
-            th = np.asarray(self.theta() if theta is None else theta)
-            if th.ndim == 1:
-                th = th.reshape(-1, 1)
-            if th.ndim != 2 or th.shape[0] != self.D or (n_cols is not None and n_cols != th.shape[1]):
-                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({self.D}, {n_cols if n_cols is not None else 'n'})")
-            th = np.asfortranarray(th, dtype=self.dtype)
-            ptr, n = capi.as_ptr(th), th.shape[1]
+        ptr, n = self._draws("hglm_coefficients", theta, n_cols)
         beta = np.empty((P.value, n), dtype=self.dtype, order="F")
         tau = np.empty((G.value, n), dtype=self.dtype, order="F")
         self._call("ahmc_hglm_coefficients", ptr, n, capi.as_ptr(beta) if beta.size else None, capi.as_ptr(tau) if tau.size else None)
@@ -856,7 +814,7 @@ class Engine:
 
     def glm_pointwise(self):
         """(η, ℓ(y_i, η_i)) at the context's current θ, each (n_obs, N): ahmc_glm_pointwise"""
-        self._need_glm("glm_pointwise")
+        self._need("has_glm", "ahmc_glm.h", "glm_pointwise")
         n = C.c_int64()
         self._call("ahmc_get_target_glm", None, C.byref(n), None)
         eta = np.empty((n.value, self.N), dtype=self.dtype, order="F")

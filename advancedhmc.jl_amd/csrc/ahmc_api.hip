@@ -103,6 +103,30 @@ struct ExtRun {
   int fe_max = 0, fe_it = 0, fe_total = 0;
 };
 
+// the bound model of AHMC_TARGET_GLM (ahmc_glm_host.hpp; {} = none).  One slab at buf: X, Xᵀ, y, offset, p [, a zero precision, the
+// group table], then the workspaces U, partial [, partial_s], gs [, W, R]; part i starts at off[i]; sizes 0 where the model has none
+enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PART_S, GLM_PARTS };
+template <class T>
+struct GlmModel {
+  T* buf = nullptr;
+  int64_t off[GLM_PARTS] = {};
+  int family = 0;
+  int64_t n_obs = 0;
+  bool has_offset = false;
+  double scale = 1;
+  int64_t P = 0;  // the columns of X; θ has D = P + G (+ 1 with aux) rows, so P = D for a plain model
+  int G = 0;      // the coefficient groups (ahmc_glm_hier.h), as received
+  int32_t lo[HGLM_MAX_GROUPS] = {}, hi[HGLM_MAX_GROUPS] = {}, centered[HGLM_MAX_GROUPS] = {};
+  double A[HGLM_MAX_GROUPS] = {};
+  bool bound_hier = false;  // bound through ahmc_hglm_set_target or ahmc_glm_aux_set_target (n_groups = 0 included)
+  bool aux = false;         // θ ends with s, the log dispersion (ahmc_glm_aux.h); its prior Normal(aux_loc, aux_scale²)
+  double aux_loc = 0, aux_scale = 1;
+
+  bool on_w() const { return G > 0 || aux; }  // the products run on the effective coefficients W, not on θ
+  T* at(int part) const { return buf + off[part]; }
+  const HglmTab<T>* tab() const { return reinterpret_cast<const HglmTab<T>*>(at(GLM_TAB)); }
+};
+
 void comm_destroy_raw(void* comm);  // ncclCommDestroy through the run-time binding of ahmc_multi_host.hpp
 
 template <class T>
@@ -243,22 +267,7 @@ struct Ctx : CtxBase {
   size_t ru_cap = 0;
   int64_t ru_off[7] = {0, 0, 0, 0, 0, 0, 0};
   int ru_k = 0;
-  // AHMC_TARGET_GLM (ahmc_glm_host.hpp): one slab of X, Xᵀ, y, offset, p, U, partial, gs at glm_off[0..7]; with coefficient groups
-  // (ahmc_glm_hier.h) also W, R, a zero precision and the group table at glm_off[8..11]; with a sampled dispersion (ahmc_glm_aux.h)
-  // also partial_s at glm_off[12]
-  T* glm_buf = nullptr;
-  int64_t glm_off[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  bool glm_aux = false;  // θ ends with s, the log dispersion; its prior Normal(glm_aux_loc, glm_aux_scale²)
-  double glm_aux_loc = 0, glm_aux_scale = 1;
-  bool hglm_bound = false;  // bound through ahmc_hglm_set_target (n_groups = 0 included)
-  int64_t hglm_P = 0;
-  int hglm_G = 0;
-  int32_t hglm_lo[32] = {}, hglm_hi[32] = {}, hglm_centered[32] = {};
-  double hglm_A[32] = {};
-  int glm_family = 0;
-  int64_t glm_nobs = 0;
-  bool glm_has_offset = false;
-  double glm_scale = 1;
+  GlmModel<T> glm;
   // the low-rank mass-matrix adaptor of that metric (ahmc_lowrank_adapt_host.hpp): parameters, counters, one slab of doubles
   struct LowRank {
     bool on = false;
@@ -307,7 +316,7 @@ struct Ctx : CtxBase {
     void* bufs[] = {vbase, tbase, ibase, lbase, tparams, minv, sqrt_minv, scratch, order, order_hist, adaptk_dev, hmc_H, da_m, da_eps, da_mu, da_xbar,
                     da_Hbar, wv_mu, wv_M, wv_var, ext_th, ext_alpha, redo, znorm, dn_minv, dn_uinv, dn_W, dn_es, dn_RB, dn_VB,
                     dn_S, dn_active, dn_list, wg_mu, wg_M, ext_g, wc_mu, wc_M, wc_S, wc_cov, stage[0], stage[1], dn_C, ext_gstage, ext_lpstage,
-                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp, ru_buf, glm_buf, lr.buf};
+                    dn_P, dn_R, dn_S2, dn_ptcur, dn_Asw, da_tab, work_prev, work_last, work_sum, work_grp, ru_buf, glm.buf, lr.buf};
     for (void* b : bufs)
       if (b) (void)hipFree(b);
     for (auto* v : {&ev_pool, &ev_pending, &ev_pending_warm})
@@ -2197,9 +2206,9 @@ int32_t ahmc_set_target_glm(ahmc_ctx* ctx, int32_t family, int64_t n_obs, const 
 int32_t ahmc_get_target_glm(ahmc_ctx* ctx, int32_t* family, int64_t* n_obs, double* scale) {
   FOR_CTX(ctx, {
     if (c->target_kind != AHMC_TARGET_GLM) return fail(c, AHMC_ERR_ARGUMENT, "get_target_glm: no GLM is bound (ahmc_set_target_glm)");
-    if (family) *family = c->glm_family;
-    if (n_obs) *n_obs = c->glm_nobs;
-    if (scale) *scale = c->glm_scale;
+    if (family) *family = c->glm.family;
+    if (n_obs) *n_obs = c->glm.n_obs;
+    if (scale) *scale = c->glm.scale;
     return AHMC_OK;
   });
 }
@@ -2215,8 +2224,8 @@ int32_t ahmc_hglm_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, int64
                              const void* prior_prec, double scale, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
                              const double* hyper_scale) {
   FOR_CTX_MUT(ctx, {
-    int rc = hglm_set(c, (int)family, n_obs, n_coef, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset),
-                      static_cast<const T*>(prior_prec), scale, (int)n_groups, lo, hi, centered, hyper_scale);
+    const HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale};
+    int rc = hglm_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), scale, hs);
     if (rc) return rc;
     return dn_refresh_fused(c);
   });
@@ -2224,15 +2233,16 @@ int32_t ahmc_hglm_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, int64
 
 int32_t ahmc_hglm_get_target(ahmc_ctx* ctx, int64_t* n_coef, int32_t* n_groups, int32_t* lo, int32_t* hi, int32_t* centered, double* hyper_scale) {
   FOR_CTX(ctx, {
-    if (c->target_kind != AHMC_TARGET_GLM || !c->hglm_bound)
+    if (c->target_kind != AHMC_TARGET_GLM || !c->glm.bound_hier)
       return fail(c, AHMC_ERR_ARGUMENT, "hglm_get_target: no hierarchical GLM is bound (ahmc_hglm_set_target)");
-    if (n_coef) *n_coef = c->D - c->hglm_G - (c->glm_aux ? 1 : 0);
-    if (n_groups) *n_groups = c->hglm_G;
-    for (int k = 0; k < c->hglm_G; ++k) {
-      if (lo) lo[k] = c->hglm_lo[k];
-      if (hi) hi[k] = c->hglm_hi[k];
-      if (centered) centered[k] = c->hglm_centered[k];
-      if (hyper_scale) hyper_scale[k] = c->hglm_A[k];
+    const GlmModel<T>& m = c->glm;
+    if (n_coef) *n_coef = m.P;
+    if (n_groups) *n_groups = m.G;
+    for (int k = 0; k < m.G; ++k) {
+      if (lo) lo[k] = m.lo[k];
+      if (hi) hi[k] = m.hi[k];
+      if (centered) centered[k] = m.centered[k];
+      if (hyper_scale) hyper_scale[k] = m.A[k];
     }
     return AHMC_OK;
   });
@@ -2249,8 +2259,8 @@ int32_t ahmc_glm_aux_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, in
                                 const void* prior_prec, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
                                 const double* hyper_scale, double aux_loc, double aux_scale) {
   FOR_CTX_MUT(ctx, {
-    int rc = hglm_set(c, (int)family, n_obs, n_coef, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset),
-                      static_cast<const T*>(prior_prec), 1.0, (int)n_groups, lo, hi, centered, hyper_scale, true, aux_loc, aux_scale);
+    const HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale, true, aux_loc, aux_scale};
+    int rc = hglm_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), 1.0, hs);
     if (rc) return rc;
     return dn_refresh_fused(c);
   });
@@ -2258,10 +2268,10 @@ int32_t ahmc_glm_aux_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, in
 
 int32_t ahmc_glm_aux_get_target(ahmc_ctx* ctx, double* aux_loc, double* aux_scale) {
   FOR_CTX(ctx, {
-    if (c->target_kind != AHMC_TARGET_GLM || !c->glm_aux)
+    if (c->target_kind != AHMC_TARGET_GLM || !c->glm.aux)
       return fail(c, AHMC_ERR_ARGUMENT, "glm_aux_get_target: no model with a sampled dispersion is bound (ahmc_glm_aux_set_target)");
-    if (aux_loc) *aux_loc = c->glm_aux_loc;
-    if (aux_scale) *aux_scale = c->glm_aux_scale;
+    if (aux_loc) *aux_loc = c->glm.aux_loc;
+    if (aux_scale) *aux_scale = c->glm.aux_scale;
     return AHMC_OK;
   });
 }

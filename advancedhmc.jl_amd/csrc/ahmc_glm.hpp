@@ -411,16 +411,16 @@ struct HglmTab {  // the group table, in the model's slab
   T inv_a2[HGLM_MAX_GROUPS];  // 1/A_k²
 };
 
-// W (column stride P) and / or τ (column stride G) of the listed columns of th (column stride P + G); either output may be nullptr.
-// One exp per (column, group).
+// W (column stride P) and / or τ (column stride G) of the listed columns of th (column stride ldt: P + G, or P + G + 1 with a
+// dispersion's row); either output may be nullptr.  One exp per (column, group).
 template <class T>
 __global__ __launch_bounds__(256) void k_hglm_coef(const T* __restrict__ th, const HglmTab<T>* __restrict__ tab, T* __restrict__ W, T* __restrict__ tau_out, int P,
-                                                   int G, int64_t ncols, const int* __restrict__ idx) {
+                                                   int G, int64_t ldt, int64_t ncols, const int* __restrict__ idx) {
   const int lane = threadIdx.x & 63;
   const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= ncols) return;
   const int64_t c = idx ? (int64_t)idx[j] : j;
-  const T* t = th + c * ((int64_t)P + G);
+  const T* t = th + c * ldt;
   T* w = W ? W + c * P : nullptr;
   int prev = 0;
   for (int k = 0; k <= G; ++k) {
@@ -441,13 +441,11 @@ __global__ __launch_bounds__(256) void k_hglm_coef(const T* __restrict__ th, con
   }
 }
 
-// dst (nr, n) = rows r0 .. r0 + nr − 1 of src (ld, n): the group scales, or the dispersion, out of k_hglm_coef's τ when the table
-// carries the dispersion's empty group
+// out[j] = exp(th[row, j]), th (ld, n): the dispersion e^s of draws (ahmc_glm_dispersion), by the exp that makes τ above
 template <class T>
-__global__ __launch_bounds__(256) void k_glm_rows(const T* __restrict__ src, int ld, int r0, int nr, int64_t n, T* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * nr) return;
-  dst[i] = src[(i / nr) * ld + r0 + (int)(i % nr)];
+__global__ __launch_bounds__(256) void k_glm_exp_row(const T* __restrict__ th, int64_t ld, int64_t row, int64_t n, T* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) out[j] = exp(th[j * ld + row]);
 }
 
 // ℓπ and g of the listed chains from partial (Σℓ per row block), R = −Xᵀu, W and θ.  k_glm_lp's sums first (Σ partial, Σ p_d θ_d² over

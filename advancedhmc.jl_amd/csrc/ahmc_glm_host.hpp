@@ -10,8 +10,6 @@ bool listed_target(const Ctx<T>* c) {
   return c->target_kind == AHMC_TARGET_KERNEL || c->target_kind == AHMC_TARGET_GLM;
 }
 
-enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PART_S, GLM_PARTS };
-
 // a hierarchical model's groups as ahmc_hglm_set_target received them (n_groups may be 0: the plain model)
 struct HglmSpec {
   int64_t P;
@@ -24,64 +22,40 @@ struct HglmSpec {
 
 inline bool glm_aux_family(int family) { return family == AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA || family == AHMC_GLM_NEGBINOMIAL_LOG; }
 
-// the model runs on the effective coefficients W: groups are bound, or θ carries the dispersion's row after the coefficients
-template <class T>
-bool glm_on_w(const Ctx<T>* c) {
-  return c->hglm_G > 0 || c->glm_aux;
-}
-
-// the entries of the group table that k_hglm_coef walks: with a dispersion row one more, an EMPTY group [P, P) whose "scale" is
-// exp(s) — the kernel then strides θ by P + G + 1 and runs unedited
-template <class T>
-int glm_tab_groups(const Ctx<T>* c) {
-  return c->hglm_G + (c->glm_aux ? 1 : 0);
-}
-
-// the columns of X: D, or P when groups or a dispersion are bound (θ then carries the G log-scales [and s] after the P coefficient parameters)
-template <class T>
-int64_t glm_ncoef(const Ctx<T>* c) {
-  return glm_on_w(c) ? c->hglm_P : c->D;
-}
-
 template <class T>
 int glm_slices(const Ctx<T>* c) {
-  return (int)((c->glm_nobs + GLM_K_SLICE - 1) / GLM_K_SLICE);
+  return (int)((c->glm.n_obs + GLM_K_SLICE - 1) / GLM_K_SLICE);
 }
 
 // drop the model's buffers (another target takes over; the stream is made idle first)
 template <class T>
 int glm_release(Ctx<T>* c) {
-  if (!c->glm_buf) return AHMC_OK;
+  if (!c->glm.buf) return AHMC_OK;
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipFree(c->glm_buf));
-  c->glm_buf = nullptr;
-  c->glm_nobs = 0;
-  c->hglm_bound = false;
-  c->hglm_P = 0;
-  c->hglm_G = 0;
-  c->glm_aux = false;
+  HIPCHK(hipFree(c->glm.buf));
+  c->glm = {};
   return AHMC_OK;
 }
 
 // η (and from it U, partial; on request η and ℓ themselves) for ncols listed chains; th: the coefficients, (D, N) with column stride D
 template <class T>
 int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols, bool small, T* eta_out, T* ll_out) {
-  const T* b = c->glm_buf;
-  const int n_obs = (int)c->glm_nobs;
+  const GlmModel<T>& m = c->glm;
+  const int n_obs = (int)m.n_obs;
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M;
-  const T* X = b + c->glm_off[GLM_X];
-  const T* y = b + c->glm_off[GLM_Y];
-  const T* off = c->glm_has_offset ? b + c->glm_off[GLM_OFF] : nullptr;
-  T* U = c->glm_buf + c->glm_off[GLM_U];
-  T* part = c->glm_buf + c->glm_off[GLM_PART];
+  const T* X = m.at(GLM_X);
+  const T* y = m.at(GLM_Y);
+  const T* off = m.has_offset ? m.at(GLM_OFF) : nullptr;
+  T* U = m.at(GLM_U);
+  T* part = m.at(GLM_PART);
   // a sampled dispersion: s is row D − 1 of the chain's own θ (th holds W); Σ ∂ℓ/∂s per row block
-  const T* aux = c->glm_aux ? c->th + (c->D - 1) : nullptr;
-  T* part_s = c->glm_aux ? c->glm_buf + c->glm_off[GLM_PART_S] : nullptr;
-  if (glm_aux_family(c->glm_family) != c->glm_aux) return fail(c, AHMC_ERR_STATE, "glm: the family and the dispersion row disagree in the context");
+  const T* aux = m.aux ? c->th + (c->D - 1) : nullptr;
+  T* part_s = m.aux ? m.at(GLM_PART_S) : nullptr;
+  if (glm_aux_family(m.family) != m.aux) return fail(c, AHMC_ERR_STATE, "glm: the family and the dispersion row disagree in the context");
   const dim3 grid = small ? dim3((unsigned)nrb, (unsigned)((ncols + 15) / 16)) : dim3((unsigned)(nrb * (((ncols + GB_N - 1) / GB_N + 7) / 8 * 8)));
 #define AHMC_GLM_ETA(FAM, BN) \
-  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)c->glm_scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out, aux, (int64_t)c->D, part_s)
-  switch (c->glm_family * 2 + (small ? 1 : 0)) {
+  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)m.scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out, aux, (int64_t)c->D, part_s)
+  switch (m.family * 2 + (small ? 1 : 0)) {
     case 0: AHMC_GLM_ETA(0, 64); break;
     case 1: AHMC_GLM_ETA(0, 16); break;
     case 2: AHMC_GLM_ETA(1, 64); break;
@@ -115,23 +89,22 @@ bool glm_small(const Ctx<T>* c, int64_t row_blocks, int64_t ncols) {
 template <class T>
 int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   if (n <= 0) return AHMC_OK;
-  if (!c->glm_buf) return fail(c, AHMC_ERR_STATE, "AHMC_TARGET_GLM without a model (ahmc_set_target_glm)");
-  // groups bound: the products run on the effective coefficients W (P, N) with a zero precision and leave R = −Xᵀu;
-  // k_hglm_coef before them and k_hglm_finish after them are the model (ahmc_glm.hpp)
-  const bool hier = glm_on_w(c);
-  const int n_obs = (int)c->glm_nobs, D = (int)glm_ncoef(c), G = c->hglm_G, ns = glm_slices(c);
+  const GlmModel<T>& m = c->glm;
+  if (!m.buf) return fail(c, AHMC_ERR_STATE, "AHMC_TARGET_GLM without a model (ahmc_set_target_glm)");
+  // groups or a dispersion bound: the products run on the effective coefficients W (P, N) with a zero precision and leave
+  // R = −Xᵀu; k_hglm_coef before them and k_hglm_finish after them are the model (ahmc_glm.hpp)
+  const bool hier = m.on_w();
+  const int n_obs = (int)m.n_obs, D = (int)m.P, G = m.G, ns = glm_slices(c);
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, nrbD = (int64_t)(D + GB_M - 1) / GB_M * ns;
-  const T* b = c->glm_buf;
-  const T* th = hier ? b + c->glm_off[GLM_W] : (const T*)c->th;
-  const T* prec = b + c->glm_off[hier ? GLM_ZERO : GLM_PREC];
-  T* g = hier ? c->glm_buf + c->glm_off[GLM_R] : c->g;
-  const HglmTab<T>* tab = reinterpret_cast<const HglmTab<T>*>(b + c->glm_off[GLM_TAB]);
-  if (hier) hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, tab, c->glm_buf + c->glm_off[GLM_W], (T*)nullptr, D, glm_tab_groups(c), n, list);
+  const T* th = hier ? m.at(GLM_W) : (const T*)c->th;
+  const T* prec = m.at(hier ? GLM_ZERO : GLM_PREC);
+  T* g = hier ? m.at(GLM_R) : c->g;
+  if (hier) hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, m.tab(), m.at(GLM_W), (T*)nullptr, D, G, c->D, n, list);
   int rc = glm_launch_eta(c, th, D, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr);
   if (rc) return rc;
-  const T* Xt = b + c->glm_off[GLM_XT];
-  const T* U = b + c->glm_off[GLM_U];
-  T* gs = c->glm_buf + c->glm_off[GLM_GS];
+  const T* Xt = m.at(GLM_XT);
+  const T* U = m.at(GLM_U);
+  T* gs = m.at(GLM_GS);
   if (glm_small(c, nrbD, n))
     hipLaunchKernelGGL((k_glm_grad<T, 16>), dim3((unsigned)nrbD, (unsigned)((n + 15) / 16)), dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, D, n, c->N,
                        list, ns);
@@ -140,15 +113,15 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
                        n_obs, D, n, c->N, list, ns);
   if (ns > 1)
     hipLaunchKernelGGL((k_glm_gsum<T>), dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, th, g, D, n, c->N, list, ns);
-  if (c->glm_aux)
-    hipLaunchKernelGGL((k_hglm_finish_aux<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], b + c->glm_off[GLM_PART_S],
-                       (const T*)g, th, b + c->glm_off[GLM_PREC], (const T*)c->th, tab, c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0,
-                       (T)c->glm_aux_loc, (T)(1.0 / (c->glm_aux_scale * c->glm_aux_scale)));
+  if (m.aux)
+    hipLaunchKernelGGL((k_hglm_finish_aux<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)m.at(GLM_PART), (const T*)m.at(GLM_PART_S),
+                       (const T*)g, th, (const T*)m.at(GLM_PREC), (const T*)c->th, m.tab(), c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0,
+                       (T)m.aux_loc, (T)(1.0 / (m.aux_scale * m.aux_scale)));
   else if (hier)
-    hipLaunchKernelGGL((k_hglm_finish<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], (const T*)g, th,
-                       b + c->glm_off[GLM_PREC], (const T*)c->th, tab, c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0);
+    hipLaunchKernelGGL((k_hglm_finish<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)m.at(GLM_PART), (const T*)g, th,
+                       (const T*)m.at(GLM_PREC), (const T*)c->th, m.tab(), c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0);
   else
-    hipLaunchKernelGGL((k_glm_lp<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, b + c->glm_off[GLM_PART], prec, th, c->lp, (int)nrb, D, n, c->N, list,
+    hipLaunchKernelGGL((k_glm_lp<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)m.at(GLM_PART), prec, th, c->lp, (int)nrb, D, n, c->N, list,
                        sanitize_lp ? 1 : 0);
   HIPCHK(hipGetLastError());
   return AHMC_OK;
@@ -158,7 +131,7 @@ template <class T>
 int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, const HglmSpec* hs = nullptr) {
   const int G = hs ? hs->G : 0;
   const bool aux = hs && hs->aux, on_w = G > 0 || aux;
-  const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the columns of X)
+  const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the columns of X: the record's P)
   if (glm_aux_family(family) && !aux)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family) +
                                           " at this entry point: it samples its dispersion and is bound through ahmc_glm_aux_set_target (include/ahmc_glm_aux.h)");
@@ -183,7 +156,9 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
     sizes[GLM_TAB] = tab_elems;
   }
   const int layout[GLM_PARTS] = {GLM_X, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_ZERO, GLM_TAB, GLM_U, GLM_PART, GLM_PART_S, GLM_GS, GLM_W, GLM_R};
-  int64_t off[GLM_PARTS], total = 0;
+  GlmModel<T> m;  // (becomes the context's once nothing can fail any more)
+  int64_t* const off = m.off;
+  int64_t total = 0;
   for (int i : layout) {
     off[i] = total;
     total += (sizes[i] + 1) / 2 * 2;  // (16-byte alignment of every part, Float32 included)
@@ -217,15 +192,11 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
       for (int64_t d = hs->lo[k]; d < hs->hi[k]; ++d)
         if ((double)h[off[GLM_PREC] + d] != 0)
           return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: prior_prec[" + std::to_string(d + 1) + "] must be 0: the coefficient is a member of group " + std::to_string(k + 1));
-      tab.lo[k] = hs->lo[k];
-      tab.hi[k] = hs->hi[k];
-      tab.centered[k] = hs->centered && hs->centered[k] ? 1 : 0;
+      tab.lo[k] = m.lo[k] = hs->lo[k];
+      tab.hi[k] = m.hi[k] = hs->hi[k];
+      tab.centered[k] = m.centered[k] = hs->centered && hs->centered[k] ? 1 : 0;
       tab.inv_a2[k] = (T)(1.0 / (hs->A[k] * hs->A[k]));
-    }
-    if (aux) {  // the dispersion's row as an empty group: what k_hglm_coef needs to stride θ by P + G + 1 (glm_tab_groups)
-      tab.lo[G] = tab.hi[G] = (int)D;
-      tab.centered[G] = 1;
-      tab.inv_a2[G] = T(0);
+      m.A[k] = hs->A[k];
     }
     memcpy(h.data() + off[GLM_TAB], &tab, sizeof(tab));
   }
@@ -233,37 +204,28 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   for (int64_t d = 0; d < D; ++d)
     for (int64_t i = 0; i < n_obs; ++i) hXt[d + i * D] = hX[i + d * n_obs];
   // everything that can fail happens before the previous target is touched
-  T* buf = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&buf), sizeof(T) * (size_t)total) != hipSuccess) {
+  if (hipMalloc(reinterpret_cast<void**>(&m.buf), sizeof(T) * (size_t)total) != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, AHMC_ERR_RUNTIME, "set_target_glm: cannot allocate " + std::to_string((long long)(sizeof(T) * (size_t)total)) + " bytes for the model (" +
                                          std::to_string((long long)(sizeof(T) * (size_t)n_data)) + ") and its workspaces U (n_obs × N), partial and the slice sums" +
                                          (on_w ? ", W and R (n_coef × N)" : "") + (aux ? ", partial_s" : ""));
   }
-  if (hipMemcpy(buf, h.data(), sizeof(T) * (size_t)n_data, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-    (void)hipFree(buf);
+  if (hipMemcpy(m.buf, h.data(), sizeof(T) * (size_t)n_data, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipFree(m.buf);
     return fail(c, AHMC_ERR_RUNTIME, std::string("set_target_glm: copying the model failed: ") + hipGetErrorString(hipGetLastError()));
   }
-  if (c->glm_buf) (void)hipFree(c->glm_buf);  // (the stream is idle)
+  if (c->glm.buf) (void)hipFree(c->glm.buf);  // (the stream is idle)
   if (c->tparams) { (void)hipFree(c->tparams); c->tparams = nullptr; }
-  c->glm_buf = buf;
-  for (int i = 0; i < GLM_PARTS; ++i) c->glm_off[i] = off[i];
-  c->hglm_bound = hs != nullptr;
-  c->hglm_P = hs ? hs->P : 0;
-  c->hglm_G = G;
-  c->glm_aux = aux;
-  c->glm_aux_loc = aux ? hs->aux_loc : 0;
-  c->glm_aux_scale = aux ? hs->aux_scale : 1;
-  for (int k = 0; k < G; ++k) {
-    c->hglm_lo[k] = hs->lo[k];
-    c->hglm_hi[k] = hs->hi[k];
-    c->hglm_centered[k] = hs->centered && hs->centered[k] ? 1 : 0;
-    c->hglm_A[k] = hs->A[k];
-  }
-  c->glm_family = family;
-  c->glm_nobs = n_obs;
-  c->glm_has_offset = offset != nullptr;
-  c->glm_scale = scale;
+  m.family = family;
+  m.n_obs = n_obs;
+  m.has_offset = offset != nullptr;
+  m.scale = scale;
+  m.P = D;
+  m.G = G;
+  m.bound_hier = hs != nullptr;
+  m.aux = aux;
+  if (aux) { m.aux_loc = hs->aux_loc; m.aux_scale = hs->aux_scale; }
+  c->glm = m;
   c->target_kind = AHMC_TARGET_GLM;
   c->have_point = false;
   invalidate_schedule(c);
@@ -272,23 +234,23 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
 
 template <class T>
 int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
-  if (c->target_kind != AHMC_TARGET_GLM || !c->glm_buf) return fail(c, AHMC_ERR_ARGUMENT, "glm_pointwise: no GLM is bound (ahmc_set_target_glm)");
+  const GlmModel<T>& m = c->glm;
+  if (c->target_kind != AHMC_TARGET_GLM || !m.buf) return fail(c, AHMC_ERR_ARGUMENT, "glm_pointwise: no GLM is bound (ahmc_set_target_glm)");
   if (!eta_out && !ll_out) return AHMC_OK;
-  const size_t n = (size_t)c->glm_nobs * (size_t)c->N;
+  const size_t n = (size_t)m.n_obs * (size_t)c->N;
   T* tmp = nullptr;
   if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * 2 * n) != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, AHMC_ERR_RUNTIME, "glm_pointwise: cannot allocate " + std::to_string((long long)(sizeof(T) * 2 * n)) + " bytes");
   }
-  const int64_t nrb = (c->glm_nobs + GB_M - 1) / GB_M;
+  const int64_t nrb = (m.n_obs + GB_M - 1) / GB_M;
   const T* th = c->th;
-  if (glm_on_w(c)) {  // the effective coefficients first
-    T* W = c->glm_buf + c->glm_off[GLM_W];
-    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th,
-                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, (T*)nullptr, (int)c->hglm_P, glm_tab_groups(c), c->N, (const int*)nullptr);
-    th = W;
+  if (m.on_w()) {  // the effective coefficients first
+    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, m.tab(), m.at(GLM_W), (T*)nullptr, (int)m.P, m.G,
+                       c->D, c->N, (const int*)nullptr);
+    th = m.at(GLM_W);
   }
-  int rc = glm_launch_eta(c, th, (int)glm_ncoef(c), (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_out ? tmp : (T*)nullptr, ll_out ? tmp + n : (T*)nullptr);
+  int rc = glm_launch_eta(c, th, (int)m.P, (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_out ? tmp : (T*)nullptr, ll_out ? tmp + n : (T*)nullptr);
   hipError_t e = hipSuccess;
   if (!rc && eta_out) e = hipMemcpyAsync(eta_out, tmp, sizeof(T) * n, hipMemcpyDefault, c->stream);
   if (!rc && e == hipSuccess && ll_out) e = hipMemcpyAsync(ll_out, tmp + n, sizeof(T) * n, hipMemcpyDefault, c->stream);
@@ -301,8 +263,10 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
 
 // ---- include/ahmc_glm_hier.h ----
 template <class T>
-int hglm_set(Ctx<T>* c, int family, int64_t n_obs, int64_t n_coef, const T* X, const T* y, const T* offset, const T* prec, double scale, int n_groups,
-             const int32_t* lo, const int32_t* hi, const int32_t* centered, const double* A, bool aux = false, double aux_loc = 0, double aux_scale = 1) {
+int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, const HglmSpec& hs) {
+  const int64_t n_coef = hs.P;
+  const int n_groups = hs.G;
+  const bool aux = hs.aux;
   if (n_groups < 0) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: n_groups must be >= 0; got " + std::to_string(n_groups));
   if (aux && n_groups > AHMC_GLM_AUX_MAX_GROUPS)
     return fail(c, AHMC_ERR_UNSUPPORTED, "glm_aux_set_target: n_groups = " + std::to_string(n_groups) + " is beyond the engine's limit AHMC_GLM_AUX_MAX_GROUPS = " +
@@ -313,99 +277,81 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, int64_t n_coef, const T* X, c
   if (n_coef < 1 || c->D != n_coef + n_groups + (aux ? 1 : 0))
     return fail(c, AHMC_ERR_ARGUMENT, "DimensionMismatch: the context has D = " + std::to_string((long long)c->D) + ", the model n_coef + n_groups = " +
                                           std::to_string((long long)n_coef) + " + " + std::to_string(n_groups) + (aux ? " (+ 1: the dispersion's row)" : ""));
-  if (aux && !std::isfinite(aux_loc)) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_loc = " + std::to_string(aux_loc) + " must be finite");
-  if (aux && !(std::isfinite(aux_scale) && aux_scale > 0))
-    return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_scale = " + std::to_string(aux_scale) + " must be finite and > 0");
-  if (n_groups > 0 && (!lo || !hi || !A)) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: lo, hi or hyper_scale is NULL");
+  if (aux && !std::isfinite(hs.aux_loc)) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_loc = " + std::to_string(hs.aux_loc) + " must be finite");
+  if (aux && !(std::isfinite(hs.aux_scale) && hs.aux_scale > 0))
+    return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_scale = " + std::to_string(hs.aux_scale) + " must be finite and > 0");
+  if (n_groups > 0 && (!hs.lo || !hs.hi || !hs.A)) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: lo, hi or hyper_scale is NULL");
   int64_t prev = 0;
   for (int k = 0; k < n_groups; ++k) {
-    const std::string grp = "group " + std::to_string(k + 1) + " = [" + std::to_string(lo[k]) + ", " + std::to_string(hi[k]) + ")";
-    if (lo[k] < 0 || hi[k] > n_coef) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is out of bounds [0, " + std::to_string((long long)n_coef) + ")");
-    if (hi[k] <= lo[k]) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is empty");
-    if (lo[k] < prev) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " overlaps the group before it or is out of order");
-    if (!(std::isfinite(A[k]) && A[k] > 0))
-      return fail(c, AHMC_ERR_ARGUMENT, "DomainError: hyper_scale[" + std::to_string(k + 1) + "] = " + std::to_string(A[k]) + " must be finite and > 0");
-    prev = hi[k];
+    const int32_t lo = hs.lo[k], hi = hs.hi[k];
+    const std::string grp = "group " + std::to_string(k + 1) + " = [" + std::to_string(lo) + ", " + std::to_string(hi) + ")";
+    if (lo < 0 || hi > n_coef) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is out of bounds [0, " + std::to_string((long long)n_coef) + ")");
+    if (hi <= lo) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is empty");
+    if (lo < prev) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " overlaps the group before it or is out of order");
+    if (!(std::isfinite(hs.A[k]) && hs.A[k] > 0))
+      return fail(c, AHMC_ERR_ARGUMENT, "DomainError: hyper_scale[" + std::to_string(k + 1) + "] = " + std::to_string(hs.A[k]) + " must be finite and > 0");
+    prev = hi;
   }
-  const HglmSpec hs{n_coef, n_groups, lo, hi, centered, A, aux, aux_loc, aux_scale};
   return glm_set(c, family, n_obs, X, y, offset, prec, scale, &hs);
+}
+
+// ahmc_hglm_coefficients and ahmc_glm_dispersion: a temporary of `elems` elements that begins with the n_theta elements of the
+// caller's draws (host or device memory); `run(tmp)` enqueues the kernel and the copies out and returns the first error
+template <class T, class F>
+int glm_on_draws(Ctx<T>* c, const char* who, const void* theta, size_t n_theta, size_t elems, F run) {
+  T* tmp = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * elems) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, AHMC_ERR_RUNTIME, std::string(who) + ": cannot allocate " + std::to_string((long long)(sizeof(T) * elems)) + " bytes");
+  }
+  hipError_t e = hipMemcpyAsync(tmp, theta, sizeof(T) * n_theta, hipMemcpyDefault, c->stream);
+  if (e == hipSuccess) e = run(tmp);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  (void)hipFree(tmp);
+  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : es));
+  return AHMC_OK;
 }
 
 // β (P, n_cols) and / or τ (G, n_cols) of any (D, n_cols) array of draws, host or device pointers
 template <class T>
 int hglm_coefficients(Ctx<T>* c, const void* theta, int64_t n_cols, void* beta_out, void* tau_out) {
-  if (c->target_kind != AHMC_TARGET_GLM || !c->glm_buf || !c->hglm_bound)
+  const GlmModel<T>& m = c->glm;
+  if (c->target_kind != AHMC_TARGET_GLM || !m.buf || !m.bound_hier)
     return fail(c, AHMC_ERR_ARGUMENT, "hglm_coefficients: no hierarchical GLM is bound (ahmc_hglm_set_target)");
   if (n_cols < 0 || (n_cols > 0 && !theta)) return fail(c, AHMC_ERR_ARGUMENT, "hglm_coefficients: theta is NULL or n_cols < 0");
   if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, "hglm_coefficients: n_cols beyond 2^31 - 1");
   if (n_cols == 0 || (!beta_out && !tau_out)) return AHMC_OK;
-  const int64_t P = glm_ncoef(c), G = c->hglm_G, GT = glm_tab_groups(c), D = P + GT;  // (GT: with the dispersion's row, an empty group)
-  if (GT == 0) {  // the plain model: β = θ
+  const int64_t P = m.P, G = m.G, D = c->D;
+  if (!m.on_w()) {  // the plain model: β = θ
     if (beta_out) HIPCHK(hipMemcpyAsync(beta_out, theta, sizeof(T) * (size_t)(P * n_cols), hipMemcpyDefault, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return AHMC_OK;
   }
-  T* tmp = nullptr;
-  const size_t total = (size_t)((D + P + GT + G) * n_cols);
-  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * total) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(c, AHMC_ERR_RUNTIME, "hglm_coefficients: cannot allocate " + std::to_string((long long)(sizeof(T) * total)) + " bytes");
-  }
-  T *th = tmp, *W = tmp + D * n_cols, *tau = W + P * n_cols;
-  hipError_t e = hipMemcpyAsync(th, theta, sizeof(T) * (size_t)(D * n_cols), hipMemcpyDefault, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, c->stream, (const T*)th,
-                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), W, tau, (int)P, (int)GT, n_cols, (const int*)nullptr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && beta_out) e = hipMemcpyAsync(beta_out, W, sizeof(T) * (size_t)(P * n_cols), hipMemcpyDefault, c->stream);
-  if (e == hipSuccess && tau_out && G > 0) {
-    const T* src = tau;
-    if (GT != G) {  // (rows 0 .. G − 1 of each column's GT: the last is the dispersion)
-      T* packed = tau + GT * n_cols;
-      hipLaunchKernelGGL((k_glm_rows<T>), dim3((unsigned)((G * n_cols + 255) / 256)), dim3(256), 0, c->stream, (const T*)tau, (int)GT, 0, (int)G, n_cols, packed);
-      e = hipGetLastError();
-      src = packed;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(tau_out, src, sizeof(T) * (size_t)(G * n_cols), hipMemcpyDefault, c->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("hglm_coefficients: ") + hipGetErrorString(e != hipSuccess ? e : es));
-  return AHMC_OK;
+  return glm_on_draws(c, "hglm_coefficients", theta, (size_t)(D * n_cols), (size_t)((D + P + G) * n_cols), [&](T* th) {
+    T *W = th + D * n_cols, *tau = W + P * n_cols;
+    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, c->stream, (const T*)th, m.tab(), W, tau, (int)P, (int)G, D, n_cols,
+                       (const int*)nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && beta_out) e = hipMemcpyAsync(beta_out, W, sizeof(T) * (size_t)(P * n_cols), hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && tau_out && G > 0) e = hipMemcpyAsync(tau_out, tau, sizeof(T) * (size_t)(G * n_cols), hipMemcpyDefault, c->stream);
+    return e;
+  });
 }
 
 // ---- include/ahmc_glm_aux.h ----
-// exp(s) of any (D, n_cols) array of draws, host or device pointers: k_hglm_coef's τ of the table's last (empty) group
+// exp(s) of any (D, n_cols) array of draws, host or device pointers: s is each column's last row
 template <class T>
 int glm_dispersion(Ctx<T>* c, const void* theta, int64_t n_cols, void* out) {
-  if (c->target_kind != AHMC_TARGET_GLM || !c->glm_buf || !c->glm_aux)
+  if (c->target_kind != AHMC_TARGET_GLM || !c->glm.buf || !c->glm.aux)
     return fail(c, AHMC_ERR_ARGUMENT, "glm_dispersion: no model with a sampled dispersion is bound (ahmc_glm_aux_set_target)");
   if (n_cols < 0 || (n_cols > 0 && (!theta || !out))) return fail(c, AHMC_ERR_ARGUMENT, "glm_dispersion: theta or out is NULL, or n_cols < 0");
   if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, "glm_dispersion: n_cols beyond 2^31 - 1");
   if (n_cols == 0) return AHMC_OK;
-  const int64_t P = glm_ncoef(c), GT = glm_tab_groups(c), D = P + GT;
-  T* tmp = nullptr;
-  const size_t total = (size_t)((D + GT + 1) * n_cols);
-  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * total) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(c, AHMC_ERR_RUNTIME, "glm_dispersion: cannot allocate " + std::to_string((long long)(sizeof(T) * total)) + " bytes");
-  }
-  T *th = tmp, *tau = tmp + D * n_cols;
-  hipError_t e = hipMemcpyAsync(th, theta, sizeof(T) * (size_t)(D * n_cols), hipMemcpyDefault, c->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n_cols + 3) / 4)), dim3(256), 0, c->stream, (const T*)th,
-                       reinterpret_cast<const HglmTab<T>*>(c->glm_buf + c->glm_off[GLM_TAB]), (T*)nullptr, tau, (int)P, (int)GT, n_cols, (const int*)nullptr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
-    T* packed = tau + GT * n_cols;
-    hipLaunchKernelGGL((k_glm_rows<T>), dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, c->stream, (const T*)tau, (int)GT, (int)(GT - 1), 1, n_cols, packed);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, packed, sizeof(T) * (size_t)n_cols, hipMemcpyDefault, c->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("glm_dispersion: ") + hipGetErrorString(e != hipSuccess ? e : es));
-  return AHMC_OK;
+  const int64_t D = c->D;
+  return glm_on_draws(c, "glm_dispersion", theta, (size_t)(D * n_cols), (size_t)((D + 1) * n_cols), [&](T* th) {
+    T* e_s = th + D * n_cols;
+    hipLaunchKernelGGL((k_glm_exp_row<T>), dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, c->stream, (const T*)th, D, D - 1, n_cols, e_s);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipMemcpyAsync(out, e_s, sizeof(T) * (size_t)n_cols, hipMemcpyDefault, c->stream);
+  });
 }

@@ -87,11 +87,11 @@ def linear_predictor(X, theta, offset=None):
 def pointwise(family, X, y, theta, offset=None, scale=1.0):
     """(η, ℓ(y_i, η_i)), each (n_obs, N): the mirror of ahmc_glm_pointwise.  A family with a sampled dispersion takes it from θ's
     last row (θ then has one row more than X has columns)."""
-    if family_code(family) in AUX_FAMILIES:
-        return hier_pointwise(family, X, y, theta, (), offset, scale)
-    eta = linear_predictor(X, theta, offset)
-    ll, _ = link(family, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, scale)
-    return eta, ll
+    fam = family_code(family)
+    if fam in AUX_FAMILIES:
+        return _link_at(fam, *_hier_pointwise_args(fam, X, theta, ()), y, offset, scale)[2:4]
+    X, th, _ = _theta(X, theta)
+    return _link_at(fam, X, th, [], y, offset, scale)[2:4]
 
 
 def block_sums(ll):
@@ -114,20 +114,9 @@ def logdensity(family, X, y, theta, offset=None, prior_prec=None, scale=1.0, aux
     ℓπ is returned as computed: an overflowing Poisson gives a non-finite value, which the engine sanitises (`sanitize`).
     `aux_prior` = (loc, scale) belongs to the families with a sampled dispersion (θ then has D + 1 rows)."""
     if family_code(family) in AUX_FAMILIES or aux_prior is not None:
-        return aux_logdensity(family, X, y, theta, (), offset, prior_prec, aux_prior)
+        return _logdensity(*_hier_args(family, X, theta, (), prior_prec, aux_prior), y, offset)
     X, th, _ = _theta(X, theta)
-    p = np.zeros(X.shape[1]) if prior_prec is None else np.asarray(prior_prec, dtype=np.float64).ravel()
-    eta = linear_predictor(X, th, offset)
-    ll, u = link(family, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, scale)
-    with np.errstate(over="ignore", invalid="ignore"):
-        lsum = block_sums(ll).sum(axis=0)
-        xtu = np.zeros_like(th)
-        for k0 in range(0, X.shape[0], K_SLICE):
-            xtu = xtu + X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
-        pt = p.reshape(-1, 1) * th
-        lp = lsum - 0.5 * (pt * th).sum(axis=0)
-        grad = xtu - pt
-    return lp, grad
+    return _logdensity(family_code(family), X, th, [], _prior_prec(prior_prec, X.shape[1], []), None, y, offset, scale)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -203,42 +192,15 @@ def hier_coefficients(theta, P, groups):
 def hier_pointwise(family, X, y, theta, groups, offset=None, scale=1.0):
     """(η, ℓ(y_i, η_i)), each (n_obs, N): `pointwise` at the effective coefficients W; the dispersion of a family that samples it
     comes from θ's last row"""
-    X = np.asarray(X, dtype=np.float64)
-    if family_code(family) in AUX_FAMILIES:
-        th = np.asarray(theta, dtype=np.float64)
-        th = th.reshape(-1, 1) if th.ndim == 1 else th
-        W, _ = hier_coefficients(th[:-1], X.shape[1], groups)
-        eta = linear_predictor(X, W, offset)
-        return eta, link(family, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, s=th[-1:])[0]
-    W, _ = hier_coefficients(theta, X.shape[1], groups)
-    return pointwise(family, X, y, W, offset, scale)
+    fam = family_code(family)
+    return _link_at(fam, *_hier_pointwise_args(fam, X, theta, groups), y, offset, scale)[2:4]
 
 
 def hier_logdensity(family, X, y, theta, groups, offset=None, prior_prec=None, scale=1.0, aux_prior=None):
     """(ℓπ (N,), ∇ℓπ (P + G, N)) at θ (P + G, N).  `prior_prec` (P) covers the coefficients in no group and must be 0 on members.
     ℓπ is returned as computed (`sanitize` makes a non-finite value −Inf, as the engine does).  A family with a sampled dispersion
     has one more row, s, with the prior `aux_prior` = (loc, scale): `aux_logdensity`."""
-    if family_code(family) in AUX_FAMILIES or aux_prior is not None:
-        return aux_logdensity(family, X, y, theta, groups, offset, prior_prec, aux_prior)
-    X = np.asarray(X, dtype=np.float64)
-    P = X.shape[1]
-    th, groups = _hier_theta(theta, P, groups)
-    p = np.zeros(P) if prior_prec is None else np.asarray(prior_prec, dtype=np.float64).ravel()
-    for lo, hi, _, _ in groups:
-        if np.any(p[lo:hi] != 0):
-            raise ValueError(f"ArgumentError: prior_prec must be 0 on the members of a group ([{lo}, {hi}))")
-    if not groups:
-        return logdensity(family, X, y, th, offset, p, scale)
-    W, tau = hier_coefficients(th, P, groups)
-    eta = linear_predictor(X, W, offset)
-    ll, u = link(family, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, scale)
-    with np.errstate(over="ignore", invalid="ignore"):
-        lsum = block_sums(ll).sum(axis=0)
-        xtu = np.zeros_like(W)
-        for k0 in range(0, X.shape[0], K_SLICE):
-            xtu = xtu + X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
-        lp, g = _hier_finish(th, W, tau, -xtu, lsum, p, groups)
-    return lp, -g
+    return _logdensity(*_hier_args(family, X, theta, groups, prior_prec, aux_prior), y, offset, scale)
 
 
 def _hier_finish(th, W, tau, R, lsum, p, groups):
@@ -387,36 +349,73 @@ def dispersion(theta):
 
 def aux_logdensity(family, X, y, theta, groups=(), offset=None, prior_prec=None, aux_prior=None):
     """(ℓπ (N,), ∇ℓπ (D, N)) at θ (D, N), D = P + G + 1, of a family with a sampled dispersion"""
-    fam = family_code(family)
-    if fam not in AUX_FAMILIES:
-        raise ValueError(f"ArgumentError: family {fam} has no sampled dispersion (aux_prior belongs to {sorted(f for f in FAMILIES if FAMILIES[f] in AUX_FAMILIES)})")
-    m, A = check_aux_prior(aux_prior)
-    X = np.asarray(X, dtype=np.float64)
-    P = X.shape[1]
-    th = np.asarray(theta, dtype=np.float64)
-    if th.ndim == 1:
-        th = th.reshape(-1, 1)
-    groups = check_groups(groups, P)
-    if th.shape[0] != P + len(groups) + 1:
-        raise ValueError(f"DimensionMismatch: θ {th.shape}, P + G + 1 = {P} + {len(groups)} + 1")
+    return _logdensity(*_hier_args(family, X, theta, groups, prior_prec, aux_prior, True), y, offset)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the one evaluation path: the public functions above check their arguments and end here
+# ------------------------------------------------------------------------------------------------------------------------------
+def _prior_prec(prior_prec, P, groups):
     p = np.zeros(P) if prior_prec is None else np.asarray(prior_prec, dtype=np.float64).ravel()
     for lo, hi, _, _ in groups:
         if np.any(p[lo:hi] != 0):
             raise ValueError(f"ArgumentError: prior_prec must be 0 on the members of a group ([{lo}, {hi}))")
-    s = th[-1]
-    W, tau = hier_coefficients(th[:-1], P, groups)
+    return p
+
+
+def _hier_args(family, X, theta, groups, prior_prec, aux_prior, is_aux=False):
+    """the checks of θ (P + G, N), or (P + G + 1, N) for a family with a sampled dispersion: `_logdensity`'s first six arguments"""
+    fam = family_code(family)
+    is_aux = is_aux or fam in AUX_FAMILIES or aux_prior is not None
+    if is_aux and fam not in AUX_FAMILIES:
+        raise ValueError(f"ArgumentError: family {fam} has no sampled dispersion (aux_prior belongs to {sorted(f for f in FAMILIES if FAMILIES[f] in AUX_FAMILIES)})")
+    aux = check_aux_prior(aux_prior) if is_aux else None
+    X = np.asarray(X, dtype=np.float64)
+    P = X.shape[1]
+    th = np.asarray(theta, dtype=np.float64)
+    th = th.reshape(-1, 1) if th.ndim == 1 else th
+    if not is_aux:
+        th, groups = _hier_theta(th, P, groups)
+    else:
+        groups = check_groups(groups, P)
+        if th.shape[0] != P + len(groups) + 1:
+            raise ValueError(f"DimensionMismatch: θ {th.shape}, P + G + 1 = {P} + {len(groups)} + 1")
+    return fam, X, th, groups, _prior_prec(prior_prec, P, groups), aux
+
+
+def _hier_pointwise_args(fam, X, theta, groups):
+    X = np.asarray(X, dtype=np.float64)
+    th = np.ascontiguousarray(theta, dtype=np.float64)   # (row-major, as W is below: numpy's product depends on the memory order)
+    th = th.reshape(-1, 1) if th.ndim == 1 else th
+    _, groups = _hier_theta(th[:-1] if fam in AUX_FAMILIES else th, X.shape[1], groups)
+    return X, th, groups
+
+
+def _link_at(fam, X, th, groups, y, offset, scale):
+    """θ (P + G [+ 1], N) split into the coefficient parameters, the log-scales and s: (W, τ, η, *`link`'s values at η); the plain
+    model's W is θ itself, in the caller's memory order"""
+    P, G = X.shape[1], len(groups)
+    W, tau = hier_coefficients(th[:P + G], P, groups) if th.shape[0] > P else (th, th[P:])
     eta = linear_predictor(X, W, offset)
-    ll, u, ds = link(fam, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, s=s.reshape(1, -1))
+    return (W, tau, eta, *link(fam, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, scale, th[P + G:] if fam in AUX_FAMILIES else None))
+
+
+def _logdensity(fam, X, th, groups, p, aux, y, offset, scale=1.0):
+    """(ℓπ, ∇ℓπ) of every model: `groups` checked (maybe none), p (P), `aux` = (m, A) of the prior of s or None"""
+    PG = X.shape[1] + len(groups)
+    W, tau, _, ll, u, *ds = _link_at(fam, X, th, groups, y, offset, scale)
     with np.errstate(over="ignore", invalid="ignore"):
         lsum = block_sums(ll).sum(axis=0)
-        dsum = block_sums(ds).sum(axis=0)
         xtu = np.zeros_like(W)
         for k0 in range(0, X.shape[0], K_SLICE):
             xtu = xtu + X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
         g = np.empty_like(th)
-        lp, g[:-1] = _hier_finish(th[:-1], W, tau, -xtu, lsum, p, groups)
-        ia2 = 1.0 / (A * A)
-        r = s - m
-        lp = lp + ((-0.5 * ia2) * r) * r
-        g[-1] = r * ia2 - dsum
+        lp, g[:PG] = _hier_finish(th[:PG], W, tau, -xtu, lsum, p, groups)
+        if aux is not None:
+            m, A = aux
+            dsum = block_sums(ds[0]).sum(axis=0)
+            ia2 = 1.0 / (A * A)
+            r = th[-1] - m
+            lp = lp + ((-0.5 * ia2) * r) * r
+            g[-1] = r * ia2 - dsum
     return lp, -g

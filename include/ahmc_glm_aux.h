@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define AHMC_GLM_AUX_VERSION 1
-#define AHMC_GLM_AUX_MAX_GROUPS 31 /* the row of s takes one entry of the engine's group table */
+#define AHMC_GLM_AUX_MAX_GROUPS 31 /* a limit this ABI version keeps: one below AHMC_HGLM_MAX_GROUPS */
 
 int32_t ahmc_glm_aux_version(void);
 

@@ -4,7 +4,7 @@
 #include "ahmc_glm.hpp"
 
 #define AHMC_PROBE_HGLM(T)                                                                                                                  \
-  template __global__ void ahmc::k_hglm_coef<T>(const T*, const ahmc::HglmTab<T>*, T*, T*, int, int, int64_t, const int*);                  \
+  template __global__ void ahmc::k_hglm_coef<T>(const T*, const ahmc::HglmTab<T>*, T*, T*, int, int, int64_t, int64_t, const int*);         \
   template __global__ void ahmc::k_hglm_finish<T>(const T*, const T*, const T*, const T*, const T*, const ahmc::HglmTab<T>*, T*, T*, int, \
                                                   int, int, int64_t, int64_t, const int*, int);
 AHMC_PROBE_HGLM(double)

@@ -9,7 +9,7 @@ Julia ccalls == exported symbols; the new instantiations scratch-free; the const
 a host emulation, right and with two planted defects; the parity tests' precondition on the oracle alone.
 
 GPU: §1 values, §2 layout independence, §3 resume, §4 parity with the oracle, §5 a posterior against ask / tell, §6 dispersion and
-the legacy families, §7 refusals.
+the legacy families, the group table's two ends (no group, AHMC_GLM_AUX_MAX_GROUPS groups), §7 refusals.
 
 The bounds of §1.  u is the unit roundoff of the element type; ε_e, ε_l twice the measured worst relative errors of exp and log1p
 (test_glm_target.function_eps); m_L, m_Ψ twice the measured worst multiples of the special functions on the fixture grid:
@@ -666,7 +666,7 @@ def test_julia_ccalls_match_the_header():
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"), reason="needs llvm-objdump")
 def test_library_exports_and_kernels_without_scratch():
     """every entry point is in the dynamic symbol table (read without loading the library); the four new instantiations of k_glm_eta
-    and the finishing kernel are in the code object with no private segment and no VGPR spill (scripts/kernel_meta.py)"""
+    the finishing kernel and k_glm_exp_row are in the code object with no private segment and no VGPR spill (scripts/kernel_meta.py)"""
     from ahmc_amd import build as B
 
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
@@ -680,7 +680,7 @@ def test_library_exports_and_kernels_without_scratch():
     meta = kernel_meta.kernel_meta(B.OUT)
     names = subprocess.run(["c++filt"], input="\n".join(k["name"] for k in meta), capture_output=True, text=True, check=True).stdout.splitlines()
     want = [f"k_glm_eta<{t}, {f}, {bn}>" for t in ("float", "double") for f in (3, 4) for bn in (64, 16)]
-    want += [f"k_hglm_finish_aux<{t}>" for t in ("float", "double")]
+    want += [f"k_{w}<{t}>" for w in ("hglm_finish_aux", "glm_exp_row") for t in ("float", "double")]
     found = {}
     for k, dn in zip(meta, names):
         for w in want:
@@ -1179,6 +1179,65 @@ def test_dispersion_of_draws_and_legacy_families(hip, dtype):
     same = out["glm"][1] == out["mirror"][1]
     assert same.mean() >= 0.9, same.mean()
     np.testing.assert_allclose(out["glm"][0][:, same], out["mirror"][0][:, same], rtol=1e-8, atol=1e-8)
+
+
+# (P, groups) at the two ends of the group table, each with the row of s after it: no group at all, and AHMC_GLM_AUX_MAX_GROUPS
+# one-member groups [k, k + 1), centred and non-centred in turn, with two free coefficients after them
+EDGE_MODELS = ((3, ()), (33, tuple((k, k + 1, k % 2 == 0, 0.7 + 0.05 * k) for k in range(capi.GLM_AUX_MAX_GROUPS))))
+
+
+def edge_mirror(c):
+    """the numpy mirror at the case's θ: (β, τ, ℓπ, g = −∇ℓπ), the mirror's float64 rounded to the case's element type"""
+    th = c["th"].astype(np.float64)
+    t = aux_target(c)
+    W, tau = t.coefficients(th) if c["groups"] else (th[:-1].copy(), np.empty((0, th.shape[1])))
+    lp, grad = t.logdensity(th)
+    assert np.isfinite(lp).all() and np.isfinite(grad).all()
+    return tuple(np.asfortranarray(a, dtype=c["dtype"]) for a in (W, tau, lp, -grad))
+
+
+def edge_check(key, c, eps, W, tau, lp, g, phi=None):
+    """§1's bounds (aux_check; τ by test_glm_hier.hier_check) on β, τ, ℓπ and every row of g"""
+    assert W.shape == (c["P"], c["th"].shape[1]) and tau.shape == (len(c["groups"]), c["th"].shape[1])
+    aux_check(key, c, eps, W=W, phi=phi, lp=lp, g=g)
+    if c["groups"]:
+        with _patched(TH, "record_bound", record_bound):
+            TH.hier_check(key, dict(c, th=c["th_h"]), eps, tau=tau)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f64", "f32"])
+def test_mirror_takes_the_edge_models(dtype):
+    """the mirror accepts no group and the most groups the header admits; its ℓπ and gradient are finite at the generated θ and inside
+    §1's bounds of the long-double references, as the device's have to be (test_table_edges_on_the_device)"""
+    for P, groups in EDGE_MODELS:
+        c = acase(65, P, groups, 3, 5, np.dtype(dtype).name)
+        edge_check(f"edge-mirror {np.dtype(dtype).name} ({P}, {len(groups)})", c, mirror_eps(dtype), *edge_mirror(c))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f64", "f32"])
+def test_table_edges_on_the_device(hip, probe, probe_a, dtype):  # noqa: F811
+    """A dispersion's row after no group and after AHMC_GLM_AUX_MAX_GROUPS groups, N = 5 chains (a block serves four): β (P, 5) and
+    τ (G, 5) of ahmc_hglm_coefficients, ℓπ and every row of g of phasepoint() inside §1's bounds of the references that the mirror is
+    held to by test_mirror_takes_the_edge_models; glm_dispersion of the current θ, of host draws and of a device pointer the same
+    bits, within §6's 16 u of exp of the last row"""
+    eps = device_eps(probe, probe_a, dtype)
+    name = np.dtype(dtype).name
+    for P, groups in EDGE_MODELS:
+        c = acase(65, P, groups, 3, 5, name)
+        key = f"edge {name} ({P}, {len(groups)})"
+        e = aux_engine(hip, c)
+        z = e.phasepoint()
+        W, tau = e.hglm_coefficients()
+        phi = e.glm_dispersion()
+        edge_check(key, c, eps, W, tau, z.lp.value.copy(), z.lp.gradient.copy(), phi=phi)
+        if not groups:
+            record_bits(f"W {key}", W, np.asfortranarray(c["th"][:P]))
+        record_bits(f"dispersion-host-draws {key}", e.glm_dispersion(c["th"][:, 1:4]), phi[1:4])
+        th_d = TG.dev(c["th"])
+        record_bits(f"dispersion-device-draws {key}", e.glm_dispersion(int(th_d.data_ptr()), n_cols=5), phi)
+        np.testing.assert_allclose(phi.astype(np.float64), np.exp(c["th"][-1].astype(np.float64)), rtol=16 * float(U[np.dtype(dtype)]))
+        e.close()
 
 
 # ---- §7 ----

@@ -758,7 +758,7 @@ def test_new_kernels_on_a_chain_list(hip, probe_h, dtype):
 
     dtype = np.dtype(dtype)
     tch = TG.TCH[dtype]
-    coef = f"_ZN4ahmc11k_hglm_coefI{tch}EEvPKT_PKNS_7HglmTabIS1_EEPS1_S8_iilPKi"
+    coef = f"_ZN4ahmc11k_hglm_coefI{tch}EEvPKT_PKNS_7HglmTabIS1_EEPS1_S8_iillPKi"
     fin = f"_ZN4ahmc13k_hglm_finishI{tch}EEvPKT_S3_S3_S3_S3_PKNS_7HglmTabIS1_EEPS1_S8_iiillPKii"
     N = 300
     for n_obs, P, groups, fam in VALUE_CASES:
@@ -777,7 +777,7 @@ def test_new_kernels_on_a_chain_list(hip, probe_h, dtype):
             tau_d = torch.full((Gn * N,), float("nan"), dtype=th_d.dtype, device="cuda")
             lp_d = torch.full((N,), float("nan"), dtype=th_d.dtype, device="cuda")
             g_d = torch.full((D * N,), float("nan"), dtype=th_d.dtype, device="cuda")
-            probe_h.launch(coef, (n + 3) // 4, 256, th_d, tab_d, W_d, tau_d, int(P), int(Gn), np.int64(n), idx_d)
+            probe_h.launch(coef, (n + 3) // 4, 256, th_d, tab_d, W_d, tau_d, int(P), int(Gn), np.int64(D), np.int64(n), idx_d)
             if which == "list":  # (finish reads W of the listed columns only; give it the full W so that NaN in g can only be "not written")
                 W_in = TG.dev(out["all"][0])
             else:
