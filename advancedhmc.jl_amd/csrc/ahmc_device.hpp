@@ -427,7 +427,7 @@ __device__ __forceinline__ void wave_allsum2(T& a, T& b) {
 // stages, same order), but the two row_newbcast that would hand lanes 0 / 1 of the row to all 64 lanes are not made: after the xor-32
 // stage lane 0 already holds the final bits of Σa and lane 1 those of Σb, so one compare of that register and bits 0 / 1 of its lane
 // mask are the two decisions.  ONLY those two lanes: the in-row rotations associate the four quads' sums in a rotated order from quad
-// to quad ((Q0 + Q1) + (Q2 + Q3) in quad 0, (Q1 + Q2) + (Q3 + Q0) in quad 1), so another even lane may hold Σa rounded differently —
+// to quad ((Q0 + Q3) + (Q2 + Q1) in quad 0, (Q1 + Q0) + (Q3 + Q2) in quad 1: row_ror:n reads lane l − n), so another even lane may hold Σa rounded differently —
 // wave_allsum2 returns lane 0's and lane 1's bits, and so must this.  Rows need no care: xor16 / xor32 add {lower, upper} in the
 // same order on both sides.  NaN: `<=` is false, as in the two compares this replaces.
 // 0: wave_allsum2 + two compares, the form of rounds 1–6, for A/B runs.
@@ -475,6 +475,39 @@ __device__ __forceinline__ void wave_allsum4(T& a, T& b, T& c, T& d) {
   b = dpp_mov<0x151>(z);
   c = dpp_mov<0x152>(z);
   d = dpp_mov<0x153>(z);
+}
+
+// What a PAIR of consecutive NUTS leaves and their level-0 merge need from the wave, in ONE reduction (k_nuts, AHMC_LEAF_PAIR): the two
+// leaves' energies ea, eb (lane partials in, sums out, the same bits in every lane) and the generalised U-turn decision
+// Σda <= 0 || Σdb <= 0 of the merged pair as one wave-uniform predicate.  The lane exchanges are wave_allsum4<64>'s with (da, db) as its
+// first pair and (ea, eb) as its second:
+//   * lanes 0 / 1 of the transposed register hold Σda / Σdb with the bits of wave_allsum2<64> — the decision is the one
+//     wave64_any_le0_pair takes (one compare, bits 0 / 1 of its lane mask; no broadcast of the two sums);
+//   * lanes 4q + 2 / 4q + 3 hold Σea / Σeb.  The single-value butterfly wave_allsum<64, T, 1> joins the four quad sums of a row as
+//     (Q0 + Q1) + (Q2 + Q3); the two in-row rotations here join them as (Qq + Qq∓1) + (Qq∓2 + Qq∓3), which is that grouping (up to
+//     the order of the operands of an addition, which changes no bit) in every second quad only.  row_ror:n on gfx950 hands lane l the
+//     value of lane l − n — decided by the device probe (tests/device_probe/pair_red.hip), not by the manual — so the matching quads
+//     are 1 and 3, and the energies are broadcast from lanes 6 / 7 of the row.  AHMC_PAIR_RED_QUAD names the quad (the probe
+//     builds the other one as well).
+// f64: 14 + 7 + 3 + 3 + 5 + 5 + 1 + 4 = 42 VALU, against 22 + 22 + 27 for two leaves' wave_allsum and the merge's predicate.
+#ifndef AHMC_PAIR_RED_QUAD
+#define AHMC_PAIR_RED_QUAD 1
+#endif
+template <class T, int Q = AHMC_PAIR_RED_QUAD>
+__device__ __forceinline__ bool wave64_pair_reduce(T da, T db, T& ea, T& eb) {
+  static_assert(Q >= 0 && Q <= 3, "a row has four quads");
+  const bool odd = (threadIdx.x & 1u) != 0, up = (threadIdx.x & 2u) != 0;
+  const T x = (odd ? db : da) + dpp_mov<0xB1>(odd ? da : db);  // quad_perm [1,0,3,2]
+  const T y = (odd ? eb : ea) + dpp_mov<0xB1>(odd ? ea : eb);
+  T z = (up ? y : x) + dpp_mov<0x4E>(up ? x : y);              // quad_perm [2,3,0,1]
+  z += dpp_mov<0x124>(z);                                       // row_ror:4
+  z += dpp_mov<0x128>(z);                                       // row_ror:8
+  z = xor16_sum(z);
+  z = xor32_sum(z);
+  const bool le0 = (__builtin_amdgcn_ballot_w64(z <= T(0)) & 3ull) != 0ull;  // lane 0: Σda, lane 1: Σdb
+  ea = dpp_mov<0x150 + 4 * Q + 2>(z);  // row_newbcast
+  eb = dpp_mov<0x150 + 4 * Q + 3>(z);
+  return le0;
 }
 
 // all-reduce (sum) of K independent values across the G lanes of each group
@@ -896,6 +929,7 @@ __device__ __forceinline__ void leapfrog_step(Point<T, E>& z, const T (&minv)[E]
 // −Inf, src/hamiltonian.jl:95-104) is applied to the sum: sanitize(ℓπ) + sanitize(ℓκ) is −Inf exactly when either is
 // non-finite, and then ℓπ + ℓκ is non-finite too (the one exception, two finite values of ≈1e308 that overflow when
 // added, does not occur for a log-density).  Returns neg_energy; z.lp / z.lk are NOT updated.
+// (TWIN: leapfrog_step_ne_partial below repeats the vector work of this function for the pair step of k_nuts — change both)
 template <class T, int G, int E, int TK>
 __device__ __forceinline__ T leapfrog_step_ne(Point<T, E>& z, const T (&minv)[E], T eps, const TargetP<T>& tp, int lane, int d0) {
   const T eh = eps / 2;
@@ -912,6 +946,27 @@ __device__ __forceinline__ T leapfrog_step_ne(Point<T, E>& z, const T (&minv)[E]
   const T s = sv[0];
   return is_finite(s) ? s : -Lim<T>::inf();
 }
+
+// The vector work of leapfrog_step_ne alone (the same expressions): returns this lane's partial of ℓπ − ½ rᵀM⁻¹r, NOT reduced (the pair step of k_nuts
+// carries two leaves' partials through one reduction).
+// TWIN of leapfrog_step_ne above, line for line up to the reduction: change both.  (Two texts on purpose: with leapfrog_step_ne written as a call of this one AND
+// the leaf's scalar work of k_nuts in a shared lambda, the -DAHMC_LEAF_PAIR=0 build no longer had the parent's device code — 760 kernels differed; the
+// two rewrites were not tried one by one.  tests/test_leaf_pairs.py holds the twins together.)
+template <class T, int G, int E, int TK>
+__device__ __forceinline__ T leapfrog_step_ne_partial(Point<T, E>& z, const T (&minv)[E], T eps, const TargetP<T>& tp, int lane, int d0) {
+  const T eh = eps / 2;
+#pragma unroll
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
+#pragma unroll
+  for (int e = 0; e < E; ++e) z.th[e] = leapfrog_drift(z.th[e], eps, minv[e], z.r[e]);
+  const T part = target_eval<T, G, E, TK>(tp, z.th, z.g, lane, d0);
+#pragma unroll
+  for (int e = 0; e < E; ++e) z.r[e] = leapfrog_kick(z.r[e], eh, z.g[e]);
+  const T kin = kinetic_partial(z.r, minv);
+  return part - kin / 2;
+}
+template <class T>
+__device__ __forceinline__ T neg_energy_sanitized(T s) { return is_finite(s) ? s : -Lim<T>::inf(); }
 
 // leapfrog_step (untempered) that sums two more caller-supplied partials of the UPDATED point in the same all-reduce
 // as ℓπ and the kinetic energy: the NUTS kernels pass the two U-turn dot products of the merge that follows the

@@ -74,6 +74,25 @@
 
 #include "ahmc_kernels.hpp"
 
+// AHMC_LEAF_PAIR 1: where ONE chain owns ONE wave (G = 64) the fast kernels (MODE 0, 1, 3, 4) build the subtree of every doubling but
+// the first TWO LEAVES PER STEP.  Leaf 2k needs nothing from leaf 2k − 1's energy, so both leapfrogs' vector work runs first — the odd
+// leaf's r stays in registers: it is the level-0 pending half (ρ and first-built r are that one vector), which the single-leaf loop
+// parks in the level-0 slot and fetches back one leaf later — then ρ = r_a + r_b and the two U-turn dot products of the pair's level-0
+// merge, and ONE reduction carries all four numbers (ahmc_device.hpp: wave64_pair_reduce): two 22-instruction energy sums and the
+// merge's 27-instruction predicate become 42, one chain of six dependent stages instead of three.  The scalar work then runs in the
+// single-leaf loop's order — leaf a, leaf b, the merge's draw and select — so the tree draws are consumed in the same order and number;
+// if leaf a diverges nothing of leaf b is used (its leapfrog was speculative: at most once per transition).  Every number takes the
+// additions it takes in the single-leaf loop: the results are bit-identical (tests/test_leaf_pairs.py).
+// 0: the single-leaf loop everywhere, instruction for instruction (A/B runs).  The measurement builds keep the single-leaf loop: their
+// stage stamps describe it.
+#ifndef AHMC_LEAF_PAIR
+#define AHMC_LEAF_PAIR 1
+#endif
+#if AHMC_LEAF_PROF || AHMC_WAVE_TIMELINE
+#undef AHMC_LEAF_PAIR
+#define AHMC_LEAF_PAIR 0
+#endif
+
 namespace ahmc {
 
 constexpr double LINW_LIMIT = 600.0;  // exp(600)·2^10 leaves is still far from the Float64 overflow; Float32 uses 60
@@ -316,6 +335,10 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   // Round 7: a chain that owns ONE wave takes the generalised U-turn decision as a scalar predicate straight from the reduction
   // (ahmc_device.hpp: wave64_any_le0_pair).  G < 64 needs it per lane, G > 64 needs the sums themselves for the cross-wave exchange.
   constexpr bool UTURN_ANY = G == 64 && AHMC_UTURN_ANY != 0;
+  // two leaves per step (AHMC_LEAF_PAIR above).  Its reduction is the DPP butterfly's and its statistics are the running ones: the
+  // experimental reductions and the per-level statistics keep the single-leaf loop.
+  constexpr bool PAIR = AHMC_LEAF_PAIR != 0 && G == 64 && !GENERAL && UTURN_ANY && !AHMC_MFMA_REDUCE && (AHMC_DS_REDUCE & 3) == 0 &&
+                        AHMC_RUNNING_STATS != 0;
   const bool strict = GENERAL && p.criterion == 2;
   const int NV = strict ? 3 : 2;  // vectors per pending level: A, RF (, RL)
   const int n_slots = NV * NLEV + NUTS_DORMANT + NUTS_CKPT;
@@ -593,10 +616,85 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
         tl_alive += (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(alive && lane == 0));
 #endif
         int merged = 0;
+        // pair step (AHMC_LEAF_PAIR): from the second doubling on an iteration builds the odd leaf `leaf` AND the even leaf behind it with
+        // their level-0 merge; `leaf` is the even one from here on — its trailing zero bits are the merges that follow
+        bool pair = false;
+        if constexpr (PAIR) {
+          pair = jw > 0;
+          if (pair) ++leaf;
+        }
         // merges after this leaf: one per trailing zero bit of `leaf` (:649-673); the count is wave-uniform
         const int nm = __builtin_ctz(leaf);
         T dots_m0[2] = {0, 0}, RF_m0[E];  // fast kernels: U-turn dot products / first-built r of the FIRST merge
-        if (alive) {
+        if (pair) {
+          if constexpr (PAIR) {
+            // (a chain owns the wave: `alive` holds for the whole wave here, and every predicate below is wave-uniform)
+            const T es = v > 0 ? eps : -eps;
+            T ea = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+            T r_a[E];  // the level-0 pending half: ρ and first-built r of a one-leaf subtree are its r
+            copy_vec(r_a, cur.r);
+            T eb = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+            T dots[2] = {0, 0};  // the expressions of merge_level(0, …)
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+              A_c[e] = r_a[e] + cur.r[e];  // ρ = ρ_left + ρ_right
+              dots[0] += A_c[e] * (minv[e] * r_a[e]);
+              dots[1] += A_c[e] * (minv[e] * cur.r[e]);
+            }
+            const bool turn_ab = wave64_pair_reduce(dots[0], dots[1], ea, eb);
+            // a leaf's scalar work — weight, divergence test, running statistics, candidate = this leaf: the lines of the single-leaf
+            // form below that a fast kernel whose chain owns the wave executes, in their order.
+            // TWIN of the block from `pos_cur += v;` to the running statistics in the single-leaf arm below ("TWIN of leaf_stats"): a change to
+            // the leaf's scalar work is made in BOTH, or the first doubling's leaf (single-leaf arm) and the later ones (here) stop
+            // agreeing bit for bit — tests/test_leaf_pairs.py's fixture is what notices.  They are two texts, not one lambda, because with the
+            // single-leaf arm compiled through a shared lambda the -DAHMC_LEAF_PAIR=0 build no longer had the parent's device code (ahmc_device.hpp:
+            // leapfrog_step_ne_partial).
+            auto leaf_stats = [&](const T ne) {
+              pos_cur += v;
+              const T dH = -ne - H0;
+              T sa_leaf = 0;
+              if constexpr (!LINW) sa_leaf = alpha_from_logweight<T, true>(H0 + ne);
+              ck_c = pos_cur;
+              if constexpr (LINW) {
+                const T lw = H0 + ne;
+                w_c = leaf_weight_exp<true>(lw);
+                sa_leaf = w_c >= T(1) ? T(1) : w_c;
+                redo = redo || AHMC_UNI(lw > (sizeof(T) == 4 ? T(60) : T(LINW_LIMIT)));
+              } else {
+                w_c = H0 + ne;
+              }
+              sub_term = AHMC_UNI(!(-H0 < p.delta_max + ne));
+              numerical = numerical || sub_term;
+              sa_c = sa_c + sa_leaf;
+              na_c = na_c + 1;
+              if constexpr (AHMC_LEAF_MICRO) {
+                if (v > 0) { dh_c = maxabs(dh_c, dH); asm volatile(""); }
+                else { dh_c = maxabs(dH, dh_c); asm volatile(""); }
+              } else {
+                dh_c = v > 0 ? maxabs(dh_c, dH) : maxabs(dH, dh_c);
+              }
+            };
+            leaf_stats(neg_energy_sanitized(ea));
+            if (!sub_term) {
+              const T w_p = w_c;
+              const int ck_p = ck_c;
+              leaf_stats(neg_energy_sanitized(eb));
+              if (!sub_term) {
+                // the level-0 merge: combine(rng, sampler′, sampler′′) and the U-turn test of the pair, as merge_level does them
+                T w_new;
+                if constexpr (LINW) w_new = w_p + w_c; else w_new = logaddexp(w_p, w_c);
+                bool keep_first;
+                if constexpr (LINW) keep_first = AHMC_UNI((T)ds.uniform() * w_new < w_p); else keep_first = AHMC_UNI(w_new < w_p + (T)ds.randexp());
+                if (keep_first) ck_c = ck_p;
+                w_c = w_new;
+                sub_term = turn_ab;
+                copy_vec(RF_c, r_a);
+                merged = 1;
+                AHMC_LP_COUNT(9, 1)
+              }
+            }
+          }
+        } else if (alive) {
           // leaf: one leapfrog step in direction v (:638-647)
           T ne_leaf = 0;
           if constexpr (GENERAL) {
@@ -653,6 +751,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #if AHMC_LEAF_PROF
           if (GENERAL || G > 64) AHMC_LP_TICK(0)   // (the other leaf forms: the whole leapfrog incl. its reduction under [0])
 #endif
+          // (TWIN of leaf_stats in the pair step above: from here to the running statistics, the fast kernels' lines are repeated there — change both)
           pos_cur += v;
           const T ne = (GENERAL || (FUSE_M0 && nm > 0)) ? cur.lp + cur.lk : ne_leaf;  // neg_energy(z′)
           const T dH = -ne - H0;
@@ -819,7 +918,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           // lane, inside the leaf loop — cfg2 2.89e9 → 2.41e9, cfg3 2.49e9 → 2.25e9.)
           bool m = AHMC_UNI(alive && !sub_term);
           if (AHMC_ANY(m)) {
-            if (m) merge_level(0, cur.r, cur.r, std::bool_constant<FUSE_M0>{});
+            if (m && !pair) merge_level(0, cur.r, cur.r, std::bool_constant<FUSE_M0>{});  // (a pair step made its level-0 merge above)
             for (int lvl = 1; lvl < nm; ++lvl) {
               m = AHMC_UNI(alive && !sub_term);
               if (!AHMC_ANY(m)) break;
