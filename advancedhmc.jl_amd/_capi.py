@@ -232,6 +232,17 @@ GLM_AUX_SIGNATURES = {
     "ahmc_glm_dispersion": (_i32, [_vp, _vp, _i64, _vp]),
 }
 
+# include/ahmc_glm_factor.h: index-coded factors of the GLM target (likewise: the HIP engine only)
+AHMC_GLM_FACTOR_VERSION = 1
+GLM_FACTOR_MAX = 8
+GLM_FACTOR_SIGNATURES = {
+    "ahmc_glm_factor_version": (_i32, []),
+    "ahmc_glm_factor_set_target": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _pi32, _pi32, _pi32, C.POINTER(_f64), _i32, _pi32, _pi32, _i32,
+                                          _f64, _f64]),
+    "ahmc_glm_factor_get_target": (_i32, [_vp, C.POINTER(_i64), _pi32, _pi32]),
+}
+
+
 class CLib:
     """One loaded implementation of the ABI."""
 
@@ -315,6 +326,16 @@ class CLib:
             v = self.dll.ahmc_glm_aux_version()
             if v != AHMC_GLM_AUX_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm_aux version {v}, expected {AHMC_GLM_AUX_VERSION}")
+        # ahmc_glm_factor.h: likewise
+        gfac = [getattr(self.dll, name, None) for name in GLM_FACTOR_SIGNATURES]
+        self.has_glm_factor = all(fn is not None for fn in gfac)
+        if self.has_glm_factor:
+            for fn, (res, args) in zip(gfac, GLM_FACTOR_SIGNATURES.values()):
+                fn.restype = res
+                fn.argtypes = args
+            v = self.dll.ahmc_glm_factor_version()
+            if v != AHMC_GLM_FACTOR_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_factor version {v}, expected {AHMC_GLM_FACTOR_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

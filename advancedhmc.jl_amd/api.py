@@ -301,6 +301,30 @@ class KernelTarget:
     params: Optional[np.ndarray] = None
 
 
+class Factor:
+    """A grouping factor of a GLMTarget, index-coded (include/ahmc_glm_factor.h): `index[i]` ∈ [0, n_levels) is the level of observation
+    i (an integer array, zero-based); `n_levels` defaults to max + 1.  It stands for n_levels one-hot columns of X — one coefficient
+    per level — without storing or multiplying them."""
+
+    def __init__(self, index, n_levels=None):
+        try:
+            idx = np.asarray(index)
+            if idx.ndim != 1 or idx.size < 1:
+                raise ValueError(f"DimensionMismatch: a factor's index is one level per observation; got shape {idx.shape}")
+            (self.index, self.n_levels), = _glm.check_factors([(idx, n_levels)], idx.size)
+        except (ValueError, TypeError) as e:
+            raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+
+    def __repr__(self):
+        return f"Factor(n_obs={self.index.size}, n_levels={self.n_levels})"
+
+
+def factor_ranges(P_x, factors):
+    """[(start, stop)] of each factor's coefficient rows in a model with P_x dense columns — known before the target is constructed,
+    as in `CoefGroup(*A.factor_ranges(1, [fac])[0], centered=False)`"""
+    return _glm.factor_ranges(P_x, [f if isinstance(f, Factor) else Factor(*f) for f in factors])
+
+
 class GLMTarget:
     """A generalised linear model as the target (include/ahmc_glm.h; arithmetic: advancedhmc.jl_amd/glm.py):
         ℓπ(θ) = Σ_i ℓ(y_i, (Xθ + offset)_i) − ½ Σ_d p_d θ_d²,    X (n_obs, D), D = X.shape[1]
@@ -309,13 +333,16 @@ class GLMTarget:
     variance μ + μ²/φ).  θ then has one more row, LAST: s = log σ or log φ, with the prior s ~ Normal(*aux_prior) = (loc, scale),
     default (0, 1), and `.D` counts it; `.dispersion(θ)` gives σ or φ of draws.  The prior of the coefficients is
     N(0, prior_scale²) per coefficient — `prior_scale` a scalar or (D,) — or given as its precision `prior_prec`; neither: flat.
+    `factors` (at most 8 `Factor`s) add one coefficient per level after the columns of X: `.P_x` = X.shape[1] dense coefficients,
+    `.P` = P_x + Σ n_levels in all, `.factor_ranges` their rows; prior_scale / prior_prec then have P entries.
     The engine evaluates all chains at once, X·Θ and Xᵀ·U on the MFMA units.  HIP engine only (the CPU checker takes the same
     density as `ExternalTarget(D, lambda th: glm.logdensity(...))` or a host KernelTarget)."""
     kind = capi.TARGET_GLM
     params = None
     groups = ()
+    factors = ()
 
-    def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None):
+    def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None, factors=None):
         X = np.asarray(X, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64).ravel()
         if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.size != X.shape[0]:
@@ -337,12 +364,23 @@ class GLMTarget:
             raise ArgumentError(capi.ERR_ARGUMENT, str(e))
         self.X = np.asfortranarray(X)
         self.y = y
-        self.P = X.shape[1]
-        self.D = self.P + (1 if self.aux else 0)
         self.n_obs = X.shape[0]
+        try:
+            facs = [f if isinstance(f, Factor) else Factor(*f) for f in (factors or ())]
+            _glm.check_factors(facs, self.n_obs)
+        except (ValueError, TypeError) as e:
+            raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+        self.factors = tuple(facs)
+        self.P_x = X.shape[1]
+        self.factor_ranges = _glm.factor_ranges(self.P_x, self.factors)
+        self.P = self.P_x + sum(f.n_levels for f in self.factors)
+        self.D = self.P + (1 if self.aux else 0)
         if prior_scale is not None:
             prior_prec = 1.0 / np.square(np.asarray(prior_scale, dtype=np.float64))
-        self.prior_prec = None if prior_prec is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prior_prec, dtype=np.float64), (self.P,)))
+        try:
+            self.prior_prec = None if prior_prec is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prior_prec, dtype=np.float64), (self.P,)))
+        except ValueError:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: the prior has {np.size(prior_prec)} entries, the model P = {self.P} coefficients")
         self.offset = None if offset is None else np.asarray(offset, dtype=np.float64).ravel()
         if self.offset is not None and self.offset.size != self.n_obs:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: offset {self.offset.shape}, n_obs {self.n_obs}")
@@ -350,7 +388,8 @@ class GLMTarget:
 
     def logdensity(self, theta):
         """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
-        return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale, self.aux_prior)
+        return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale, self.aux_prior,
+                                    factors=self.factors)
 
     def dispersion(self, theta):
         """σ or φ = exp(s) of draws θ (D, n) by the numpy mirror (a family with a sampled dispersion)"""
@@ -375,12 +414,14 @@ class CoefGroup:
 
 class HierGLMTarget(GLMTarget):
     """A GLMTarget whose coefficient `groups` (CoefGroup, ascending and disjoint) each have a sampled prior scale
-    (include/ahmc_glm_hier.h; arithmetic: glm.hier_logdensity).  θ has D = P + G entries: the P = X.shape[1] coefficient parameters,
+    (include/ahmc_glm_hier.h; arithmetic: glm.hier_logdensity).  θ has D = P + G entries: the P coefficient parameters (X.shape[1], and
+    with `factors` their levels after them: a group may cover a factor's rows, `A.factor_ranges`),
     then log τ of each group.  `prior_scale` / `prior_prec` cover the coefficients in no group; on members they are forced to 0.
     `.coefficients(θ)` gives (β, τ) on the model's own scale.  HIP engine only."""
 
-    def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None):
-        super().__init__(X, y, family=family, prior_scale=prior_scale, prior_prec=prior_prec, offset=offset, scale=scale, aux_prior=aux_prior)
+    def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None, factors=None):
+        super().__init__(X, y, family=family, prior_scale=prior_scale, prior_prec=prior_prec, offset=offset, scale=scale, aux_prior=aux_prior,
+                         factors=factors)
         groups = [g if isinstance(g, CoefGroup) else CoefGroup(*g) for g in groups]
         try:
             _glm.check_groups(groups, self.P)
@@ -752,7 +793,9 @@ class Engine:
 
     def _set_glm(self, t):
         """bind a GLMTarget through the entry point of its kind: a sampled dispersion first, then coefficient groups, then the plain model"""
-        hier, G = isinstance(t, HierGLMTarget), len(t.groups)
+        hier, G, F = isinstance(t, HierGLMTarget), len(t.groups), len(t.factors)
+        if F:
+            self._need("has_glm_factor", "ahmc_glm_factor.h", f"{type(t).__name__}(factors=…)")
         if t.aux:
             self._need("has_glm_aux", "ahmc_glm_aux.h", f"GLMTarget(family={t.family})")
             model = f"the model has P + G + 1 = {t.P} + {G} + 1 parameters"
@@ -771,7 +814,12 @@ class Engine:
         data = (capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p))
         table = (G, (C.c_int32 * max(G, 1))(*[g.start for g in t.groups]), (C.c_int32 * max(G, 1))(*[g.stop for g in t.groups]),
                  (C.c_int32 * max(G, 1))(*[int(g.centered) for g in t.groups]), (C.c_double * max(G, 1))(*[g.scale for g in t.groups]))
-        if t.aux:
+        if F:
+            lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32)
+            aux = t.aux_prior if t.aux else (0.0, 1.0)
+            self._call("ahmc_glm_factor_set_target", int(t.family), int(t.n_obs), int(t.P_x), *data, float(t.scale), *table, F,
+                       (C.c_int32 * F)(*[f.n_levels for f in t.factors]), lev.ctypes.data_as(C.POINTER(C.c_int32)), int(t.aux), float(aux[0]), float(aux[1]))
+        elif t.aux:
             self._call("ahmc_glm_aux_set_target", int(t.family), int(t.n_obs), int(t.P), *data, *table, float(t.aux_prior[0]), float(t.aux_prior[1]))
         elif hier:
             self._call("ahmc_hglm_set_target", int(t.family), int(t.n_obs), int(t.P), *data, float(t.scale), *table)
@@ -811,6 +859,13 @@ class Engine:
         tau = np.empty((G.value, n), dtype=self.dtype, order="F")
         self._call("ahmc_hglm_coefficients", ptr, n, capi.as_ptr(beta) if beta.size else None, capi.as_ptr(tau) if tau.size else None)
         return beta, tau
+
+    def glm_factors(self):
+        """(P_x, [n_levels of each factor]) of the bound GLM: ahmc_glm_factor_get_target"""
+        self._need("has_glm_factor", "ahmc_glm_factor.h", "glm_factors")
+        Px, F, L = C.c_int64(), C.c_int32(), (C.c_int32 * capi.GLM_FACTOR_MAX)()
+        self._call("ahmc_glm_factor_get_target", C.byref(Px), C.byref(F), L)
+        return Px.value, [int(L[f]) for f in range(F.value)]
 
     def glm_pointwise(self):
         """(η, ℓ(y_i, η_i)) at the context's current θ, each (n_obs, N): ahmc_glm_pointwise"""

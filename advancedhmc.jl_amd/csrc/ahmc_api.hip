@@ -8,6 +8,7 @@
 #include "ahmc_glm.h"
 #include "ahmc_glm_hier.h"
 #include "ahmc_glm_aux.h"
+#include "ahmc_glm_factor.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -104,8 +105,10 @@ struct ExtRun {
 };
 
 // the bound model of AHMC_TARGET_GLM (ahmc_glm_host.hpp; {} = none).  One slab at buf: X, Xᵀ, y, offset, p [, a zero precision, the
-// group table], then the workspaces U, partial [, partial_s], gs [, W, R]; part i starts at off[i]; sizes 0 where the model has none
-enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PART_S, GLM_PARTS };
+// group table; the factor table, the level indices, the permutations by level and their row pointers], then the workspaces U,
+// partial [, partial_s], gs [, W, R]; part i starts at off[i]; sizes 0 where the model has none
+enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PART_S, GLM_FTAB, GLM_LEV, GLM_PERM, GLM_RP,
+       GLM_PARTS };
 template <class T>
 struct GlmModel {
   T* buf = nullptr;
@@ -114,7 +117,11 @@ struct GlmModel {
   int64_t n_obs = 0;
   bool has_offset = false;
   double scale = 1;
-  int64_t P = 0;  // the columns of X; θ has D = P + G (+ 1 with aux) rows, so P = D for a plain model
+  int64_t P = 0;  // the coefficient rows: the columns of X and the factors' levels; θ has D = P + G (+ 1 with aux) rows
+  int64_t Px = 0;  // the columns of X (= P without factors)
+  int F = 0;       // the factors (ahmc_glm_factor.h) and their levels; Lt = Σ levels = P − Px
+  int32_t L[GLM_MAX_FACTORS] = {};
+  int64_t Lt = 0;
   int G = 0;      // the coefficient groups (ahmc_glm_hier.h), as received
   int32_t lo[HGLM_MAX_GROUPS] = {}, hi[HGLM_MAX_GROUPS] = {}, centered[HGLM_MAX_GROUPS] = {};
   double A[HGLM_MAX_GROUPS] = {};
@@ -122,9 +129,11 @@ struct GlmModel {
   bool aux = false;         // θ ends with s, the log dispersion (ahmc_glm_aux.h); its prior Normal(aux_loc, aux_scale²)
   double aux_loc = 0, aux_scale = 1;
 
-  bool on_w() const { return G > 0 || aux; }  // the products run on the effective coefficients W, not on θ
+  bool on_w() const { return G > 0 || aux || F > 0; }  // the products run on the effective coefficients W, not on θ
   T* at(int part) const { return buf + off[part]; }
   const HglmTab<T>* tab() const { return reinterpret_cast<const HglmTab<T>*>(at(GLM_TAB)); }
+  const GlmFacTab* ftab() const { return reinterpret_cast<const GlmFacTab*>(at(GLM_FTAB)); }
+  const int* ints(int part) const { return reinterpret_cast<const int*>(at(part)); }
 };
 
 void comm_destroy_raw(void* comm);  // ncclCommDestroy through the run-time binding of ahmc_multi_host.hpp
@@ -2278,6 +2287,37 @@ int32_t ahmc_glm_aux_get_target(ahmc_ctx* ctx, double* aux_loc, double* aux_scal
 
 int32_t ahmc_glm_dispersion(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* out) {
   FOR_CTX_MUT(ctx, { return glm_dispersion(c, theta, n_cols, out); });
+}
+
+// ---- include/ahmc_glm_factor.h: index-coded factors instead of one-hot columns of X ----------------------------------------------------
+int32_t ahmc_glm_factor_version(void) { return AHMC_GLM_FACTOR_VERSION; }
+
+int32_t ahmc_glm_factor_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset,
+                                   const void* prior_prec, double scale, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
+                                   const double* hyper_scale, int32_t n_factors, const int32_t* n_levels, const int32_t* levels, int32_t has_aux,
+                                   double aux_loc, double aux_scale) {
+  FOR_CTX_MUT(ctx, {
+    HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale, has_aux != 0, aux_loc, aux_scale};
+    hs.F = (int)n_factors;
+    hs.Px = n_coef;
+    hs.n_levels = n_levels;
+    hs.levels = levels;
+    int rc = glm_factor_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset),
+                            static_cast<const T*>(prior_prec), has_aux ? 1.0 : scale, hs);
+    if (rc) return rc;
+    return dn_refresh_fused(c);
+  });
+}
+
+int32_t ahmc_glm_factor_get_target(ahmc_ctx* ctx, int64_t* n_coef, int32_t* n_factors, int32_t* n_levels) {
+  FOR_CTX(ctx, {
+    if (c->target_kind != AHMC_TARGET_GLM || !c->glm.buf) return fail(c, AHMC_ERR_ARGUMENT, "glm_factor_get_target: no GLM is bound");
+    if (n_coef) *n_coef = c->glm.Px;
+    if (n_factors) *n_factors = c->glm.F;
+    if (n_levels)
+      for (int f = 0; f < c->glm.F; ++f) n_levels[f] = c->glm.L[f];
+    return AHMC_OK;
+  });
 }
 
 }  // extern "C"

@@ -210,11 +210,24 @@ __device__ __forceinline__ void glm_link_aux(T y, T eta, T s, T cs, T& ll, T& u,
 // tile's 64 rows in ascending row order by one thread per column (rows past n_obs contribute +0).
 // FAM >= 3: the chain's log dispersion s is read from aux[col·aux_ld] (row D_θ − 1 of the chain's own θ, not of `th`, which holds the
 // effective coefficients), once per tile column, and Σ_rows ∂ℓ/∂s goes to partial_s[row block][chain] by the same column sum.
-template <class T, int FAM, int BN>
-__global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const T* __restrict__ y, const T* __restrict__ off, T scale, const T* __restrict__ th,
-                                                 T* __restrict__ U, T* __restrict__ partial, int n_obs, int D, int64_t ncols, int64_t N,
-                                                 const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out, const T* __restrict__ aux,
-                                                 int64_t aux_ld, T* __restrict__ partial_s) {
+//
+// FAC (include/ahmc_glm_factor.h): the product runs over the D dense columns only, `th` has column stride ldw (the model's P rows), and
+// before the link each element takes W[off_f + lev[row, f]] of its chain's column for f = 0, 1, … in this order: what the fma chain
+// would add for one-hot columns appended to X (fma(0, w, a) = a, fma(1, w, a) = a + w).
+constexpr int GLM_MAX_FACTORS = 8;
+
+struct GlmFacTab {  // the factor table, in the model's slab
+  int F;                      // factors
+  int off[GLM_MAX_FACTORS];   // the first coefficient row of factor f
+  int L[GLM_MAX_FACTORS];     // its levels
+};
+
+template <class T, int FAM, int BN, bool FAC>
+__device__ __forceinline__ void glm_eta_body(const T* __restrict__ X, const T* __restrict__ y, const T* __restrict__ off, T scale,
+                                             const T* __restrict__ th, T* __restrict__ U, T* __restrict__ partial, int n_obs, int D, int64_t ncols, int64_t N,
+                                             const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out, const T* __restrict__ aux,
+                                             int64_t aux_ld, T* __restrict__ partial_s, int64_t ldw, const GlmFacTab* __restrict__ ft,
+                                             const int* __restrict__ lev) {
   using S = GlmShape<BN>;
   using Mf = Mfma<T>;
   __shared__ T smem[S::SMEM];
@@ -234,7 +247,7 @@ __global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const 
   {
     const int bn = tid / (GB_K / S::BE);
     const int64_t bcol = n0 + bn < ncols ? (idx ? (int64_t)idx[n0 + bn] : n0 + bn) : -1;
-    glm_tile_product<T, BN>(X, (int64_t)n_obs, n_obs, m0, bcol >= 0 ? th + bcol * D : nullptr, 0, D, smem, acc);
+    glm_tile_product<T, BN>(X, (int64_t)n_obs, n_obs, m0, bcol >= 0 ? th + bcol * ldw : nullptr, 0, D, smem, acc);
   }
   const int wm = (w % S::WR) * 16 * S::MI, wn = (w / S::WR) * 16 * S::MI;
   T ll[S::MI][S::MI][4];
@@ -265,7 +278,13 @@ __global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const 
         T l = T(0), u = T(0);
         [[maybe_unused]] T dl = T(0);
         if (row < n_obs && col >= 0) {
-          const T eta = off ? acc[ti][tj][v] + off[row] : acc[ti][tj][v];
+          T eta = acc[ti][tj][v];
+          if constexpr (FAC) {
+            const T* wc = th + col * ldw;
+            const int F = ft->F;
+            for (int f = 0; f < F; ++f) eta += wc[ft->off[f] + lev[row + (int64_t)f * n_obs]];
+          }
+          if (off) eta += off[row];
           if constexpr (FAM >= 3) glm_link_aux<T, FAM>(y[row], eta, sv[tj], cv[tj], l, u, dl);
           else glm_link<T, FAM>(y[row], eta, scale, l, u);
           if (eta_out) eta_out[row + col * n_obs] = eta;
@@ -318,13 +337,32 @@ __global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const 
   }
 }
 
+template <class T, int FAM, int BN>
+__global__ __launch_bounds__(256) void k_glm_eta(const T* __restrict__ X, const T* __restrict__ y, const T* __restrict__ off, T scale, const T* __restrict__ th,
+                                                 T* __restrict__ U, T* __restrict__ partial, int n_obs, int D, int64_t ncols, int64_t N,
+                                                 const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out, const T* __restrict__ aux,
+                                                 int64_t aux_ld, T* __restrict__ partial_s) {
+  glm_eta_body<T, FAM, BN, false>(X, y, off, scale, th, U, partial, n_obs, D, ncols, N, idx, eta_out, ll_out, aux, aux_ld, partial_s, (int64_t)D,
+                                  (const GlmFacTab*)nullptr, (const int*)nullptr);
+}
+
+// k_glm_eta for a model with factors: X (n_obs, Px), W with column stride P, the level indices lev (n_obs, F) column-major
+template <class T, int FAM, int BN>
+__global__ __launch_bounds__(256) void k_glm_eta_f(const T* __restrict__ X, const T* __restrict__ y, const T* __restrict__ off, T scale, const T* __restrict__ W,
+                                                   T* __restrict__ U, T* __restrict__ partial, int n_obs, int Px, int64_t P, int64_t ncols, int64_t N,
+                                                   const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out, const T* __restrict__ aux,
+                                                   int64_t aux_ld, T* __restrict__ partial_s, const GlmFacTab* __restrict__ ft, const int* __restrict__ lev) {
+  glm_eta_body<T, FAM, BN, true>(X, y, off, scale, W, U, partial, n_obs, Px, ncols, N, idx, eta_out, ll_out, aux, aux_ld, partial_s, P, ft, lev);
+}
+
 // Xᵀ·U for the listed chains.  Tile rows are coefficients, tile columns chains, K = the workgroup's slice of the observations; the
 // A operand is the transposed copy Xt (D, n_obs) made when the target was set.  One slice (n_obs <= GLM_K_SLICE): the epilogue
 // writes g = −acc + p∘θ to the chain's column of g.  More: the slice's sum goes to gs[slice][chain][d] and k_glm_gsum finishes.
+// ldg: the column stride of th and g (D; the model's P when the D dense rows are the first of P: k_glm_grad_ld).
 template <class T, int BN>
-__global__ __launch_bounds__(256) void k_glm_grad(const T* __restrict__ Xt, const T* __restrict__ U, const T* __restrict__ prec, const T* __restrict__ th,
-                                                  T* __restrict__ g, T* __restrict__ gs, int n_obs, int D, int64_t ncols, int64_t N,
-                                                  const int* __restrict__ idx, int n_slices) {
+__device__ __forceinline__ void glm_grad_body(const T* __restrict__ Xt, const T* __restrict__ U, const T* __restrict__ prec,
+                                              const T* __restrict__ th, T* __restrict__ g, T* __restrict__ gs, int n_obs, int D, int64_t ncols, int64_t N,
+                                              const int* __restrict__ idx, int n_slices, int64_t ldg) {
   using S = GlmShape<BN>;
   using Mf = Mfma<T>;
   __shared__ T smem[S::SMEM];
@@ -358,24 +396,83 @@ __global__ __launch_bounds__(256) void k_glm_grad(const T* __restrict__ Xt, cons
       for (int v = 0; v < 4; ++v) {
         const int row = m0 + wm + ti * 16 + Mf::row(lane, v);
         if (row < D && col >= 0) {
-          if (n_slices == 1) g[row + col * D] = fma(prec[row], th[row + col * D], -acc[ti][tj][v]);
+          if (n_slices == 1) g[row + col * ldg] = fma(prec[row], th[row + col * ldg], -acc[ti][tj][v]);
           else gs[((int64_t)slice * N + col) * D + row] = acc[ti][tj][v];
         }
       }
     }
 }
 
-// g = −(Σ_slices gs, ascending) + p∘θ for the listed chains (n_slices > 1)
+template <class T, int BN>
+__global__ __launch_bounds__(256) void k_glm_grad(const T* __restrict__ Xt, const T* __restrict__ U, const T* __restrict__ prec, const T* __restrict__ th,
+                                                  T* __restrict__ g, T* __restrict__ gs, int n_obs, int D, int64_t ncols, int64_t N,
+                                                  const int* __restrict__ idx, int n_slices) {
+  glm_grad_body<T, BN>(Xt, U, prec, th, g, gs, n_obs, D, ncols, N, idx, n_slices, (int64_t)D);
+}
+
+// k_glm_grad over the Px dense columns of a model with factors: rows [0, Px) of R, whose column stride (and W's) is P
+template <class T, int BN>
+__global__ __launch_bounds__(256) void k_glm_grad_ld(const T* __restrict__ Xt, const T* __restrict__ U, const T* __restrict__ prec, const T* __restrict__ W,
+                                                     T* __restrict__ R, T* __restrict__ gs, int n_obs, int Px, int64_t P, int64_t ncols, int64_t N,
+                                                     const int* __restrict__ idx, int n_slices) {
+  glm_grad_body<T, BN>(Xt, U, prec, W, R, gs, n_obs, Px, ncols, N, idx, n_slices, P);
+}
+
+// g = −(Σ_slices gs, ascending) + p∘θ for the listed chains (n_slices > 1); th and g have the column stride ldg
 template <class T>
-__global__ __launch_bounds__(256) void k_glm_gsum(const T* __restrict__ gs, const T* __restrict__ prec, const T* __restrict__ th, T* __restrict__ g, int D,
-                                                  int64_t ncols, int64_t N, const int* __restrict__ idx, int n_slices) {
+__device__ __forceinline__ void glm_gsum_body(const T* __restrict__ gs, const T* __restrict__ prec, const T* __restrict__ th, T* __restrict__ g, int D,
+                                              int64_t ncols, int64_t N, const int* __restrict__ idx, int n_slices, int64_t ldg) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ncols * D) return;
   const int64_t j = i / D, col = idx ? (int64_t)idx[j] : j;
   const int d = (int)(i % D);
   T s = gs[col * D + d];
   for (int sl = 1; sl < n_slices; ++sl) s += gs[((int64_t)sl * N + col) * D + d];
-  g[d + col * D] = fma(prec[d], th[d + col * D], -s);
+  g[d + col * ldg] = fma(prec[d], th[d + col * ldg], -s);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_glm_gsum(const T* __restrict__ gs, const T* __restrict__ prec, const T* __restrict__ th, T* __restrict__ g, int D,
+                                                  int64_t ncols, int64_t N, const int* __restrict__ idx, int n_slices) {
+  glm_gsum_body<T>(gs, prec, th, g, D, ncols, N, idx, n_slices, (int64_t)D);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_glm_gsum_ld(const T* __restrict__ gs, const T* __restrict__ prec, const T* __restrict__ W, T* __restrict__ R, int Px,
+                                                     int64_t P, int64_t ncols, int64_t N, const int* __restrict__ idx, int n_slices) {
+  glm_gsum_body<T>(gs, prec, W, R, Px, ncols, N, idx, n_slices, P);
+}
+
+// The factor rows of R = −Xᵀu for the listed chains, without the one-hot columns: row Px + q of R is level q of the factors' levels
+// taken together (factor 0's first).  perm lists, level after level, the observations of the level in ascending order (the stable
+// permutation by level made when the target was set; rp[q] .. rp[q + 1] is level q's stretch).  One thread per (chain, level) walks
+// its stretch: within a slice of GLM_K_SLICE observations u is summed in ascending order from +0, the slice sums are added in
+// ascending order — the fma chain of a one-hot column and k_glm_gsum's order (a slice without a member adds +0: no change).  A
+// chain's column of U is read once and stays in L2 meanwhile; consecutive lanes write consecutive rows of R.  An empty level writes
+// a zero.  No atomics, no workspace.
+template <class T>
+__global__ __launch_bounds__(256) void k_glm_fgrad(const T* __restrict__ U, const int* __restrict__ perm, const int* __restrict__ rp, T* __restrict__ R, int n_obs,
+                                                   int Px, int Lt, int64_t P, int64_t ncols, const int* __restrict__ idx) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ncols * Lt) return;
+  const int64_t j = t / Lt, c = idx ? (int64_t)idx[j] : j;
+  const int q = (int)(t % Lt);
+  const T* u = U + c * n_obs;
+  T tot = T(0), s = T(0);
+  int sl = 0;
+  const int k1 = rp[q + 1];
+  for (int k = rp[q]; k < k1; ++k) {
+    const int i = perm[k];
+    const int si = i / GLM_K_SLICE;
+    if (si != sl) {
+      tot += s;
+      s = T(0);
+      sl = si;
+    }
+    s += u[i];
+  }
+  tot += s;
+  R[(int64_t)Px + q + c * P] = -tot;
 }
 
 // ℓπ = Σ_row blocks partial − ½ Σ_d p_d θ_d², one wave per chain (as k_d_coldot): lane l sums the row blocks and the coefficients

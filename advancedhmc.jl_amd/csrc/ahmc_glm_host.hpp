@@ -18,6 +18,10 @@ struct HglmSpec {
   const double* A;
   bool aux = false;  // ahmc_glm_aux_set_target: θ ends with s, the log dispersion, with the prior Normal(aux_loc, aux_scale²)
   double aux_loc = 0, aux_scale = 1;
+  // ahmc_glm_factor_set_target: P = Px + Σ n_levels; levels (n_obs, F) column-major, zero-based (host memory)
+  int F = 0;
+  int64_t Px = 0;
+  const int32_t *n_levels = nullptr, *levels = nullptr;
 };
 
 inline bool glm_aux_family(int family) { return family == AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA || family == AHMC_GLM_NEGBINOMIAL_LOG; }
@@ -37,7 +41,8 @@ int glm_release(Ctx<T>* c) {
   return AHMC_OK;
 }
 
-// η (and from it U, partial; on request η and ℓ themselves) for ncols listed chains; th: the coefficients, (D, N) with column stride D
+// η (and from it U, partial; on request η and ℓ themselves) for ncols listed chains; th: the coefficients, (D, N) with column stride D.
+// A model with factors: the product over its Px dense columns, the factors' rows of th gathered in the epilogue (k_glm_eta_f).
 template <class T>
 int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols, bool small, T* eta_out, T* ll_out) {
   const GlmModel<T>& m = c->glm;
@@ -55,6 +60,28 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
   const dim3 grid = small ? dim3((unsigned)nrb, (unsigned)((ncols + 15) / 16)) : dim3((unsigned)(nrb * (((ncols + GB_N - 1) / GB_N + 7) / 8 * 8)));
 #define AHMC_GLM_ETA(FAM, BN) \
   hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)m.scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out, aux, (int64_t)c->D, part_s)
+#define AHMC_GLM_ETA_F(FAM, BN)                                                                                                                          \
+  hipLaunchKernelGGL((k_glm_eta_f<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)m.scale, th, U, part, n_obs, (int)m.Px, (int64_t)D, ncols, c->N, list, \
+                     eta_out, ll_out, aux, (int64_t)c->D, part_s, m.ftab(), m.ints(GLM_LEV))
+  if (m.F > 0) {
+    if (D != m.P) return fail(c, AHMC_ERR_STATE, "glm: a model with factors runs on its P rows of W");
+    switch (m.family * 2 + (small ? 1 : 0)) {
+      case 0: AHMC_GLM_ETA_F(0, 64); break;
+      case 1: AHMC_GLM_ETA_F(0, 16); break;
+      case 2: AHMC_GLM_ETA_F(1, 64); break;
+      case 3: AHMC_GLM_ETA_F(1, 16); break;
+      case 4: AHMC_GLM_ETA_F(2, 64); break;
+      case 5: AHMC_GLM_ETA_F(2, 16); break;
+      case 6: AHMC_GLM_ETA_F(3, 64); break;
+      case 7: AHMC_GLM_ETA_F(3, 16); break;
+      case 8: AHMC_GLM_ETA_F(4, 64); break;
+      case 9: AHMC_GLM_ETA_F(4, 16); break;
+      default: return fail(c, AHMC_ERR_STATE, "glm: unknown family in the context");
+    }
+    HIPCHK(hipGetLastError());
+    return AHMC_OK;
+  }
+#undef AHMC_GLM_ETA_F
   switch (m.family * 2 + (small ? 1 : 0)) {
     case 0: AHMC_GLM_ETA(0, 64); break;
     case 1: AHMC_GLM_ETA(0, 16); break;
@@ -94,8 +121,9 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   // groups or a dispersion bound: the products run on the effective coefficients W (P, N) with a zero precision and leave
   // R = −Xᵀu; k_hglm_coef before them and k_hglm_finish after them are the model (ahmc_glm.hpp)
   const bool hier = m.on_w();
-  const int n_obs = (int)m.n_obs, D = (int)m.P, G = m.G, ns = glm_slices(c);
-  const int64_t nrb = (n_obs + GB_M - 1) / GB_M, nrbD = (int64_t)(D + GB_M - 1) / GB_M * ns;
+  // factors: the dense product covers rows [0, Px) of R, k_glm_fgrad the factors' rows; W and R keep the column stride P
+  const int n_obs = (int)m.n_obs, D = (int)m.P, Px = (int)m.Px, G = m.G, ns = glm_slices(c);
+  const int64_t nrb = (n_obs + GB_M - 1) / GB_M, nrbD = (int64_t)(Px + GB_M - 1) / GB_M * ns;
   const T* th = hier ? m.at(GLM_W) : (const T*)c->th;
   const T* prec = m.at(hier ? GLM_ZERO : GLM_PREC);
   T* g = hier ? m.at(GLM_R) : c->g;
@@ -105,14 +133,25 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   const T* Xt = m.at(GLM_XT);
   const T* U = m.at(GLM_U);
   T* gs = m.at(GLM_GS);
-  if (glm_small(c, nrbD, n))
-    hipLaunchKernelGGL((k_glm_grad<T, 16>), dim3((unsigned)nrbD, (unsigned)((n + 15) / 16)), dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, D, n, c->N,
-                       list, ns);
-  else
-    hipLaunchKernelGGL((k_glm_grad<T, 64>), dim3((unsigned)(nrbD * (((n + GB_N - 1) / GB_N + 7) / 8 * 8))), dim3(256), 0, c->stream, Xt, U, prec, th, g, gs,
-                       n_obs, D, n, c->N, list, ns);
-  if (ns > 1)
-    hipLaunchKernelGGL((k_glm_gsum<T>), dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, th, g, D, n, c->N, list, ns);
+  const dim3 grid16((unsigned)nrbD, (unsigned)((n + 15) / 16)), grid64((unsigned)(nrbD * (((n + GB_N - 1) / GB_N + 7) / 8 * 8)));
+  if (m.F > 0) {
+    if (glm_small(c, nrbD, n))
+      hipLaunchKernelGGL((k_glm_grad_ld<T, 16>), grid16, dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, Px, (int64_t)D, n, c->N, list, ns);
+    else
+      hipLaunchKernelGGL((k_glm_grad_ld<T, 64>), grid64, dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, Px, (int64_t)D, n, c->N, list, ns);
+    if (ns > 1)
+      hipLaunchKernelGGL((k_glm_gsum_ld<T>), dim3((unsigned)((n * Px + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, th, g, Px, (int64_t)D, n, c->N,
+                         list, ns);
+    hipLaunchKernelGGL((k_glm_fgrad<T>), dim3((unsigned)((n * m.Lt + 255) / 256)), dim3(256), 0, c->stream, U, m.ints(GLM_PERM), m.ints(GLM_RP), g, n_obs, Px,
+                       (int)m.Lt, (int64_t)D, n, list);
+  } else {
+    if (glm_small(c, nrbD, n))
+      hipLaunchKernelGGL((k_glm_grad<T, 16>), grid16, dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, D, n, c->N, list, ns);
+    else
+      hipLaunchKernelGGL((k_glm_grad<T, 64>), grid64, dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, D, n, c->N, list, ns);
+    if (ns > 1)
+      hipLaunchKernelGGL((k_glm_gsum<T>), dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, th, g, D, n, c->N, list, ns);
+  }
   if (m.aux)
     hipLaunchKernelGGL((k_hglm_finish_aux<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)m.at(GLM_PART), (const T*)m.at(GLM_PART_S),
                        (const T*)g, th, (const T*)m.at(GLM_PREC), (const T*)c->th, m.tab(), c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0,
@@ -130,8 +169,10 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
 template <class T>
 int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, const HglmSpec* hs = nullptr) {
   const int G = hs ? hs->G : 0;
-  const bool aux = hs && hs->aux, on_w = G > 0 || aux;
-  const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the columns of X: the record's P)
+  const bool aux = hs && hs->aux, on_w = G > 0 || aux || (hs && hs->F > 0);
+  const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the coefficient rows: the record's P)
+  const int F = hs ? hs->F : 0;
+  const int64_t Px = F > 0 ? hs->Px : D, Lt = D - Px;  // (the columns of X; the factors' levels together)
   if (glm_aux_family(family) && !aux)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family) +
                                           " at this entry point: it samples its dispersion and is bound through ahmc_glm_aux_set_target (include/ahmc_glm_aux.h)");
@@ -149,13 +190,20 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   // the slab: X, Xᵀ, y, offset, p [, a zero precision, the group table], then the workspaces U, partial [, partial_s], gs [, W, R]
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, ns = (n_obs + GLM_K_SLICE - 1) / GLM_K_SLICE;
   const int64_t tab_elems = (int64_t)((sizeof(HglmTab<T>) + sizeof(T) - 1) / sizeof(T));
-  int64_t sizes[GLM_PARTS] = {n_obs * D, n_obs * D, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * D * N : 0, 0, 0, 0, 0, aux ? nrb * N : 0};
+  int64_t sizes[GLM_PARTS] = {n_obs * Px, n_obs * Px, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * Px * N : 0, 0, 0, 0, 0, aux ? nrb * N : 0, 0, 0, 0, 0};
   if (on_w) {
     sizes[GLM_W] = sizes[GLM_R] = D * N;
     sizes[GLM_ZERO] = D;
     sizes[GLM_TAB] = tab_elems;
   }
-  const int layout[GLM_PARTS] = {GLM_X, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_ZERO, GLM_TAB, GLM_U, GLM_PART, GLM_PART_S, GLM_GS, GLM_W, GLM_R};
+  const auto int_elems = [](int64_t n_ints) { return (int64_t)((n_ints * sizeof(int) + sizeof(T) - 1) / sizeof(T)); };  // int32 parts, in elements
+  if (F > 0) {
+    sizes[GLM_FTAB] = int_elems((int64_t)(sizeof(GlmFacTab) / sizeof(int)));
+    sizes[GLM_LEV] = sizes[GLM_PERM] = int_elems(n_obs * F);
+    sizes[GLM_RP] = int_elems(Lt + 1);
+  }
+  const int layout[GLM_PARTS] = {GLM_X,   GLM_XT, GLM_Y,    GLM_OFF,    GLM_PREC, GLM_ZERO, GLM_TAB, GLM_FTAB, GLM_LEV,
+                                 GLM_PERM, GLM_RP, GLM_U,    GLM_PART,   GLM_PART_S, GLM_GS,  GLM_W,   GLM_R};
   GlmModel<T> m;  // (becomes the context's once nothing can fail any more)
   int64_t* const off = m.off;
   int64_t total = 0;
@@ -165,12 +213,12 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   }
   const int64_t n_data = off[GLM_U];
   std::vector<T> h((size_t)n_data, T(0));
-  HIPCHK(hipMemcpy(h.data() + off[GLM_X], X, sizeof(T) * n_obs * D, hipMemcpyDefault));
+  HIPCHK(hipMemcpy(h.data() + off[GLM_X], X, sizeof(T) * n_obs * Px, hipMemcpyDefault));
   HIPCHK(hipMemcpy(h.data() + off[GLM_Y], y, sizeof(T) * n_obs, hipMemcpyDefault));
   if (offset) HIPCHK(hipMemcpy(h.data() + off[GLM_OFF], offset, sizeof(T) * n_obs, hipMemcpyDefault));
   if (prec) HIPCHK(hipMemcpy(h.data() + off[GLM_PREC], prec, sizeof(T) * D, hipMemcpyDefault));
   const T* hX = h.data() + off[GLM_X];
-  for (int64_t i = 0; i < n_obs * D; ++i)
+  for (int64_t i = 0; i < n_obs * Px; ++i)
     if (!std::isfinite((double)hX[i])) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: X holds a non-finite value");
   for (int64_t i = 0; i < n_obs; ++i) {
     const double yi = (double)h[off[GLM_Y] + i];
@@ -201,14 +249,42 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
     memcpy(h.data() + off[GLM_TAB], &tab, sizeof(tab));
   }
   T* hXt = h.data() + off[GLM_XT];
-  for (int64_t d = 0; d < D; ++d)
-    for (int64_t i = 0; i < n_obs; ++i) hXt[d + i * D] = hX[i + d * n_obs];
+  for (int64_t d = 0; d < Px; ++d)
+    for (int64_t i = 0; i < n_obs; ++i) hXt[d + i * Px] = hX[i + d * n_obs];
+  if (F > 0) {
+    // the factor table, the level indices as received (checked by glm_factor_set), and per factor the stable permutation of the
+    // observations by level (a counting sort: ascending observations within a level) with the row pointers of all levels together
+    GlmFacTab ft{};
+    int* lev = reinterpret_cast<int*>(h.data() + off[GLM_LEV]);
+    int* perm = reinterpret_cast<int*>(h.data() + off[GLM_PERM]);
+    int* rp = reinterpret_cast<int*>(h.data() + off[GLM_RP]);
+    ft.F = F;
+    int64_t row = Px, q0 = 0;
+    for (int f = 0; f < F; ++f) {
+      const int Lf = hs->n_levels[f];
+      ft.off[f] = (int)row;
+      ft.L[f] = m.L[f] = Lf;
+      const int32_t* lf = hs->levels + (int64_t)f * n_obs;
+      std::vector<int64_t> cnt((size_t)Lf + 1, 0);
+      for (int64_t i = 0; i < n_obs; ++i) {
+        lev[i + f * n_obs] = lf[i];
+        ++cnt[(size_t)lf[i] + 1];
+      }
+      for (int l = 0; l < Lf; ++l) cnt[(size_t)l + 1] += cnt[(size_t)l];
+      for (int l = 0; l <= Lf; ++l) rp[q0 + l] = (int)((int64_t)f * n_obs + cnt[(size_t)l]);
+      for (int64_t i = 0; i < n_obs; ++i) perm[(int64_t)f * n_obs + cnt[(size_t)lf[i]]++] = (int)i;
+      row += Lf;
+      q0 += Lf;
+    }
+    memcpy(h.data() + off[GLM_FTAB], &ft, sizeof(ft));
+  }
   // everything that can fail happens before the previous target is touched
   if (hipMalloc(reinterpret_cast<void**>(&m.buf), sizeof(T) * (size_t)total) != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, AHMC_ERR_RUNTIME, "set_target_glm: cannot allocate " + std::to_string((long long)(sizeof(T) * (size_t)total)) + " bytes for the model (" +
                                          std::to_string((long long)(sizeof(T) * (size_t)n_data)) + ") and its workspaces U (n_obs × N), partial and the slice sums" +
-                                         (on_w ? ", W and R (n_coef × N)" : "") + (aux ? ", partial_s" : ""));
+                                         (on_w ? ", W and R (n_coef × N)" : "") + (aux ? ", partial_s" : "") +
+                                         (F > 0 ? "; the model holds the level indices, permutations and row pointers of " + std::to_string(F) + " factors" : ""));
   }
   if (hipMemcpy(m.buf, h.data(), sizeof(T) * (size_t)n_data, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
     (void)hipFree(m.buf);
@@ -221,6 +297,9 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   m.has_offset = offset != nullptr;
   m.scale = scale;
   m.P = D;
+  m.Px = Px;
+  m.F = F;
+  m.Lt = Lt;
   m.G = G;
   m.bound_hier = hs != nullptr;
   m.aux = aux;
@@ -276,7 +355,8 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const
                                              std::to_string(AHMC_HGLM_MAX_GROUPS));
   if (n_coef < 1 || c->D != n_coef + n_groups + (aux ? 1 : 0))
     return fail(c, AHMC_ERR_ARGUMENT, "DimensionMismatch: the context has D = " + std::to_string((long long)c->D) + ", the model n_coef + n_groups = " +
-                                          std::to_string((long long)n_coef) + " + " + std::to_string(n_groups) + (aux ? " (+ 1: the dispersion's row)" : ""));
+                                          std::to_string((long long)n_coef) + " + " + std::to_string(n_groups) + (aux ? " (+ 1: the dispersion's row)" : "") +
+                                          (hs.F > 0 ? " (n_coef: " + std::to_string((long long)hs.Px) + " columns of X and the factors' levels)" : ""));
   if (aux && !std::isfinite(hs.aux_loc)) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_loc = " + std::to_string(hs.aux_loc) + " must be finite");
   if (aux && !(std::isfinite(hs.aux_scale) && hs.aux_scale > 0))
     return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_scale = " + std::to_string(hs.aux_scale) + " must be finite and > 0");
@@ -293,6 +373,40 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const
     prev = hi;
   }
   return glm_set(c, family, n_obs, X, y, offset, prec, scale, &hs);
+}
+
+// ---- include/ahmc_glm_factor.h ----
+// hs.Px, hs.F, hs.n_levels, hs.levels as received; hs.P is filled in here (Px + Σ levels), then hglm_set checks the groups against it
+template <class T>
+int glm_factor_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, HglmSpec hs) {
+  const int F = hs.F;
+  if (F < 0) return fail(c, AHMC_ERR_ARGUMENT, "glm_factor_set_target: n_factors must be >= 0; got " + std::to_string(F));
+  if (F > AHMC_GLM_FACTOR_MAX)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "glm_factor_set_target: n_factors = " + std::to_string(F) + " is beyond the engine's limit AHMC_GLM_FACTOR_MAX = " +
+                                             std::to_string(AHMC_GLM_FACTOR_MAX));
+  if (hs.Px < 1)
+    return fail(c, AHMC_ERR_ARGUMENT, "DimensionMismatch: X must keep at least one dense column; n_coef = " + std::to_string((long long)hs.Px));
+  if (n_obs < 1) return fail(c, AHMC_ERR_ARGUMENT, "glm_factor_set_target: n_obs must be >= 1; got " + std::to_string(n_obs));
+  if (n_obs > AHMC_GLM_MAX_OBS)  // (before the level indices are read)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "glm_factor_set_target: n_obs = " + std::to_string(n_obs) + " is beyond the engine's limit AHMC_GLM_MAX_OBS = " +
+                                             std::to_string((long long)AHMC_GLM_MAX_OBS));
+  if (F > 0 && (!hs.n_levels || !hs.levels)) return fail(c, AHMC_ERR_ARGUMENT, "glm_factor_set_target: n_levels or levels is NULL");
+  int64_t P = hs.Px;
+  for (int f = 0; f < F; ++f) {
+    const int32_t Lf = hs.n_levels[f];
+    if (Lf < 1) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: factor " + std::to_string(f + 1) + " has n_levels = " + std::to_string(Lf) + "; must be >= 1");
+    P += Lf;
+  }
+  if (P > INT32_MAX / 2) return fail(c, AHMC_ERR_UNSUPPORTED, "glm_factor_set_target: " + std::to_string((long long)P) + " coefficient rows are beyond 2^30");
+  for (int f = 0; f < F; ++f)
+    for (int64_t i = 0; i < n_obs; ++i) {
+      const int32_t l = hs.levels[i + (int64_t)f * n_obs];
+      if (l < 0 || l >= hs.n_levels[f])
+        return fail(c, AHMC_ERR_ARGUMENT, "DomainError: levels[" + std::to_string((long long)i + 1) + ", " + std::to_string(f + 1) + "] = " + std::to_string(l) +
+                                              " is outside [0, " + std::to_string(hs.n_levels[f]) + ") (zero-based level indices)");
+    }
+  hs.P = P;
+  return hglm_set(c, family, n_obs, X, y, offset, prec, scale, hs);
 }
 
 // ahmc_hglm_coefficients and ahmc_glm_dispersion: a temporary of `elems` elements that begins with the n_theta elements of the

@@ -84,14 +84,14 @@ def linear_predictor(X, theta, offset=None):
     return eta
 
 
-def pointwise(family, X, y, theta, offset=None, scale=1.0):
+def pointwise(family, X, y, theta, offset=None, scale=1.0, factors=None):
     """(η, ℓ(y_i, η_i)), each (n_obs, N): the mirror of ahmc_glm_pointwise.  A family with a sampled dispersion takes it from θ's
-    last row (θ then has one row more than X has columns)."""
+    last row (θ then has one row more than X has columns).  `factors`: index-coded factors (the section at the end)."""
     fam = family_code(family)
-    if fam in AUX_FAMILIES:
-        return _link_at(fam, *_hier_pointwise_args(fam, X, theta, ()), y, offset, scale)[2:4]
+    if fam in AUX_FAMILIES or factors:
+        return _link_at(fam, *_hier_pointwise_args(fam, X, theta, (), factors), y, offset, scale)[2:4]
     X, th, _ = _theta(X, theta)
-    return _link_at(fam, X, th, [], y, offset, scale)[2:4]
+    return _link_at(fam, X, th, [], [], y, offset, scale)[2:4]
 
 
 def block_sums(ll):
@@ -109,14 +109,14 @@ def sanitize(lp):
     return np.where(np.isfinite(lp), lp, -np.inf)
 
 
-def logdensity(family, X, y, theta, offset=None, prior_prec=None, scale=1.0, aux_prior=None):
+def logdensity(family, X, y, theta, offset=None, prior_prec=None, scale=1.0, aux_prior=None, factors=None):
     """(ℓπ (N,), ∇ℓπ (D, N)) at θ (D, N) — with the model bound (functools.partial, a lambda) the callback of an ExternalTarget.
     ℓπ is returned as computed: an overflowing Poisson gives a non-finite value, which the engine sanitises (`sanitize`).
     `aux_prior` = (loc, scale) belongs to the families with a sampled dispersion (θ then has D + 1 rows)."""
-    if family_code(family) in AUX_FAMILIES or aux_prior is not None:
-        return _logdensity(*_hier_args(family, X, theta, (), prior_prec, aux_prior), y, offset)
+    if family_code(family) in AUX_FAMILIES or aux_prior is not None or factors:
+        return _logdensity(*_hier_args(family, X, theta, (), prior_prec, aux_prior, factors=factors), y, offset, scale)
     X, th, _ = _theta(X, theta)
-    return _logdensity(family_code(family), X, th, [], _prior_prec(prior_prec, X.shape[1], []), None, y, offset, scale)
+    return _logdensity(family_code(family), X, th, [], _prior_prec(prior_prec, X.shape[1], []), None, [], y, offset, scale)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -176,9 +176,10 @@ def _hier_theta(theta, P, groups):
     return th, groups
 
 
-def hier_coefficients(theta, P, groups):
+def hier_coefficients(theta, P, groups, factors=None):
     """(β (P, N), τ (G, N)): the coefficients on the model's own scale (β = W) and the group scales, from draws θ (P + G, N) —
-    the mirror of ahmc_hglm_coefficients"""
+    the mirror of ahmc_hglm_coefficients.  With `factors`, P counts the dense columns and the factors' levels are added to it."""
+    P = P + sum(n_levels(f) for f in factors or ())
     th, groups = _hier_theta(theta, P, groups)
     with np.errstate(over="ignore", invalid="ignore"):
         tau = np.exp(th[P:])
@@ -189,18 +190,18 @@ def hier_coefficients(theta, P, groups):
     return W, tau
 
 
-def hier_pointwise(family, X, y, theta, groups, offset=None, scale=1.0):
+def hier_pointwise(family, X, y, theta, groups, offset=None, scale=1.0, factors=None):
     """(η, ℓ(y_i, η_i)), each (n_obs, N): `pointwise` at the effective coefficients W; the dispersion of a family that samples it
     comes from θ's last row"""
     fam = family_code(family)
-    return _link_at(fam, *_hier_pointwise_args(fam, X, theta, groups), y, offset, scale)[2:4]
+    return _link_at(fam, *_hier_pointwise_args(fam, X, theta, groups, factors), y, offset, scale)[2:4]
 
 
-def hier_logdensity(family, X, y, theta, groups, offset=None, prior_prec=None, scale=1.0, aux_prior=None):
+def hier_logdensity(family, X, y, theta, groups, offset=None, prior_prec=None, scale=1.0, aux_prior=None, factors=None):
     """(ℓπ (N,), ∇ℓπ (P + G, N)) at θ (P + G, N).  `prior_prec` (P) covers the coefficients in no group and must be 0 on members.
     ℓπ is returned as computed (`sanitize` makes a non-finite value −Inf, as the engine does).  A family with a sampled dispersion
     has one more row, s, with the prior `aux_prior` = (loc, scale): `aux_logdensity`."""
-    return _logdensity(*_hier_args(family, X, theta, groups, prior_prec, aux_prior), y, offset, scale)
+    return _logdensity(*_hier_args(family, X, theta, groups, prior_prec, aux_prior, factors=factors), y, offset, scale)
 
 
 def _hier_finish(th, W, tau, R, lsum, p, groups):
@@ -347,9 +348,70 @@ def dispersion(theta):
         return np.exp(th[-1])
 
 
-def aux_logdensity(family, X, y, theta, groups=(), offset=None, prior_prec=None, aux_prior=None):
+def aux_logdensity(family, X, y, theta, groups=(), offset=None, prior_prec=None, aux_prior=None, factors=None):
     """(ℓπ (N,), ∇ℓπ (D, N)) at θ (D, N), D = P + G + 1, of a family with a sampled dispersion"""
-    return _logdensity(*_hier_args(family, X, theta, groups, prior_prec, aux_prior, True), y, offset)
+    return _logdensity(*_hier_args(family, X, theta, groups, prior_prec, aux_prior, True, factors), y, offset)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# include/ahmc_glm_factor.h: index-coded factors instead of one-hot columns of X (csrc/ahmc_glm.hpp: k_glm_eta_f, k_glm_fgrad)
+# ------------------------------------------------------------------------------------------------------------------------------
+__doc__ += """
+Index-coded factors (`factors=` of every function above; check_factors, factor_ranges, expand_factors):
+    factor f has L_f levels and a level index idx_f[i] ∈ [0, L_f) per observation; X keeps the P_x >= 1 dense columns; the coefficient
+    parameters are P = P_x + Σ L_f rows, the dense ones first, then factor 0's levels, factor 1's, …  Groups, prior_prec and the rows
+    after the coefficients (log τ_k, s) address these P rows as they address the columns of X.
+    η_i = (X·W[0:P_x])_i + W[off_0 + idx_0[i]] + W[off_1 + idx_1[i]] + … + offset_i        the gathers in this order, offset last
+    R_d = −(Xᵀu)_d for d < P_x as above;  R[off_f + l] = −Σ_slices Σ_{i in the slice, idx_f[i] = l} u_i: observations in slices of
+    K_SLICE, within a slice ascending i from +0, the slice sums added in ascending order.
+This is what the orders of the first header give for the one-hot columns of `expand_factors(X, factors)`: fma(0, w, a) = a and
+fma(1, u, a) = a + u for finite operands, so the two encodings give the same numbers (up to the sign of a zero).
+"""
+
+GLM_FACTOR_MAX = 8   # AHMC_GLM_FACTOR_MAX
+
+
+def n_levels(factor):
+    """the levels of a factor given as (index, n_levels) or an object with these attributes; n_levels None: max + 1"""
+    idx, L = (factor.index, factor.n_levels) if hasattr(factor, "n_levels") else factor
+    return int(np.max(idx)) + 1 if L is None else int(L)
+
+
+def check_factors(factors, n_obs):
+    """factors as a list of (index (n_obs,) int64, n_levels): integer indices in [0, n_levels), one per observation, at most GLM_FACTOR_MAX"""
+    out = []
+    for f, fac in enumerate(factors or ()):
+        idx, L = (fac.index, fac.n_levels) if hasattr(fac, "n_levels") else fac
+        idx = np.asarray(idx)
+        if idx.ndim != 1 or idx.size != n_obs:
+            raise ValueError(f"DimensionMismatch: factor {f + 1} has an index of shape {idx.shape}, n_obs = {n_obs}")
+        if not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError(f"ArgumentError: factor {f + 1}: the level index must have an integer type, not {idx.dtype}")
+        L = int(idx.max()) + 1 if L is None else int(L)
+        if L < 1:
+            raise ValueError(f"DomainError: factor {f + 1} has n_levels = {L}; must be >= 1")
+        if idx.min() < 0 or idx.max() >= L:
+            bad = int(np.flatnonzero((idx < 0) | (idx >= L))[0])
+            raise ValueError(f"DomainError: factor {f + 1}: index[{bad}] = {int(idx[bad])} is outside [0, {L}) (zero-based level indices)")
+        out.append((idx.astype(np.int64), L))
+    if len(out) > GLM_FACTOR_MAX:
+        raise ValueError(f"ArgumentError: {len(out)} factors; at most {GLM_FACTOR_MAX}")
+    return out
+
+
+def factor_ranges(P_x, factors):
+    """[(start, stop)] of each factor's coefficient rows: P_x dense rows, then factor 0's levels, factor 1's, …"""
+    out, lo = [], int(P_x)
+    for fac in factors or ():
+        out.append((lo, lo + n_levels(fac)))
+        lo = out[-1][1]
+    return out
+
+
+def expand_factors(X, factors):
+    """X with every factor written as one-hot columns appended in order: the dense (n_obs, P) equivalent of (X, factors)"""
+    X = np.asarray(X, dtype=np.float64)
+    return np.column_stack([X] + [np.eye(L)[idx] for idx, L in check_factors(factors, X.shape[0])])
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -363,15 +425,16 @@ def _prior_prec(prior_prec, P, groups):
     return p
 
 
-def _hier_args(family, X, theta, groups, prior_prec, aux_prior, is_aux=False):
-    """the checks of θ (P + G, N), or (P + G + 1, N) for a family with a sampled dispersion: `_logdensity`'s first six arguments"""
+def _hier_args(family, X, theta, groups, prior_prec, aux_prior, is_aux=False, factors=None):
+    """the checks of θ (P + G, N), or (P + G + 1, N) for a family with a sampled dispersion: `_logdensity`'s first seven arguments"""
     fam = family_code(family)
     is_aux = is_aux or fam in AUX_FAMILIES or aux_prior is not None
     if is_aux and fam not in AUX_FAMILIES:
         raise ValueError(f"ArgumentError: family {fam} has no sampled dispersion (aux_prior belongs to {sorted(f for f in FAMILIES if FAMILIES[f] in AUX_FAMILIES)})")
     aux = check_aux_prior(aux_prior) if is_aux else None
     X = np.asarray(X, dtype=np.float64)
-    P = X.shape[1]
+    factors = check_factors(factors, X.shape[0])
+    P = X.shape[1] + sum(L for _, L in factors)
     th = np.asarray(theta, dtype=np.float64)
     th = th.reshape(-1, 1) if th.ndim == 1 else th
     if not is_aux:
@@ -380,35 +443,50 @@ def _hier_args(family, X, theta, groups, prior_prec, aux_prior, is_aux=False):
         groups = check_groups(groups, P)
         if th.shape[0] != P + len(groups) + 1:
             raise ValueError(f"DimensionMismatch: θ {th.shape}, P + G + 1 = {P} + {len(groups)} + 1")
-    return fam, X, th, groups, _prior_prec(prior_prec, P, groups), aux
+    return fam, X, th, groups, _prior_prec(prior_prec, P, groups), aux, factors
 
 
-def _hier_pointwise_args(fam, X, theta, groups):
+def _hier_pointwise_args(fam, X, theta, groups, factors=None):
     X = np.asarray(X, dtype=np.float64)
+    factors = check_factors(factors, X.shape[0])
     th = np.ascontiguousarray(theta, dtype=np.float64)   # (row-major, as W is below: numpy's product depends on the memory order)
     th = th.reshape(-1, 1) if th.ndim == 1 else th
-    _, groups = _hier_theta(th[:-1] if fam in AUX_FAMILIES else th, X.shape[1], groups)
-    return X, th, groups
+    _, groups = _hier_theta(th[:-1] if fam in AUX_FAMILIES else th, X.shape[1] + sum(L for _, L in factors), groups)
+    return X, th, groups, factors
 
 
-def _link_at(fam, X, th, groups, y, offset, scale):
+def _link_at(fam, X, th, groups, factors, y, offset, scale):
     """θ (P + G [+ 1], N) split into the coefficient parameters, the log-scales and s: (W, τ, η, *`link`'s values at η); the plain
-    model's W is θ itself, in the caller's memory order"""
-    P, G = X.shape[1], len(groups)
+    model's W is θ itself, in the caller's memory order.  `factors` checked (maybe none): their rows of W are gathered into η after
+    the product over X's columns, factor after factor, and before the offset"""
+    Px, G = X.shape[1], len(groups)
+    P = Px + sum(L for _, L in factors)
     W, tau = hier_coefficients(th[:P + G], P, groups) if th.shape[0] > P else (th, th[P:])
-    eta = linear_predictor(X, W, offset)
+    if factors:
+        eta = X @ W[:Px]
+        for (lo, _), (idx, _) in zip(factor_ranges(Px, factors), factors):
+            eta = eta + W[lo + idx]
+        if offset is not None:
+            eta = eta + np.asarray(offset, dtype=np.float64).reshape(-1, 1)
+    else:
+        eta = linear_predictor(X, W, offset)
     return (W, tau, eta, *link(fam, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, scale, th[P + G:] if fam in AUX_FAMILIES else None))
 
 
-def _logdensity(fam, X, th, groups, p, aux, y, offset, scale=1.0):
-    """(ℓπ, ∇ℓπ) of every model: `groups` checked (maybe none), p (P), `aux` = (m, A) of the prior of s or None"""
-    PG = X.shape[1] + len(groups)
-    W, tau, _, ll, u, *ds = _link_at(fam, X, th, groups, y, offset, scale)
+def _logdensity(fam, X, th, groups, p, aux, factors, y, offset, scale=1.0):
+    """(ℓπ, ∇ℓπ) of every model: `groups` and `factors` checked (maybe none), p (P), `aux` = (m, A) of the prior of s or None"""
+    Px = X.shape[1]
+    PG = Px + sum(L for _, L in factors) + len(groups)
+    W, tau, _, ll, u, *ds = _link_at(fam, X, th, groups, factors, y, offset, scale)
     with np.errstate(over="ignore", invalid="ignore"):
         lsum = block_sums(ll).sum(axis=0)
         xtu = np.zeros_like(W)
         for k0 in range(0, X.shape[0], K_SLICE):
-            xtu = xtu + X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
+            part = np.zeros_like(W)
+            part[:Px] = X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
+            for (lo, _), (idx, _) in zip(factor_ranges(Px, factors), factors):
+                np.add.at(part, lo + idx[k0:k0 + K_SLICE], u[k0:k0 + K_SLICE])   # (in order: ascending i within the slice)
+            xtu = xtu + part
         g = np.empty_like(th)
         lp, g[:PG] = _hier_finish(th[:PG], W, tau, -xtu, lsum, p, groups)
         if aux is not None:

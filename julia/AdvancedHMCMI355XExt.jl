@@ -518,5 +518,6 @@ include("AdvancedHMCMI355XLowRankAdapt.jl")  # lowrank_adaptor_init!: include/ah
 include("AdvancedHMCMI355XGLM.jl")  # set_target!(z, ::GLMTarget), glm_pointwise: include/ahmc_glm.h
 include("AdvancedHMCMI355XGLMHier.jl")  # set_target!(z, ::HierGLMTarget), hglm_coefficients: include/ahmc_glm_hier.h
 include("AdvancedHMCMI355XGLMAux.jl")  # set_target!(z, ::AuxGLMTarget), glm_dispersion: include/ahmc_glm_aux.h
+include("AdvancedHMCMI355XGLMFactor.jl")  # set_target!(z, ::FactorGLMTarget), get_target_glm_factor: include/ahmc_glm_factor.h
 
 end # module
