@@ -188,6 +188,8 @@ static __device__ const unsigned long long EXP2_64_BITS[64] = {
 #ifndef AHMC_LEAF_MICRO
 #define AHMC_LEAF_MICRO 1   // round 5's two instruction cuts in the leaf (no underflow select in the weight's exp; ΔH_max by a scalar branch on the direction); 0: round 4's forms, for A/B runs
 #endif
+// (TWIN: leaf_weight_exp_pair below repeats the table form of this function, statement for statement, for two leaves in the two lane
+// parities of a wave — change both)
 template <bool UNIFORM>
 __device__ __forceinline__ double leaf_weight_exp(double x) {
   constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
@@ -254,6 +256,43 @@ __device__ __forceinline__ T alpha_from_logweight(T lw) {
   const T w = leaf_weight_exp<UNIFORM>(lw > T(0) ? T(0) : lw);
   return w >= T(1) ? T(1) : w;
 }
+
+// leaf_weight_exp<true> for TWO leaves of a chain that owns the wave in one pass: even lanes carry leaf a's argument, odd lanes leaf
+// b's (pair_leaf_stats below), and lanes LA / LB are the ones whose results are read.  The two table entries are two scalar loads issued
+// together — their indices come from lanes LA / LB by v_readlane — and lane parity picks the entry; everything else is lane-local, so
+// each of the two lanes runs the instructions of leaf_weight_exp<true> on its own argument and returns its bits.
+// TWIN of the table form of leaf_weight_exp above, statement for statement: change both.  EVERY lane's argument must be a value whose
+// (int)dk is defined (the caller hands every lane one of the two leaves' arguments, so it is wherever leaf_weight_exp's own is).
+template <int LA, int LB>
+__device__ __forceinline__ double leaf_weight_exp_pair(double x, bool odd) {
+#if AHMC_LEAF_EXP == 2
+  constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
+  const double xc = x < -1100.0 ? -1100.0 : x;
+  const double dk = __builtin_rint(xc * 92.33248261689366);                // 64 / ln 2
+  double t = __builtin_fma(dk, -0x1.62e42fef00000p-7, xc);                  // − k·ln2/64: high part (20 trailing zero bits: exact product)
+  t = __builtin_fma(dk, -0x1.473de6af278edp-40, t);                         // low part
+  const int k = (int)dk;
+  const int ka = __builtin_amdgcn_readlane(k, LA), kb = __builtin_amdgcn_readlane(k, LB);
+  const double tja = C(EXP2_64_BITS[ka & 63]), tjb = C(EXP2_64_BITS[kb & 63]);
+  const double tj = odd ? tjb : tja;
+  double q = __builtin_fma(t, 8.3333333333333332e-03, 4.1666666666666664e-02);  // 1/120, 1/24
+  q = fma3(t, q, 1.6666666666666666e-01);
+  q = fma3(t, q, 0.5);
+  q = fma3(t, q, 1.0);
+  q = q * t;                                                                // e^t − 1
+#if AHMC_LEAF_MICRO
+  return __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
+#else
+  double z = __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
+  z = x < -1075.0 ? 0.0 : z;
+  return z;
+#endif
+#else
+  return leaf_weight_exp<true>(x);   // (the Horner forms read no table: already lane-local)
+#endif
+}
+template <int LA, int LB>
+__device__ __forceinline__ float leaf_weight_exp_pair(float x, bool) { return exp(x); }
 
 template <class T> __device__ __forceinline__ T maxabs(T a, T b) { return fabs(a) > fabs(b) ? a : b; }  // :526
 
@@ -508,6 +547,26 @@ __device__ __forceinline__ bool wave64_pair_reduce(T da, T db, T& ea, T& eb) {
   ea = dpp_mov<0x150 + 4 * Q + 2>(z);  // row_newbcast
   eb = dpp_mov<0x150 + 4 * Q + 3>(z);
   return le0;
+}
+// wave64_pair_reduce without the four row_newbcast moves: the same exchanges, additions and decision, and the TRANSPOSED register itself
+// comes back in z — lanes 0 / 1 of a row hold Σda / Σdb, lanes 4q + 2 / 4q + 3 hold Σea / Σeb (with the butterfly's bits in quads 1 and 3,
+// as above).  For pair_leaf_stats (below), which does both leaves' scalar work in the two lane parities instead of once per broadcast
+// value.  TWIN of wave64_pair_reduce up to `le0`: change both (tests/device_probe/pair_stats.hip runs them on the same data).
+// AHMC_PAIR_LANE_STATS 0: k_nuts keeps wave64_pair_reduce and the serial leaf_stats — the parent's device code, for A/B runs.
+#ifndef AHMC_PAIR_LANE_STATS
+#define AHMC_PAIR_LANE_STATS 1
+#endif
+template <class T>
+__device__ __forceinline__ bool wave64_pair_reduce_t(T da, T db, T ea, T eb, T& z) {
+  const bool odd = (threadIdx.x & 1u) != 0, up = (threadIdx.x & 2u) != 0;
+  const T x = (odd ? db : da) + dpp_mov<0xB1>(odd ? da : db);  // quad_perm [1,0,3,2]
+  const T y = (odd ? eb : ea) + dpp_mov<0xB1>(odd ? ea : eb);
+  z = (up ? y : x) + dpp_mov<0x4E>(up ? x : y);                // quad_perm [2,3,0,1]
+  z += dpp_mov<0x124>(z);                                       // row_ror:4
+  z += dpp_mov<0x128>(z);                                       // row_ror:8
+  z = xor16_sum(z);
+  z = xor32_sum(z);
+  return (__builtin_amdgcn_ballot_w64(z <= T(0)) & 3ull) != 0ull;  // lane 0: Σda, lane 1: Σdb
 }
 
 // all-reduce (sum) of K independent values across the G lanes of each group
@@ -967,6 +1026,56 @@ __device__ __forceinline__ T leapfrog_step_ne_partial(Point<T, E>& z, const T (&
 }
 template <class T>
 __device__ __forceinline__ T neg_energy_sanitized(T s) { return is_finite(s) ? s : -Lim<T>::inf(); }
+
+// v_readlane of a float / double: the value of lane L as a wave-uniform (scalar) one
+template <int L> __device__ __forceinline__ float readlane_t(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), L)); }
+template <int L> __device__ __forceinline__ double readlane_t(double v) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), L), __builtin_amdgcn_readlane(__double2loint(v), L));
+}
+
+// The order-independent scalar work of the TWO leaves of a pair step of k_nuts (AHMC_PAIR_LANE_STATS), once, with lane parity picking
+// the leaf — in k_nuts' leaf_stats it runs once per leaf in all 64 lanes on a wave-uniform value, the second run behind the first.
+// z is wave64_pair_reduce_t's transposed register.  One quad_perm [2,3,2,3] gives EVERY lane an energy (even lanes Σea, odd lanes
+// Σeb): lanes 0 / 1 of a quad hold dot-product sums, which may be ±Inf or NaN, and (int)dk of the weight's exp on those is undefined
+// behaviour.  Quads 0 and 2 then hold the energies in another rounding (wave64_pair_reduce); nothing reads them.  Lanes 4Q + 2 / 4Q + 3
+// (6 / 7) take leaf a's / leaf b's value through the expressions of leaf_stats, in its order, and v_readlane and the compares' lane
+// masks hand the results back as scalars.  No exec-masked region.  What depends on the ORDER of the two leaves (the running sums, maxabs,
+// redo / numerical / sub_term, the branch that drops leaf b) stays with the caller.
+// TWIN of leaf_stats in the pair arm of k_nuts (ahmc_nuts.hpp): a change to a leaf's scalar work is made in both and in the single-leaf arm.
+template <class T> struct PairLeafStats {
+  T w[2], sa[2], dH[2];     // leaf weight (LINW: W, else ℓw), α = min(1, W), ΔH
+  bool redo[2], div[2];     // ℓw above the linear domain's limit; the divergence test !(−H0 < Δ_max + ne)
+};
+template <class T, bool LINW, int Q = AHMC_PAIR_RED_QUAD>
+__device__ __forceinline__ void pair_leaf_stats(T z, T H0, T delta_max, T lw_limit, PairLeafStats<T>& o) {
+  static_assert(Q >= 0 && Q <= 3, "a row has four quads");
+  constexpr int LA = 4 * Q + 2, LB = 4 * Q + 3;
+  const bool odd = (threadIdx.x & 1u) != 0;
+  const T ne = neg_energy_sanitized(dpp_mov<0xEE>(z));  // quad_perm [2,3,2,3]
+  const T dH = -ne - H0;
+  const T lw = H0 + ne;
+  T w, sa;
+  if constexpr (LINW) {
+    w = leaf_weight_exp_pair<LA, LB>(lw, odd);
+    sa = w >= T(1) ? T(1) : w;
+  } else {
+    const T wa = leaf_weight_exp_pair<LA, LB>(lw > T(0) ? T(0) : lw, odd);  // alpha_from_logweight
+    sa = wa >= T(1) ? T(1) : wa;
+    w = lw;
+  }
+  const unsigned long long m_redo = __builtin_amdgcn_ballot_w64(lw > lw_limit);
+  const unsigned long long m_div = __builtin_amdgcn_ballot_w64(!(-H0 < delta_max + ne));
+  o.w[0] = readlane_t<LA>(w);
+  o.w[1] = readlane_t<LB>(w);
+  o.sa[0] = readlane_t<LA>(sa);
+  o.sa[1] = readlane_t<LB>(sa);
+  o.dH[0] = readlane_t<LA>(dH);
+  o.dH[1] = readlane_t<LB>(dH);
+  o.redo[0] = LINW && ((m_redo >> LA) & 1ull) != 0ull;
+  o.redo[1] = LINW && ((m_redo >> LB) & 1ull) != 0ull;
+  o.div[0] = ((m_div >> LA) & 1ull) != 0ull;
+  o.div[1] = ((m_div >> LB) & 1ull) != 0ull;
+}
 
 // leapfrog_step (untempered) that sums two more caller-supplied partials of the UPDATED point in the same all-reduce
 // as ℓπ and the kinetic energy: the NUTS kernels pass the two U-turn dot products of the merge that follows the

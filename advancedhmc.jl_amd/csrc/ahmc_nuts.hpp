@@ -641,6 +641,38 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
               dots[0] += A_c[e] * (minv[e] * r_a[e]);
               dots[1] += A_c[e] * (minv[e] * cur.r[e]);
             }
+#if AHMC_PAIR_LANE_STATS
+            // The reduction hands back its transposed register, and what the two leaves' scalar work computes that does not depend on
+            // their order — sanitised energy, ΔH, ℓw, the weight's exp, min(1, W), the redo and divergence compares — runs ONCE, leaf a in
+            // the even lanes and leaf b in the odd ones (ahmc_device.hpp: pair_leaf_stats, the TWIN of leaf_stats below): one exp chain
+            // with its scalar table load on the leaf loop's chain of dependent stages instead of two back to back.  What depends on the
+            // order is applied here, in leaf_stats' order; if leaf a diverges nothing of leaf b is applied, its redo bit included.
+            T z_t;
+            const bool turn_ab = wave64_pair_reduce_t(dots[0], dots[1], ea, eb, z_t);
+            PairLeafStats<T> ps;
+            pair_leaf_stats<T, LINW>(z_t, H0, p.delta_max, sizeof(T) == 4 ? T(60) : T(LINW_LIMIT), ps);
+            auto leaf_apply = [&](const int i) {
+              pos_cur += v;
+              ck_c = pos_cur;
+              w_c = ps.w[i];
+              if constexpr (LINW) redo = redo || ps.redo[i];
+              sub_term = ps.div[i];
+              numerical = numerical || sub_term;
+              sa_c = sa_c + ps.sa[i];
+              na_c = na_c + 1;
+              if constexpr (AHMC_LEAF_MICRO) {
+                if (v > 0) { dh_c = maxabs(dh_c, ps.dH[i]); asm volatile(""); }
+                else { dh_c = maxabs(ps.dH[i], dh_c); asm volatile(""); }
+              } else {
+                dh_c = v > 0 ? maxabs(dh_c, ps.dH[i]) : maxabs(ps.dH[i], dh_c);
+              }
+            };
+            leaf_apply(0);
+            if (!sub_term) {
+              const T w_p = w_c;
+              const int ck_p = ck_c;
+              leaf_apply(1);
+#else
             const bool turn_ab = wave64_pair_reduce(dots[0], dots[1], ea, eb);
             // a leaf's scalar work — weight, divergence test, running statistics, candidate = this leaf: the lines of the single-leaf
             // form below that a fast kernel whose chain owns the wave executes, in their order.
@@ -648,7 +680,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
             // the leaf's scalar work is made in BOTH, or the first doubling's leaf (single-leaf arm) and the later ones (here) stop
             // agreeing bit for bit — tests/test_leaf_pairs.py's fixture is what notices.  They are two texts, not one lambda, because with the
             // single-leaf arm compiled through a shared lambda the -DAHMC_LEAF_PAIR=0 build no longer had the parent's device code (ahmc_device.hpp:
-            // leapfrog_step_ne_partial).
+            // leapfrog_step_ne_partial).  (-DAHMC_PAIR_LANE_STATS=0 only: the arm above does this work through its TWIN pair_leaf_stats.)
             auto leaf_stats = [&](const T ne) {
               pos_cur += v;
               const T dH = -ne - H0;
@@ -679,6 +711,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
               const T w_p = w_c;
               const int ck_p = ck_c;
               leaf_stats(neg_energy_sanitized(eb));
+#endif
               if (!sub_term) {
                 // the level-0 merge: combine(rng, sampler′, sampler′′) and the U-turn test of the pair, as merge_level does them
                 T w_new;
