@@ -242,6 +242,18 @@ GLM_FACTOR_SIGNATURES = {
     "ahmc_glm_factor_get_target": (_i32, [_vp, C.POINTER(_i64), _pi32, _pi32]),
 }
 
+# include/ahmc_glm_ordinal.h: the ordered-logit family of the GLM target, whose cutpoints are sampled (likewise: the HIP engine only)
+AHMC_GLM_ORDINAL_VERSION = 1
+GLM_ORDINAL_MAX_CATEGORIES = 16
+GLM_ORDERED_LOGIT = 5
+GLM_ORDINAL_SIGNATURES = {
+    "ahmc_glm_ordinal_version": (_i32, []),
+    "ahmc_glm_ordinal_set_target": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _pi32, _pi32, _pi32, C.POINTER(_f64), _i32, _pi32, _pi32, _i32,
+                                           C.POINTER(_f64)]),
+    "ahmc_glm_ordinal_get_target": (_i32, [_vp, _pi32, C.POINTER(_f64)]),
+    "ahmc_glm_cutpoints": (_i32, [_vp, _vp, _i64, _vp]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -336,6 +348,15 @@ class CLib:
             v = self.dll.ahmc_glm_factor_version()
             if v != AHMC_GLM_FACTOR_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm_factor version {v}, expected {AHMC_GLM_FACTOR_VERSION}")
+        # ahmc_glm_ordinal.h: likewise
+        gord = [getattr(self.dll, name, None) for name in GLM_ORDINAL_SIGNATURES]
+        self.has_glm_ordinal = all(fn is not None for fn in gord)
+        if self.has_glm_ordinal:
+            for fn, (res, args) in zip(gord, GLM_ORDINAL_SIGNATURES.values()):
+                fn.restype, fn.argtypes = res, args
+            v = self.dll.ahmc_glm_ordinal_version()
+            if v != AHMC_GLM_ORDINAL_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_ordinal version {v}, expected {AHMC_GLM_ORDINAL_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

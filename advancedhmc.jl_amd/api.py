@@ -335,6 +335,10 @@ class GLMTarget:
     N(0, prior_scale²) per coefficient — `prior_scale` a scalar or (D,) — or given as its precision `prior_prec`; neither: flat.
     `factors` (at most 8 `Factor`s) add one coefficient per level after the columns of X: `.P_x` = X.shape[1] dense coefficients,
     `.P` = P_x + Σ n_levels in all, `.factor_ranges` their rows; prior_scale / prior_prec then have P entries.
+    `family="ordered_logit"` with `n_categories=C` (include/ahmc_glm_ordinal.h): y holds ordered categories 0 … C − 1 and
+    P(y <= k) = σ(c_{k+1} − η).  The model has no intercept — the cutpoints take its place, and a constant column in X is not
+    identified.  θ ends with C − 1 rows κ (`.cut_rows`): κ_1 = c_1, κ_j = log(c_j − c_{j−1}), with the prior `cut_prior` =
+    (loc_1, scale_1, loc_gap, scale_gap) on κ itself, default (0, 2.5, 0, 1); `.cutpoints(θ)` gives c of draws.
     The engine evaluates all chains at once, X·Θ and Xᵀ·U on the MFMA units.  HIP engine only (the CPU checker takes the same
     density as `ExternalTarget(D, lambda th: glm.logdensity(...))` or a host KernelTarget)."""
     kind = capi.TARGET_GLM
@@ -342,15 +346,32 @@ class GLMTarget:
     groups = ()
     factors = ()
 
-    def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None, factors=None):
+    n_categories = 0
+    cut_prior = None
+
+    def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None, factors=None,
+                 n_categories=None, cut_prior=None):
         X = np.asarray(X, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64).ravel()
         if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.size != X.shape[0]:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: X {X.shape}, y {y.shape}")
+        ordinal = family in _glm.ORDINAL_FAMILIES if isinstance(family, str) else isinstance(family, (int, np.integer)) and family == _glm.ORDERED_LOGIT
         try:
-            self.family = _glm.family_code(family)
+            self.family = _glm.ORDERED_LOGIT if ordinal else _glm.family_code(family)
         except ValueError as e:
             raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+        if not ordinal and (n_categories is not None or cut_prior is not None):
+            raise ArgumentError(capi.ERR_ARGUMENT, f"GLMTarget: n_categories and cut_prior belong to family \"ordered_logit\", not to family {self.family}")
+        if ordinal:
+            if scale != 1.0 or aux_prior is not None:
+                raise ArgumentError(capi.ERR_ARGUMENT, "GLMTarget: family \"ordered_logit\" has no scale and no dispersion; scale and aux_prior do not apply")
+            if n_categories is None:
+                raise ArgumentError(capi.ERR_ARGUMENT, "GLMTarget: family \"ordered_logit\" needs n_categories")
+            try:
+                _, self.n_categories = _glm.check_categories(y, n_categories)
+                self.cut_prior = _glm.check_cut_prior(cut_prior)
+            except (ValueError, TypeError) as e:
+                raise ArgumentError(capi.ERR_ARGUMENT, str(e))
         if prior_scale is not None and prior_prec is not None:
             raise ArgumentError(capi.ERR_ARGUMENT, "GLMTarget: give prior_scale or prior_prec, not both")
         self.aux = self.family in _glm.AUX_FAMILIES
@@ -374,7 +395,7 @@ class GLMTarget:
         self.P_x = X.shape[1]
         self.factor_ranges = _glm.factor_ranges(self.P_x, self.factors)
         self.P = self.P_x + sum(f.n_levels for f in self.factors)
-        self.D = self.P + (1 if self.aux else 0)
+        self.D = self.P + (1 if self.aux else 0) + self._n_cut
         if prior_scale is not None:
             prior_prec = 1.0 / np.square(np.asarray(prior_scale, dtype=np.float64))
         try:
@@ -386,8 +407,27 @@ class GLMTarget:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: offset {self.offset.shape}, n_obs {self.n_obs}")
         self.scale = float(scale)
 
+    @property
+    def _n_cut(self):
+        return self.n_categories - 1 if self.n_categories else 0
+
+    @property
+    def cut_rows(self):
+        """(start, stop) of the rows κ of θ: (D − C + 1, D)"""
+        if not self.n_categories:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"cut_rows: family {self.family} has no cutpoints")
+        return self.D - self._n_cut, self.D
+
+    def cutpoints(self, theta):
+        """c (C − 1, n) of draws θ (D, n) by the numpy mirror (family "ordered_logit")"""
+        lo, hi = self.cut_rows
+        return _glm.cutpoints(np.asarray(theta, dtype=np.float64)[lo:hi])
+
     def logdensity(self, theta):
         """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
+        if self.n_categories:
+            return _glm.ordinal_logdensity(self.X, self.y, theta, self.n_categories, self.groups, self.offset, self.prior_prec, self.cut_prior,
+                                           factors=self.factors)
         return _glm.hier_logdensity(self.family, self.X, self.y, theta, self.groups, self.offset, self.prior_prec, self.scale, self.aux_prior,
                                     factors=self.factors)
 
@@ -419,16 +459,17 @@ class HierGLMTarget(GLMTarget):
     then log τ of each group.  `prior_scale` / `prior_prec` cover the coefficients in no group; on members they are forced to 0.
     `.coefficients(θ)` gives (β, τ) on the model's own scale.  HIP engine only."""
 
-    def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None, factors=None):
+    def __init__(self, X, y, groups, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None, factors=None,
+                 n_categories=None, cut_prior=None):
         super().__init__(X, y, family=family, prior_scale=prior_scale, prior_prec=prior_prec, offset=offset, scale=scale, aux_prior=aux_prior,
-                         factors=factors)
+                         factors=factors, n_categories=n_categories, cut_prior=cut_prior)
         groups = [g if isinstance(g, CoefGroup) else CoefGroup(*g) for g in groups]
         try:
             _glm.check_groups(groups, self.P)
         except (ValueError, TypeError) as e:
             raise ArgumentError(capi.ERR_ARGUMENT, str(e))
         self.groups = tuple(CoefGroup(int(g.start), int(g.stop), bool(g.centered), float(g.scale)) for g in groups)
-        self.D = self.P + len(self.groups) + (1 if self.aux else 0)
+        self.D = self.P + len(self.groups) + (1 if self.aux else 0) + self._n_cut
         if self.prior_prec is not None:
             self.prior_prec = self.prior_prec.copy()
             for g in self.groups:
@@ -437,7 +478,7 @@ class HierGLMTarget(GLMTarget):
     def coefficients(self, theta):
         """(β (P, n), τ (G, n)) of draws θ (D, n) by the numpy mirror"""
         th = np.asarray(theta, dtype=np.float64)
-        return _glm.hier_coefficients(th[:-1] if self.aux else th, self.P, self.groups)
+        return _glm.hier_coefficients(th[:th.shape[0] - self._n_cut - (1 if self.aux else 0)], self.P, self.groups)
 
     def __repr__(self):
         return f"HierGLMTarget(n_obs={self.n_obs}, P={self.P}, groups={len(self.groups)}, family={self.family})"
@@ -796,7 +837,10 @@ class Engine:
         hier, G, F = isinstance(t, HierGLMTarget), len(t.groups), len(t.factors)
         if F:
             self._need("has_glm_factor", "ahmc_glm_factor.h", f"{type(t).__name__}(factors=…)")
-        if t.aux:
+        if t.n_categories:
+            self._need("has_glm_ordinal", "ahmc_glm_ordinal.h", f"{type(t).__name__}(family=\"ordered_logit\")")
+            model = f"the model has P + G + (C - 1) = {t.P} + {G} + {t.n_categories - 1} parameters"
+        elif t.aux:
             self._need("has_glm_aux", "ahmc_glm_aux.h", f"GLMTarget(family={t.family})")
             model = f"the model has P + G + 1 = {t.P} + {G} + 1 parameters"
         elif hier:
@@ -814,7 +858,11 @@ class Engine:
         data = (capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p))
         table = (G, (C.c_int32 * max(G, 1))(*[g.start for g in t.groups]), (C.c_int32 * max(G, 1))(*[g.stop for g in t.groups]),
                  (C.c_int32 * max(G, 1))(*[int(g.centered) for g in t.groups]), (C.c_double * max(G, 1))(*[g.scale for g in t.groups]))
-        if F:
+        if t.n_categories:
+            lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32) if F else None
+            self._call("ahmc_glm_ordinal_set_target", int(t.n_obs), int(t.P_x), *data, *table, F, (C.c_int32 * F)(*[f.n_levels for f in t.factors]) if F else None,
+                       lev.ctypes.data_as(C.POINTER(C.c_int32)) if F else None, int(t.n_categories), (C.c_double * 4)(*t.cut_prior))
+        elif F:
             lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32)
             aux = t.aux_prior if t.aux else (0.0, 1.0)
             self._call("ahmc_glm_factor_set_target", int(t.family), int(t.n_obs), int(t.P_x), *data, float(t.scale), *table, F,
@@ -846,6 +894,17 @@ class Engine:
         ptr, n = self._draws("glm_dispersion", theta, n_cols)
         out = np.empty(n, dtype=self.dtype)
         self._call("ahmc_glm_dispersion", ptr, n, capi.as_ptr(out) if n else None)
+        return out
+
+    def glm_cutpoints(self, draws=None, n_cols=None):
+        """the cutpoints c (C − 1, n) of draws θ (D, n) of the bound ordinal model — an array (default: the context's current θ), or a
+        device pointer (an int) together with `n_cols`: ahmc_glm_cutpoints"""
+        self._need("has_glm_ordinal", "ahmc_glm_ordinal.h", "glm_cutpoints")
+        nc = C.c_int32()
+        self._call("ahmc_glm_ordinal_get_target", C.byref(nc), None)
+        ptr, n = self._draws("glm_cutpoints", draws, n_cols)
+        out = np.empty((nc.value - 1, n), dtype=self.dtype, order="F")
+        self._call("ahmc_glm_cutpoints", ptr, n, capi.as_ptr(out) if n else None)
         return out
 
     def hglm_coefficients(self, theta=None, n_cols=None):

@@ -204,12 +204,90 @@ __device__ __forceinline__ void glm_link_aux(T y, T eta, T s, T cs, T& ll, T& u,
   }
 }
 
+// ---- include/ahmc_glm_ordinal.h: the ordered-logit family, whose C − 1 cutpoints are sampled (FAM == 5) -----------------------------
+// θ ends with κ (C − 1 rows): c_1 = κ_1, δ_j = exp(κ_j) and c_j = c_{j−1} + δ_j for j >= 2 (glm.py: cutpoints).  Per (chain, cutpoint)
+// constants of an interior category's link: lg_j = log(1 − e^{−δ_j}) — log(−expm1(−δ)) for δ <= log 2, log1p(−exp(−δ)) above — and
+// r_j = 1/expm1(δ_j); both 0 at j = 1, which has no gap below it.
+constexpr int GLM_ORD_MAX_CAT = 16;  // AHMC_GLM_ORDINAL_MAX_CATEGORIES
+
+// (lg, r) of a gap δ > 0
+template <class T>
+__device__ __forceinline__ void glm_cut_gap(T d, T& lg, T& r) {
+  const T em = exp(-d);
+  lg = d <= T(0.693147180559945309417) ? log(-expm1(-d)) : log1p(-em);
+  r = T(1) / expm1(d);
+}
+
+// the table of the listed columns of th (column stride ldt; κ begins at row k0): tab[(q·(C−1) + j)·ldo + column], q = 0 c, 1 lg, 2 r.
+// One thread per column, j ascending.  With lgr = 0 only c is written (ahmc_glm_cutpoints: tab is then (C−1, n) with ldo = 1 and
+// the column's stride C − 1: c_out).
+template <class T>
+__global__ __launch_bounds__(256) void k_glm_cut(const T* __restrict__ th, int64_t ldt, int64_t k0, int Cm1, T* __restrict__ tab, int64_t N, int64_t ncols,
+                                                 const int* __restrict__ idx, int lgr) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= ncols) return;
+  const int64_t c = idx ? (int64_t)idx[j] : j;
+  const T* kap = th + c * ldt + k0;
+  // (lgr: tab (3, C−1, N), a chain per column; otherwise the draws' layout, a column's C − 1 cutpoints together)
+  const int64_t sj = lgr ? N : 1, base = lgr ? c : c * Cm1;
+  T cj = kap[0];
+  tab[base] = cj;
+  if (lgr) {
+    tab[((int64_t)Cm1) * N + c] = T(0);
+    tab[((int64_t)2 * Cm1) * N + c] = T(0);
+  }
+  for (int q = 1; q < Cm1; ++q) {
+    const T d = exp(kap[q]);
+    cj = cj + d;
+    tab[base + q * sj] = cj;
+    if (lgr) {
+      T lg, r;
+      glm_cut_gap(d, lg, r);
+      tab[((int64_t)Cm1 + q) * N + c] = lg;
+      tab[((int64_t)2 * Cm1 + q) * N + c] = r;
+    }
+  }
+}
+
+// (ℓ, u = ∂ℓ/∂η, da = ∂ℓ/∂a, db = ∂ℓ/∂b) of one observation in category yi of C: a = ca − η with ca = c_{y+1} (yi < C − 1),
+// b = cb − η with cb = c_y (yi > 0); lg, r: the constants of the gap between them (used by an interior category only).  softplus and
+// σ from one exp(−|x|) each, as FAM 0; no difference of two sigmoids is formed.
+template <class T>
+__device__ __forceinline__ void glm_link_ord(int yi, int Cm1, T eta, T ca, T cb, T lg, T r, T& ll, T& u, T& da, T& db) {
+  const bool ha = yi < Cm1, hb = yi > 0;
+  T spa = T(0), sna = T(0), spb = T(0), sb = T(0);
+  if (ha) {
+    const T a = ca - eta;
+    const T e = exp(-fabs(a));
+    const T d = T(1) + e;
+    spa = (a < T(0) ? -a : T(0)) + log1p(e);   // softplus(−a)
+    sna = a <= T(0) ? T(1) / d : e / d;        // σ(−a)
+  }
+  if (hb) {
+    const T b = cb - eta;
+    const T e = exp(-fabs(b));
+    const T d = T(1) + e;
+    spb = (b > T(0) ? b : T(0)) + log1p(e);    // softplus(b)
+    sb = b >= T(0) ? T(1) / d : e / d;         // σ(b)
+  }
+  const bool in = ha && hb;
+  ll = (-spa - spb) + (in ? lg : T(0));
+  u = sb - sna;
+  da = ha ? sna + (in ? r : T(0)) : T(0);
+  db = hb ? -sb - (in ? r : T(0)) : T(0);
+}
+
 // η = X·Θ + offset for the listed chains, and from it in registers u → U (n_obs, N) and the tile's Σ_rows ℓ → partial[row block][chain].
 // Tile rows are observations, tile columns chains, K = D.  η itself is stored only on request (ahmc_glm_pointwise: eta_out / ll_out,
 // (n_obs, N) arrays).  U leaves through LDS so that a wave writes 64 consecutive observations of one chain; ℓ is summed over the
 // tile's 64 rows in ascending row order by one thread per column (rows past n_obs contribute +0).
-// FAM >= 3: the chain's log dispersion s is read from aux[col·aux_ld] (row D_θ − 1 of the chain's own θ, not of `th`, which holds the
+// FAM 3 and 4: the chain's log dispersion s is read from aux[col·aux_ld] (row D_θ − 1 of the chain's own θ, not of `th`, which holds the
 // effective coefficients), once per tile column, and Σ_rows ∂ℓ/∂s goes to partial_s[row block][chain] by the same column sum.
+// FAM == 5 (include/ahmc_glm_ordinal.h): y holds the category 0 … C − 1; aux is the cutpoint table of k_glm_cut (3, C−1, N), aux_ld
+// = C − 1 and partial_s is partial_c (C−1, row blocks, N).  Each element gathers its chain's c / lg / r at the rows its y names from
+// the table in global memory (at most 45 values per chain: L1 serves them).  da goes to an LDS array of its own as it is made, db
+// through the tile buffers after ℓ; the column thread then forms, for k = 1 … C − 1, S_k of the tile: from +0, rows ascending, da
+// of a row with y = k − 1, db of a row with y = k, nothing otherwise.
 //
 // FAC (include/ahmc_glm_factor.h): the product runs over the D dense columns only, `th` has column stride ldw (the model's P rows), and
 // before the link each element takes W[off_f + lev[row, f]] of its chain's column for f = 0, 1, … in this order: what the fma chain
@@ -250,11 +328,25 @@ __device__ __forceinline__ void glm_eta_body(const T* __restrict__ X, const T* _
     glm_tile_product<T, BN>(X, (int64_t)n_obs, n_obs, m0, bcol >= 0 ? th + bcol * ldw : nullptr, 0, D, smem, acc);
   }
   const int wm = (w % S::WR) * 16 * S::MI, wn = (w / S::WR) * 16 * S::MI;
+  [[maybe_unused]] T* ord_da = nullptr;
+  [[maybe_unused]] int* ord_y = nullptr;
+  if constexpr (FAM == 5) {
+    __shared__ T s_da[GB_M * (BN + 1)];   // ∂ℓ/∂a, [row][column]
+    __shared__ int s_y[GB_M];             // the tile rows' categories (−1 past n_obs: matches no cutpoint)
+    ord_da = s_da;
+    ord_y = s_y;
+    if (tid < GB_M) s_y[tid] = m0 + tid < n_obs ? (int)y[m0 + tid] : -1;
+    __syncthreads();
+  }
   T ll[S::MI][S::MI][4];
-  constexpr int AM = FAM >= 3 ? S::MI : 1;          // (the legacy families carry none of the three)
+  constexpr bool AUXF = FAM == 3 || FAM == 4, ORD = FAM == 5;
+  constexpr int AM = AUXF ? S::MI : 1;              // (the legacy families carry none of the three)
   [[maybe_unused]] T ds[AM][AM][4];                 // ∂ℓ/∂s
   [[maybe_unused]] T sv[AM], cv[AM];                // s and exp(−2s) / exp(s) of this thread's tile columns
-  if constexpr (FAM >= 3) {
+  constexpr int OM = ORD ? S::MI : 1;
+  [[maybe_unused]] T dbv[OM][OM][4];                // ∂ℓ/∂b
+  [[maybe_unused]] const int Cm1 = ORD ? (int)aux_ld : 0;
+  if constexpr (AUXF) {
 #pragma unroll
     for (int tj = 0; tj < S::MI; ++tj) {
       const int64_t j = n0 + wn + tj * 16 + (lane & 15);
@@ -276,7 +368,7 @@ __device__ __forceinline__ void glm_eta_body(const T* __restrict__ X, const T* _
         const int rl = wm + ti * 16 + Mf::row(lane, v);
         const int row = m0 + rl;
         T l = T(0), u = T(0);
-        [[maybe_unused]] T dl = T(0);
+        [[maybe_unused]] T dl = T(0), dav = T(0), dbe = T(0);
         if (row < n_obs && col >= 0) {
           T eta = acc[ti][tj][v];
           if constexpr (FAC) {
@@ -285,12 +377,21 @@ __device__ __forceinline__ void glm_eta_body(const T* __restrict__ X, const T* _
             for (int f = 0; f < F; ++f) eta += wc[ft->off[f] + lev[row + (int64_t)f * n_obs]];
           }
           if (off) eta += off[row];
-          if constexpr (FAM >= 3) glm_link_aux<T, FAM>(y[row], eta, sv[tj], cv[tj], l, u, dl);
+          if constexpr (ORD) {
+            const int yi = ord_y[rl];
+            const int ia = yi < Cm1 ? yi : Cm1 - 1, ib = yi > 0 ? yi - 1 : 0;  // (clamped: the link ignores the side that does not exist)
+            const T* tc = aux + col;
+            glm_link_ord<T>(yi, Cm1, eta, tc[(int64_t)ia * N], tc[(int64_t)ib * N], tc[((int64_t)Cm1 + ia) * N], tc[((int64_t)2 * Cm1 + ia) * N], l, u, dav, dbe);
+          } else if constexpr (AUXF) glm_link_aux<T, FAM>(y[row], eta, sv[tj], cv[tj], l, u, dl);
           else glm_link<T, FAM>(y[row], eta, scale, l, u);
           if (eta_out) eta_out[row + col * n_obs] = eta;
           if (ll_out) ll_out[row + col * n_obs] = l;
         }
-        if constexpr (FAM >= 3) ds[ti][tj][v] = dl;
+        if constexpr (AUXF) ds[ti][tj][v] = dl;
+        if constexpr (ORD) {
+          dbv[ti][tj][v] = dbe;
+          ord_da[rl * (BN + 1) + cl] = dav;
+        }
         ll[ti][tj][v] = l;
         smem[cl * S::LDE + rl] = u;
       }
@@ -318,7 +419,30 @@ __device__ __forceinline__ void glm_eta_body(const T* __restrict__ X, const T* _
     for (int r = 0; r < GB_M; ++r) s += smem[r * (BN + 1) + tid];
     partial[(int64_t)rblk * N + col] = s;
   }
-  if constexpr (FAM >= 3) {
+  if constexpr (ORD) {
+    // ∂ℓ/∂b → smem[row][column] beside ∂ℓ/∂a; S_k of the tile, k outer, rows ascending, the term chosen by comparing y with k
+    __syncthreads();
+#pragma unroll
+    for (int ti = 0; ti < S::MI; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < S::MI; ++tj)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) smem[(wm + ti * 16 + Mf::row(lane, v)) * (BN + 1) + wn + tj * 16 + (lane & 15)] = dbv[ti][tj][v];
+    __syncthreads();
+    if (tid < BN && n0 + tid < ncols) {
+      const int64_t col = idx ? (int64_t)idx[n0 + tid] : n0 + tid;
+      for (int k = 1; k <= Cm1; ++k) {
+        T s = T(0);
+        for (int r = 0; r < GB_M; ++r) {
+          const int yr = ord_y[r];
+          if (yr == k - 1) s += ord_da[r * (BN + 1) + tid];
+          else if (yr == k) s += smem[r * (BN + 1) + tid];
+        }
+        partial_s[((int64_t)(k - 1) * nrb + rblk) * N + col] = s;
+      }
+    }
+  }
+  if constexpr (AUXF) {
     // ∂ℓ/∂s → smem[row][column], the same column sums
     __syncthreads();
 #pragma unroll
@@ -552,12 +676,21 @@ __global__ __launch_bounds__(256) void k_glm_exp_row(const T* __restrict__ th, i
 // AUX (include/ahmc_glm_aux.h): θ has one more row, s = the log of the family's dispersion, after the G log-scales.  Σ_row blocks
 // partial_s (= Σ_i ∂ℓ/∂s) is summed beside Σ partial in the same lane-strided order and by a butterfly of its own; after the groups
 // the prior s ~ Normal(m, A²) is added: r = s − m, ℓπ = fma((−½/A²)·r, r, ℓπ), g[D−1] = fma(r, 1/A², −Σ ∂ℓ/∂s).
-template <class T, bool AUX>
+//
+// ORD (include/ahmc_glm_ordinal.h): θ's last n_cut = C − 1 rows are κ, after the G log-scales.  The prior first, j ascending:
+// r_j = κ_j − loc, ℓπ = fma((−½/scale²)·r_j, r_j, ℓπ) with (loc_1, scale_1) for j = 1 and (loc_gap, scale_gap) above.  Then j
+// descending: S_j = Σ_row blocks partial_c[j] (lane-strided, a butterfly of its own, as partial_s), T_j = S_j + T_{j+1},
+// g[κ_1] = fma(r_1, 1/scale_1², −T_1), g[κ_j] = fma(−δ_j, T_j, r_j·(1/scale_gap²)) with δ_j = exp(κ_j), k_glm_cut's exp.
+struct GlmCutPrior {
+  double loc1, ia1, locg, iag;  // (loc_1, 1/scale_1², loc_gap, 1/scale_gap²)
+};
+
+template <class T, bool AUX, bool ORD = false>
 __device__ __forceinline__ void hglm_finish_body(const T* __restrict__ partial, const T* __restrict__ R, const T* __restrict__ W, const T* __restrict__ prec,
                                                  const T* __restrict__ th, const HglmTab<T>* __restrict__ tab, T* __restrict__ lp, T* __restrict__ g, int nrb, int P,
                                                  int G, int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp, const T* __restrict__ partial_s,
-                                                 T aux_loc, T aux_ia2) {
-  const int64_t ldt = (int64_t)P + G + (AUX ? 1 : 0);
+                                                 T aux_loc, T aux_ia2, int n_cut = 0, GlmCutPrior cp = {}) {
+  const int64_t ldt = (int64_t)P + G + (AUX ? 1 : 0) + (ORD ? n_cut : 0);
   const int lane = threadIdx.x & 63;
   const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= ncols) return;
@@ -617,7 +750,36 @@ __device__ __forceinline__ void hglm_finish_body(const T* __restrict__ partial, 
     v = fma((T(-0.5) * aux_ia2) * ra, ra, v);
     if (lane == 0) gc[P + G] = fma(ra, aux_ia2, -dsum[0]);
   }
+  if constexpr (ORD) {
+    const T* kap = t + P + G;
+    const T ia1 = (T)cp.ia1, iag = (T)cp.iag, loc1 = (T)cp.loc1, locg = (T)cp.locg;
+    for (int q = 0; q < n_cut; ++q) {
+      const T rq = kap[q] - (q == 0 ? loc1 : locg);
+      v = fma((T(-0.5) * (q == 0 ? ia1 : iag)) * rq, rq, v);
+    }
+    T Tq = T(0);
+    for (int q = n_cut - 1; q >= 0; --q) {
+      T sq[2] = {0, 0};
+      const T* pc = partial_s + (int64_t)q * nrb * N + c;
+      for (int rb = lane; rb < nrb; rb += 64) sq[0] += pc[(int64_t)rb * N];
+      wave_allsum2<64>(sq[0], sq[1]);
+      Tq = q == n_cut - 1 ? sq[0] : sq[0] + Tq;
+      const T kq = kap[q];
+      const T gq = q == 0 ? fma(kq - loc1, ia1, -Tq) : fma(-exp(kq), Tq, (kq - locg) * iag);
+      if (lane == 0) gc[P + G + q] = gq;
+    }
+  }
   if (lane == 0) lp[c] = sanitize_lp ? sanitize(v) : v;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_hglm_finish_ord(const T* __restrict__ partial, const T* __restrict__ partial_c, const T* __restrict__ R,
+                                                         const T* __restrict__ W, const T* __restrict__ prec, const T* __restrict__ th,
+                                                         const HglmTab<T>* __restrict__ tab, T* __restrict__ lp, T* __restrict__ g, int nrb, int P, int G,
+                                                         int64_t ncols, int64_t N, const int* __restrict__ idx, int sanitize_lp, int n_cut, double loc1,
+                                                         double ia1, double locg, double iag) {
+  hglm_finish_body<T, false, true>(partial, R, W, prec, th, tab, lp, g, nrb, P, G, ncols, N, idx, sanitize_lp, partial_c, T(0), T(0), n_cut,
+                                   GlmCutPrior{loc1, ia1, locg, iag});
 }
 
 template <class T>

@@ -22,9 +22,21 @@ struct HglmSpec {
   int F = 0;
   int64_t Px = 0;
   const int32_t *n_levels = nullptr, *levels = nullptr;
+  // ahmc_glm_ordinal_set_target: C categories, θ ends with the C − 1 rows κ; cut_prior = (loc_1, scale_1, loc_gap, scale_gap)
+  int n_cat = 0;
+  const double* cut_prior = nullptr;
 };
 
 inline bool glm_aux_family(int family) { return family == AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA || family == AHMC_GLM_NEGBINOMIAL_LOG; }
+
+// what the entry points of the older headers answer to AHMC_GLM_ORDERED_LOGIT
+inline std::string glm_ordinal_elsewhere(int family, bool aux) {
+  const std::string where = "it samples its cutpoints and is bound through ahmc_glm_ordinal_set_target (include/ahmc_glm_ordinal.h)";
+  if (aux)
+    return "glm_aux_set_target: family " + std::to_string(family) +
+           " has no sampled dispersion (AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA, AHMC_GLM_NEGBINOMIAL_LOG): " + where;
+  return "set_target_glm: unknown family " + std::to_string(family) + " at this entry point: " + where;
+}
 
 template <class T>
 int glm_slices(const Ctx<T>* c) {
@@ -57,12 +69,20 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
   const T* aux = m.aux ? c->th + (c->D - 1) : nullptr;
   T* part_s = m.aux ? m.at(GLM_PART_S) : nullptr;
   if (glm_aux_family(m.family) != m.aux) return fail(c, AHMC_ERR_STATE, "glm: the family and the dispersion row disagree in the context");
+  if ((m.family == AHMC_GLM_ORDERED_LOGIT) != (m.n_cat > 0)) return fail(c, AHMC_ERR_STATE, "glm: the family and the cutpoint rows disagree in the context");
+  // an ordinal model: the cutpoint table k_glm_cut made, C − 1, and partial_c take the places of s, its stride and partial_s
+  int64_t aux_ld = c->D;
+  if (m.n_cat > 0) {
+    aux = m.at(GLM_CUT);
+    aux_ld = m.n_cat - 1;
+    part_s = m.at(GLM_PART_C);
+  }
   const dim3 grid = small ? dim3((unsigned)nrb, (unsigned)((ncols + 15) / 16)) : dim3((unsigned)(nrb * (((ncols + GB_N - 1) / GB_N + 7) / 8 * 8)));
 #define AHMC_GLM_ETA(FAM, BN) \
-  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)m.scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out, aux, (int64_t)c->D, part_s)
+  hipLaunchKernelGGL((k_glm_eta<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)m.scale, th, U, part, n_obs, D, ncols, c->N, list, eta_out, ll_out, aux, aux_ld, part_s)
 #define AHMC_GLM_ETA_F(FAM, BN)                                                                                                                          \
   hipLaunchKernelGGL((k_glm_eta_f<T, FAM, BN>), grid, dim3(256), 0, c->stream, X, y, off, (T)m.scale, th, U, part, n_obs, (int)m.Px, (int64_t)D, ncols, c->N, list, \
-                     eta_out, ll_out, aux, (int64_t)c->D, part_s, m.ftab(), m.ints(GLM_LEV))
+                     eta_out, ll_out, aux, aux_ld, part_s, m.ftab(), m.ints(GLM_LEV))
   if (m.F > 0) {
     if (D != m.P) return fail(c, AHMC_ERR_STATE, "glm: a model with factors runs on its P rows of W");
     switch (m.family * 2 + (small ? 1 : 0)) {
@@ -76,6 +96,8 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
       case 7: AHMC_GLM_ETA_F(3, 16); break;
       case 8: AHMC_GLM_ETA_F(4, 64); break;
       case 9: AHMC_GLM_ETA_F(4, 16); break;
+      case 10: AHMC_GLM_ETA_F(5, 64); break;
+      case 11: AHMC_GLM_ETA_F(5, 16); break;
       default: return fail(c, AHMC_ERR_STATE, "glm: unknown family in the context");
     }
     HIPCHK(hipGetLastError());
@@ -93,11 +115,21 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
     case 7: AHMC_GLM_ETA(3, 16); break;
     case 8: AHMC_GLM_ETA(4, 64); break;
     case 9: AHMC_GLM_ETA(4, 16); break;
+    case 10: AHMC_GLM_ETA(5, 64); break;
+    case 11: AHMC_GLM_ETA(5, 16); break;
     default: return fail(c, AHMC_ERR_STATE, "glm: unknown family in the context");
   }
 #undef AHMC_GLM_ETA
   HIPCHK(hipGetLastError());
   return AHMC_OK;
+}
+
+// an ordinal model's cutpoint table (c, lg, r) of the listed chains from the κ rows of the context's θ, before k_glm_eta
+template <class T>
+void glm_launch_cut(Ctx<T>* c, const int* list, int64_t n) {
+  const GlmModel<T>& m = c->glm;
+  hipLaunchKernelGGL((k_glm_cut<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const T*)c->th, c->D, c->D - (m.n_cat - 1), m.n_cat - 1,
+                     m.at(GLM_CUT), c->N, n, list, 1);
 }
 
 // few columns: the 64×16 tiles put 4× as many workgroups on the chip (dn_gemm's rule; same arithmetic per column, so the
@@ -128,6 +160,7 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   const T* prec = m.at(hier ? GLM_ZERO : GLM_PREC);
   T* g = hier ? m.at(GLM_R) : c->g;
   if (hier) hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, m.tab(), m.at(GLM_W), (T*)nullptr, D, G, c->D, n, list);
+  if (m.n_cat > 0) glm_launch_cut(c, list, n);
   int rc = glm_launch_eta(c, th, D, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr);
   if (rc) return rc;
   const T* Xt = m.at(GLM_XT);
@@ -152,7 +185,12 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
     if (ns > 1)
       hipLaunchKernelGGL((k_glm_gsum<T>), dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, th, g, D, n, c->N, list, ns);
   }
-  if (m.aux)
+  if (m.n_cat > 0) {
+    const double* q = m.cut_prior;
+    hipLaunchKernelGGL((k_hglm_finish_ord<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)m.at(GLM_PART), (const T*)m.at(GLM_PART_C),
+                       (const T*)g, th, (const T*)m.at(GLM_PREC), (const T*)c->th, m.tab(), c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0,
+                       m.n_cat - 1, q[0], 1.0 / (q[1] * q[1]), q[2], 1.0 / (q[3] * q[3]));
+  } else if (m.aux)
     hipLaunchKernelGGL((k_hglm_finish_aux<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)m.at(GLM_PART), (const T*)m.at(GLM_PART_S),
                        (const T*)g, th, (const T*)m.at(GLM_PREC), (const T*)c->th, m.tab(), c->lp, c->g, (int)nrb, D, G, n, c->N, list, sanitize_lp ? 1 : 0,
                        (T)m.aux_loc, (T)(1.0 / (m.aux_scale * m.aux_scale)));
@@ -169,17 +207,19 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
 template <class T>
 int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, const HglmSpec* hs = nullptr) {
   const int G = hs ? hs->G : 0;
-  const bool aux = hs && hs->aux, on_w = G > 0 || aux || (hs && hs->F > 0);
+  const int n_cat = hs ? hs->n_cat : 0;  // (> 0: checked by glm_ordinal_set)
+  const bool aux = hs && hs->aux, on_w = G > 0 || aux || (hs && hs->F > 0) || n_cat > 0;
   const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the coefficient rows: the record's P)
   const int F = hs ? hs->F : 0;
   const int64_t Px = F > 0 ? hs->Px : D, Lt = D - Px;  // (the columns of X; the factors' levels together)
+  if (family == AHMC_GLM_ORDERED_LOGIT && n_cat == 0) return fail(c, AHMC_ERR_ARGUMENT, glm_ordinal_elsewhere(family, aux));
   if (glm_aux_family(family) && !aux)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family) +
                                           " at this entry point: it samples its dispersion and is bound through ahmc_glm_aux_set_target (include/ahmc_glm_aux.h)");
   if (aux && !glm_aux_family(family))
     return fail(c, AHMC_ERR_ARGUMENT, "glm_aux_set_target: family " + std::to_string(family) +
                                           " has no sampled dispersion (AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA, AHMC_GLM_NEGBINOMIAL_LOG)");
-  if (!aux && family != AHMC_GLM_BERNOULLI_LOGIT && family != AHMC_GLM_POISSON_LOG && family != AHMC_GLM_GAUSSIAN_IDENTITY)
+  if (!aux && n_cat == 0 && family != AHMC_GLM_BERNOULLI_LOGIT && family != AHMC_GLM_POISSON_LOG && family != AHMC_GLM_GAUSSIAN_IDENTITY)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family));
   if (n_obs < 1) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: n_obs must be >= 1; got " + std::to_string(n_obs));
   if (n_obs > AHMC_GLM_MAX_OBS)
@@ -190,7 +230,8 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   // the slab: X, Xᵀ, y, offset, p [, a zero precision, the group table], then the workspaces U, partial [, partial_s], gs [, W, R]
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, ns = (n_obs + GLM_K_SLICE - 1) / GLM_K_SLICE;
   const int64_t tab_elems = (int64_t)((sizeof(HglmTab<T>) + sizeof(T) - 1) / sizeof(T));
-  int64_t sizes[GLM_PARTS] = {n_obs * Px, n_obs * Px, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * Px * N : 0, 0, 0, 0, 0, aux ? nrb * N : 0, 0, 0, 0, 0};
+  int64_t sizes[GLM_PARTS] = {n_obs * Px, n_obs * Px, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * Px * N : 0, 0, 0, 0, 0, aux ? nrb * N : 0, 0, 0, 0, 0,
+                              n_cat > 0 ? 3 * (int64_t)(n_cat - 1) * N : 0, n_cat > 0 ? (int64_t)(n_cat - 1) * nrb * N : 0};
   if (on_w) {
     sizes[GLM_W] = sizes[GLM_R] = D * N;
     sizes[GLM_ZERO] = D;
@@ -203,7 +244,7 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
     sizes[GLM_RP] = int_elems(Lt + 1);
   }
   const int layout[GLM_PARTS] = {GLM_X,   GLM_XT, GLM_Y,    GLM_OFF,    GLM_PREC, GLM_ZERO, GLM_TAB, GLM_FTAB, GLM_LEV,
-                                 GLM_PERM, GLM_RP, GLM_U,    GLM_PART,   GLM_PART_S, GLM_GS,  GLM_W,   GLM_R};
+                                 GLM_PERM, GLM_RP, GLM_U,    GLM_PART,   GLM_PART_S, GLM_GS,  GLM_W,   GLM_R,   GLM_CUT, GLM_PART_C};
   GlmModel<T> m;  // (becomes the context's once nothing can fail any more)
   int64_t* const off = m.off;
   int64_t total = 0;
@@ -224,7 +265,13 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
     const double yi = (double)h[off[GLM_Y] + i];
     if (!std::isfinite((double)h[off[GLM_OFF] + i])) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: offset holds a non-finite value");
     const bool counts = family == AHMC_GLM_POISSON_LOG || family == AHMC_GLM_NEGBINOMIAL_LOG;
-    const bool ok = family == AHMC_GLM_BERNOULLI_LOGIT ? (yi >= 0 && yi <= 1) : counts ? (std::isfinite(yi) && yi >= 0) : std::isfinite(yi);
+    const bool ok = n_cat > 0                            ? (yi >= 0 && yi < n_cat && yi == std::floor(yi))
+                    : family == AHMC_GLM_BERNOULLI_LOGIT ? (yi >= 0 && yi <= 1)
+                    : counts                             ? (std::isfinite(yi) && yi >= 0)
+                                                         : std::isfinite(yi);
+    if (!ok && n_cat > 0)
+      return fail(c, AHMC_ERR_ARGUMENT, "DomainError: y[" + std::to_string(i + 1) + "] = " + std::to_string(yi) + " is not a category: an integer in [0, " +
+                                            std::to_string(n_cat) + ")");
     if (!ok)
       return fail(c, AHMC_ERR_ARGUMENT, "DomainError: y[" + std::to_string(i + 1) + "] = " + std::to_string(yi) + " is outside the family's domain (" +
                                             (family == AHMC_GLM_BERNOULLI_LOGIT ? "0 <= y <= 1" : counts ? "y >= 0, finite" : "finite") + ")");
@@ -284,6 +331,7 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
     return fail(c, AHMC_ERR_RUNTIME, "set_target_glm: cannot allocate " + std::to_string((long long)(sizeof(T) * (size_t)total)) + " bytes for the model (" +
                                          std::to_string((long long)(sizeof(T) * (size_t)n_data)) + ") and its workspaces U (n_obs × N), partial and the slice sums" +
                                          (on_w ? ", W and R (n_coef × N)" : "") + (aux ? ", partial_s" : "") +
+                                         (n_cat > 0 ? ", the cutpoint table (3 × (C − 1) × N) and partial_c" : "") +
                                          (F > 0 ? "; the model holds the level indices, permutations and row pointers of " + std::to_string(F) + " factors" : ""));
   }
   if (hipMemcpy(m.buf, h.data(), sizeof(T) * (size_t)n_data, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
@@ -304,6 +352,9 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   m.bound_hier = hs != nullptr;
   m.aux = aux;
   if (aux) { m.aux_loc = hs->aux_loc; m.aux_scale = hs->aux_scale; }
+  m.n_cat = n_cat;
+  if (n_cat > 0)
+    for (int i = 0; i < 4; ++i) m.cut_prior[i] = hs->cut_prior[i];
   c->glm = m;
   c->target_kind = AHMC_TARGET_GLM;
   c->have_point = false;
@@ -329,6 +380,7 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
                        c->D, c->N, (const int*)nullptr);
     th = m.at(GLM_W);
   }
+  if (m.n_cat > 0) glm_launch_cut(c, (const int*)nullptr, c->N);
   int rc = glm_launch_eta(c, th, (int)m.P, (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_out ? tmp : (T*)nullptr, ll_out ? tmp + n : (T*)nullptr);
   hipError_t e = hipSuccess;
   if (!rc && eta_out) e = hipMemcpyAsync(eta_out, tmp, sizeof(T) * n, hipMemcpyDefault, c->stream);
@@ -346,6 +398,7 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const
   const int64_t n_coef = hs.P;
   const int n_groups = hs.G;
   const bool aux = hs.aux;
+  if (family == AHMC_GLM_ORDERED_LOGIT && hs.n_cat == 0) return fail(c, AHMC_ERR_ARGUMENT, glm_ordinal_elsewhere(family, aux));  // (whatever D is)
   if (n_groups < 0) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: n_groups must be >= 0; got " + std::to_string(n_groups));
   if (aux && n_groups > AHMC_GLM_AUX_MAX_GROUPS)
     return fail(c, AHMC_ERR_UNSUPPORTED, "glm_aux_set_target: n_groups = " + std::to_string(n_groups) + " is beyond the engine's limit AHMC_GLM_AUX_MAX_GROUPS = " +
@@ -353,9 +406,11 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const
   if (n_groups > AHMC_HGLM_MAX_GROUPS)
     return fail(c, AHMC_ERR_UNSUPPORTED, "hglm_set_target: n_groups = " + std::to_string(n_groups) + " is beyond the engine's limit AHMC_HGLM_MAX_GROUPS = " +
                                              std::to_string(AHMC_HGLM_MAX_GROUPS));
-  if (n_coef < 1 || c->D != n_coef + n_groups + (aux ? 1 : 0))
+  const int n_cut = hs.n_cat > 0 ? hs.n_cat - 1 : 0;
+  if (n_coef < 1 || c->D != n_coef + n_groups + (aux ? 1 : 0) + n_cut)
     return fail(c, AHMC_ERR_ARGUMENT, "DimensionMismatch: the context has D = " + std::to_string((long long)c->D) + ", the model n_coef + n_groups = " +
                                           std::to_string((long long)n_coef) + " + " + std::to_string(n_groups) + (aux ? " (+ 1: the dispersion's row)" : "") +
+                                          (n_cut ? " + " + std::to_string(n_cut) + " (n_categories - 1: the cutpoints' rows)" : "") +
                                           (hs.F > 0 ? " (n_coef: " + std::to_string((long long)hs.Px) + " columns of X and the factors' levels)" : ""));
   if (aux && !std::isfinite(hs.aux_loc)) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_loc = " + std::to_string(hs.aux_loc) + " must be finite");
   if (aux && !(std::isfinite(hs.aux_scale) && hs.aux_scale > 0))
@@ -407,6 +462,25 @@ int glm_factor_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y,
     }
   hs.P = P;
   return hglm_set(c, family, n_obs, X, y, offset, prec, scale, hs);
+}
+
+// ---- include/ahmc_glm_ordinal.h ----
+// hs as glm_factor_set takes it (hs.F may be 0); the family is AHMC_GLM_ORDERED_LOGIT, there is no scale and no dispersion
+template <class T>
+int glm_ordinal_set(Ctx<T>* c, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, HglmSpec hs, int32_t n_categories, const double* cut_prior) {
+  if (n_categories < 2)
+    return fail(c, AHMC_ERR_ARGUMENT, "DomainError: n_categories = " + std::to_string(n_categories) + "; an ordered outcome has at least 2 categories");
+  if (n_categories > AHMC_GLM_ORDINAL_MAX_CATEGORIES)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "glm_ordinal_set_target: n_categories = " + std::to_string(n_categories) +
+                                             " is beyond the engine's limit AHMC_GLM_ORDINAL_MAX_CATEGORIES = " + std::to_string(AHMC_GLM_ORDINAL_MAX_CATEGORIES));
+  if (!cut_prior) return fail(c, AHMC_ERR_ARGUMENT, "glm_ordinal_set_target: cut_prior is NULL");
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(cut_prior[i]) || (i % 2 == 1 && !(cut_prior[i] > 0)))
+      return fail(c, AHMC_ERR_ARGUMENT, "DomainError: cut_prior[" + std::to_string(i + 1) + "] = " + std::to_string(cut_prior[i]) +
+                                            (i % 2 == 1 ? " must be finite and > 0 (a scale)" : " must be finite (a location)"));
+  hs.n_cat = n_categories;
+  hs.cut_prior = cut_prior;
+  return glm_factor_set(c, AHMC_GLM_ORDERED_LOGIT, n_obs, X, y, offset, prec, 1.0, hs);
 }
 
 // ahmc_hglm_coefficients and ahmc_glm_dispersion: a temporary of `elems` elements that begins with the n_theta elements of the
@@ -467,5 +541,24 @@ int glm_dispersion(Ctx<T>* c, const void* theta, int64_t n_cols, void* out) {
     hipLaunchKernelGGL((k_glm_exp_row<T>), dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, c->stream, (const T*)th, D, D - 1, n_cols, e_s);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : hipMemcpyAsync(out, e_s, sizeof(T) * (size_t)n_cols, hipMemcpyDefault, c->stream);
+  });
+}
+
+// ---- include/ahmc_glm_ordinal.h ----
+// the cutpoints c (C−1, n_cols) of any (D, n_cols) array of draws, host or device pointers: κ is each column's last C − 1 rows
+template <class T>
+int glm_cutpoints(Ctx<T>* c, const void* theta, int64_t n_cols, void* out) {
+  if (c->target_kind != AHMC_TARGET_GLM || !c->glm.buf || c->glm.n_cat == 0)
+    return fail(c, AHMC_ERR_ARGUMENT, "glm_cutpoints: no ordinal model is bound (ahmc_glm_ordinal_set_target)");
+  if (n_cols < 0 || (n_cols > 0 && (!theta || !out))) return fail(c, AHMC_ERR_ARGUMENT, "glm_cutpoints: theta or out is NULL, or n_cols < 0");
+  if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, "glm_cutpoints: n_cols beyond 2^31 - 1");
+  if (n_cols == 0) return AHMC_OK;
+  const int64_t D = c->D, Cm1 = c->glm.n_cat - 1;
+  return glm_on_draws(c, "glm_cutpoints", theta, (size_t)(D * n_cols), (size_t)((D + Cm1) * n_cols), [&](T* th) {
+    T* cut = th + D * n_cols;
+    hipLaunchKernelGGL((k_glm_cut<T>), dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, c->stream, (const T*)th, D, D - Cm1, (int)Cm1, cut, n_cols, n_cols,
+                       (const int*)nullptr, 0);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipMemcpyAsync(out, cut, sizeof(T) * (size_t)(Cm1 * n_cols), hipMemcpyDefault, c->stream);
   });
 }

@@ -473,6 +473,19 @@ def _link_at(fam, X, th, groups, factors, y, offset, scale):
     return (W, tau, eta, *link(fam, np.asarray(y, dtype=np.float64).reshape(-1, 1), eta, scale, th[P + G:] if fam in AUX_FAMILIES else None))
 
 
+def _xtu(X, u, W, factors):
+    """Xᵀu (P, N) by slices of K_SLICE observations, the slice sums added in ascending order; the factors' rows by ordered additions"""
+    Px = X.shape[1]
+    xtu = np.zeros_like(W)
+    for k0 in range(0, X.shape[0], K_SLICE):
+        part = np.zeros_like(W)
+        part[:Px] = X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
+        for (lo, _), (idx, _) in zip(factor_ranges(Px, factors), factors):
+            np.add.at(part, lo + idx[k0:k0 + K_SLICE], u[k0:k0 + K_SLICE])   # (in order: ascending i within the slice)
+        xtu = xtu + part
+    return xtu
+
+
 def _logdensity(fam, X, th, groups, p, aux, factors, y, offset, scale=1.0):
     """(ℓπ, ∇ℓπ) of every model: `groups` and `factors` checked (maybe none), p (P), `aux` = (m, A) of the prior of s or None"""
     Px = X.shape[1]
@@ -480,13 +493,7 @@ def _logdensity(fam, X, th, groups, p, aux, factors, y, offset, scale=1.0):
     W, tau, _, ll, u, *ds = _link_at(fam, X, th, groups, factors, y, offset, scale)
     with np.errstate(over="ignore", invalid="ignore"):
         lsum = block_sums(ll).sum(axis=0)
-        xtu = np.zeros_like(W)
-        for k0 in range(0, X.shape[0], K_SLICE):
-            part = np.zeros_like(W)
-            part[:Px] = X[k0:k0 + K_SLICE].T @ u[k0:k0 + K_SLICE]
-            for (lo, _), (idx, _) in zip(factor_ranges(Px, factors), factors):
-                np.add.at(part, lo + idx[k0:k0 + K_SLICE], u[k0:k0 + K_SLICE])   # (in order: ascending i within the slice)
-            xtu = xtu + part
+        xtu = _xtu(X, u, W, factors)
         g = np.empty_like(th)
         lp, g[:PG] = _hier_finish(th[:PG], W, tau, -xtu, lsum, p, groups)
         if aux is not None:
@@ -496,4 +503,183 @@ def _logdensity(fam, X, th, groups, p, aux, factors, y, offset, scale=1.0):
             r = th[-1] - m
             lp = lp + ((-0.5 * ia2) * r) * r
             g[-1] = r * ia2 - dsum
+    return lp, -g
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# include/ahmc_glm_ordinal.h: the ordered-logit family, whose cutpoints are sampled (csrc/ahmc_glm.hpp: k_glm_cut, glm_link_ord,
+# k_glm_eta<T, 5, BN>, k_hglm_finish_ord)
+# ------------------------------------------------------------------------------------------------------------------------------
+__doc__ += """
+The ordered-logit family (ordinal_logdensity, ordinal_pointwise, ordinal_link, cutpoints, ordinal_probs):
+    y_i ∈ {0, …, C − 1};  c_1 < … < c_{C−1};  P(y <= k) = σ(c_{k+1} − η);  no intercept (a constant column of X is not identified).
+    θ (D, N), D = P + G + (C − 1): the P coefficient parameters and the G log-scales as above, then LAST the C − 1 rows κ:
+    κ_1 = c_1, κ_j = log(c_j − c_{j−1}) for j >= 2.  Prior on κ itself (no Jacobian term): κ_1 ~ Normal(loc_1, scale_1²),
+    κ_j ~ Normal(loc_gap, scale_gap²); cut_prior = (loc_1, scale_1, loc_gap, scale_gap), default (0, 2.5, 0, 1).
+    Once per (chain, cutpoint), j ascending:  c_1 = κ_1;  δ_j = exp(κ_j), c_j = c_{j−1} + δ_j;
+        lg_j = log(−expm1(−δ_j)) for δ_j <= log 2, log1p(−exp(−δ_j)) above;  r_j = 1/expm1(δ_j);  lg_1 = r_1 = 0.
+    Per element, a = c_{y+1} − η (y < C − 1), b = c_y − η (y > 0); e = exp(−|x|), softplus(x) = max(x, 0) + log1p(e), σ(x) = 1/(1 + e)
+    for x >= 0 and e/(1 + e) below — softplus(−a) and σ(−a) from one e, softplus(b) and σ(b) from another; a side that does not exist
+    contributes exact zeros:
+        ℓ = (−softplus(−a) − softplus(b)) + lg_{y+1},   da = σ(−a) + r_{y+1},   db = −σ(b) − r_{y+1},   u = σ(b) − σ(−a)
+    with lg and r only for an interior category (0 < y < C − 1).  No difference of two sigmoids is formed:
+    σ(a) − σ(b) = σ(a)·σ(−b)·(1 − e^{b−a}) and a − b = δ_{y+1} does not depend on the observation.
+    S_k = Σ_{y_i = k−1} da_i + Σ_{y_i = k} db_i (k = 1 … C − 1);  T_{C−1} = S_{C−1}, T_j = S_j + T_{j+1};  ∂ℓ/∂κ_1 = T_1, ∂ℓ/∂κ_j = δ_j·T_j.
+    ℓπ = [the hierarchical ℓπ over the first P + G rows, with Σℓ from above] − ½ Σ_j ((κ_j − loc)/scale)².
+Order of the new sums (Σℓ, X·W and Xᵀu keep theirs):
+  * S_k: per block of ROW_BLOCK observations from +0 in ascending row order — a row with y = k − 1 adds its da, a row with y = k its db,
+    any other row nothing — to partial_c[k][row block][chain]; the blocks then lane-strided ascending and the butterfly, as Σ_i ∂ℓ/∂s;
+  * the prior, after the groups' terms, j ascending:  r_j = κ_j − loc,  ℓπ = fma((−½·(1/scale²))·r_j, r_j, ℓπ);
+  * then j descending:  T_j = S_j + T_{j+1};  g[κ_1] = fma(r_1, 1/scale_1², −T_1);  g[κ_j] = fma(−δ_j, T_j, r_j·(1/scale_gap²)), with
+    δ_j = exp(κ_j) once more (the same exp of the same κ_j: the same bits).
+A chain's bits depend on (n_obs, P, groups, factors, C, element type) only.  δ_j overflows at κ_j ≈ 710 (89 in Float32): an observation
+at or above category j − 1 then has ℓ = −∞ and ℓπ is sanitised to −Inf; κ_j → −∞ closes the gap (lg → −∞, r → ∞) but stays finite
+down to κ_j ≈ −700.
+"""
+
+ORDERED_LOGIT = 5
+ORDINAL_FAMILIES = {"ordered_logit": ORDERED_LOGIT}
+ORDINAL_MAX_CATEGORIES = 16   # AHMC_GLM_ORDINAL_MAX_CATEGORIES
+CUT_PRIOR = (0.0, 2.5, 0.0, 1.0)
+_LOG2 = 0.6931471805599453
+
+
+def check_cut_prior(cut_prior):
+    """(loc_1, scale_1, loc_gap, scale_gap) of the prior on κ; all finite, both scales > 0.  None: the default (0, 2.5, 0, 1)"""
+    cp = CUT_PRIOR if cut_prior is None else tuple(float(v) for v in cut_prior)
+    if len(cp) != 4:
+        raise ValueError(f"ArgumentError: cut_prior = (loc_1, scale_1, loc_gap, scale_gap); got {len(cp)} entries")
+    for i, v in enumerate(cp):
+        if not np.isfinite(v) or (i % 2 == 1 and not v > 0):
+            raise ValueError(f"DomainError: cut_prior[{i + 1}] = {v} must be finite" + (" and > 0 (a scale)" if i % 2 else " (a location)"))
+    return cp
+
+
+def check_categories(y, n_categories):
+    """y as int64 categories in [0, C), 2 <= C <= ORDINAL_MAX_CATEGORIES"""
+    C = int(n_categories)
+    if not 2 <= C <= ORDINAL_MAX_CATEGORIES:
+        raise ValueError(f"DomainError: n_categories = {C}; must be in [2, {ORDINAL_MAX_CATEGORIES}]")
+    y = np.asarray(y, dtype=np.float64).ravel()
+    bad = np.flatnonzero(~((y >= 0) & (y < C) & (y == np.floor(y))))
+    if bad.size:
+        raise ValueError(f"DomainError: y[{int(bad[0]) + 1}] = {y[bad[0]]} is not a category: an integer in [0, {C})")
+    return y.astype(np.int64), C
+
+
+def cut_constants(kappa):
+    """(c, lg, r, δ), each (C − 1, N), from κ (C − 1, N) in κ's floating type: what k_glm_cut writes (δ_1 is set to 1: ∂c_1/∂κ_1)"""
+    k = np.asarray(kappa)
+    k = k.astype(np.float64) if k.dtype.kind != "f" else k          # (float32: a Float32 context's arithmetic; long double: a reference)
+    k = k.reshape(-1, 1) if k.ndim == 1 else k
+    one = k.dtype.type(1)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        d = np.exp(k)
+        d[0] = one
+        c = np.add.accumulate(np.concatenate([k[:1], d[1:]]), axis=0)   # (sequential: c_j = c_{j−1} + δ_j ascending)
+        em = np.exp(-d)
+        lg = np.where(d <= k.dtype.type(_LOG2), np.log(-np.expm1(-d)), np.log1p(-em))
+        r = one / np.expm1(d)
+        lg[0] = 0
+        r[0] = 0
+    return c, lg, r, d
+
+
+def cutpoints(kappa):
+    """c (C − 1, n) of κ (C − 1, n): c_1 = κ_1, c_j = c_{j−1} + exp(κ_j) ascending — the mirror of ahmc_glm_cutpoints on the last C − 1
+    rows of draws.  A vector gives a vector."""
+    k = np.asarray(kappa)
+    c = cut_constants(k)[0]
+    return c[:, 0] if k.ndim == 1 else c
+
+
+def ordinal_link(y, eta, c, lg, r):
+    """(ℓ, u = ∂ℓ/∂η, da = ∂ℓ/∂a, db = ∂ℓ/∂b) elementwise in η's floating type: y integer categories (n_obs,), η (n_obs, N), and
+    c, lg, r (C − 1, N) from `cut_constants`"""
+    eta = np.asarray(eta)
+    eta = eta.astype(np.float64) if eta.dtype.kind != "f" else eta
+    y = np.asarray(y).astype(np.int64)
+    Cm1 = c.shape[0]
+    ia, ib = np.minimum(y, Cm1 - 1), np.maximum(y - 1, 0)     # (clamped: the side that does not exist is masked below)
+    shape = y.shape + (1,) * (eta.ndim - y.ndim)
+    ha, hb = (y < Cm1).reshape(shape), (y > 0).reshape(shape)
+    inn = ha & hb
+    zero = eta.dtype.type(0)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        a = c[ia] - eta
+        e = np.exp(-np.abs(a))
+        d = 1 + e
+        spa = np.where(ha, np.where(a < 0, -a, zero) + np.log1p(e), zero)
+        sna = np.where(ha, np.where(a <= 0, 1 / d, e / d), zero)
+        b = c[ib] - eta
+        e = np.exp(-np.abs(b))
+        d = 1 + e
+        spb = np.where(hb, np.where(b > 0, b, zero) + np.log1p(e), zero)
+        sb = np.where(hb, np.where(b >= 0, 1 / d, e / d), zero)
+        lgv, rv = np.where(inn, lg[ia], zero), np.where(inn, r[ia], zero)
+        return (-spa - spb) + lgv, sb - sna, np.where(ha, sna + rv, zero), np.where(hb, -sb - rv, zero)
+
+
+def ordinal_probs(eta, c):
+    """(C, …) category probabilities at η (n_obs, N) [or (n_obs,)] and cutpoints c (C − 1, N) [or (C − 1,)], for posterior-predictive
+    use: exp of `ordinal_link`'s ℓ at every category, the gaps' constants from δ_j = c_j − c_{j−1}"""
+    eta, c = np.asarray(eta, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    vec = eta.ndim == 1
+    eta2, c2 = (eta.reshape(-1, 1) if vec else eta), (c.reshape(-1, 1) if c.ndim == 1 else c)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        d = np.diff(c2, axis=0, prepend=c2[:1])
+        lg = np.where(d <= _LOG2, np.log(-np.expm1(-d)), np.log1p(-np.exp(-d)))
+        lg[0] = 0
+        out = np.stack([np.exp(ordinal_link(np.full(eta2.shape[0], k), eta2, c2, lg, np.zeros_like(lg))[0]) for k in range(c2.shape[0] + 1)])
+    return out[:, :, 0] if vec else out
+
+
+def _ordinal_args(X, y, theta, n_categories, groups, factors):
+    y, C = check_categories(y, n_categories)
+    X = np.asarray(X, dtype=np.float64)
+    factors = check_factors(factors, X.shape[0])
+    P = X.shape[1] + sum(L for _, L in factors)
+    th = np.ascontiguousarray(theta, dtype=np.float64)
+    th = th.reshape(-1, 1) if th.ndim == 1 else th
+    groups = check_groups(groups, P)
+    if y.size != X.shape[0]:
+        raise ValueError(f"DimensionMismatch: X {X.shape}, y {y.shape}")
+    if th.shape[0] != P + len(groups) + C - 1:
+        raise ValueError(f"DimensionMismatch: θ {th.shape}, P + G + (C − 1) = {P} + {len(groups)} + {C - 1}")
+    return X, y, th, C, groups, factors, P + len(groups)
+
+
+def _ordinal_at(X, y, th, PG, groups, factors, offset):
+    """(W, τ, η, c, lg, r, δ, *`ordinal_link`'s values): the coefficient rows through `_link_at`'s path with a family that ignores y"""
+    W, tau, eta = _link_at(GAUSSIAN_IDENTITY, X, th[:PG], groups, factors, np.zeros(X.shape[0]), offset, 1.0)[:3]
+    c, lg, r, d = cut_constants(th[PG:])
+    return (W, tau, eta, c, lg, r, d, *ordinal_link(y, eta, c, lg, r))
+
+
+def ordinal_pointwise(X, y, theta, n_categories, groups=(), offset=None, factors=None):
+    """(η, ℓ(y_i, η_i)), each (n_obs, N): the mirror of ahmc_glm_pointwise on an ordinal model"""
+    X, y, th, C, groups, factors, PG = _ordinal_args(X, y, theta, n_categories, groups, factors)
+    out = _ordinal_at(X, y, th, PG, groups, factors, offset)
+    return out[2], out[7]
+
+
+def ordinal_logdensity(X, y, theta, n_categories, groups=(), offset=None, prior_prec=None, cut_prior=None, factors=None):
+    """(ℓπ (N,), ∇ℓπ (D, N)) at θ (D, N), D = P + G + (C − 1), of the ordered-logit model.  ℓπ is returned as computed (`sanitize`)."""
+    X, y, th, C, groups, factors, PG = _ordinal_args(X, y, theta, n_categories, groups, factors)
+    loc1, sc1, locg, scg = check_cut_prior(cut_prior)
+    p = _prior_prec(prior_prec, PG - len(groups), groups)
+    W, tau, _, _, _, _, d, ll, u, da, db = _ordinal_at(X, y, th, PG, groups, factors, offset)
+    yc = y.reshape(-1, 1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        g = np.empty_like(th)
+        lp, g[:PG] = _hier_finish(th[:PG], W, tau, -_xtu(X, u, W, factors), block_sums(ll).sum(axis=0), p, groups)
+        kap = th[PG:]
+        S = [block_sums(np.where(yc == k - 1, da, np.where(yc == k, db, 0.0))).sum(axis=0) for k in range(1, C)]
+        for j in range(C - 1):
+            rj = kap[j] - (loc1 if j == 0 else locg)
+            lp = lp + ((-0.5 * (1.0 / (sc1 * sc1) if j == 0 else 1.0 / (scg * scg))) * rj) * rj
+        T = np.zeros_like(lp)
+        for j in range(C - 2, -1, -1):
+            T = S[j] if j == C - 2 else S[j] + T
+            g[PG + j] = (kap[j] - loc1) * (1.0 / (sc1 * sc1)) - T if j == 0 else -d[j] * T + (kap[j] - locg) * (1.0 / (scg * scg))
     return lp, -g

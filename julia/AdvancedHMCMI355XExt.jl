@@ -519,5 +519,6 @@ include("AdvancedHMCMI355XGLM.jl")  # set_target!(z, ::GLMTarget), glm_pointwise
 include("AdvancedHMCMI355XGLMHier.jl")  # set_target!(z, ::HierGLMTarget), hglm_coefficients: include/ahmc_glm_hier.h
 include("AdvancedHMCMI355XGLMAux.jl")  # set_target!(z, ::AuxGLMTarget), glm_dispersion: include/ahmc_glm_aux.h
 include("AdvancedHMCMI355XGLMFactor.jl")  # set_target!(z, ::FactorGLMTarget), get_target_glm_factor: include/ahmc_glm_factor.h
+include("AdvancedHMCMI355XGLMOrdinal.jl")  # set_target!(z, ::OrdinalGLMTarget), glm_cutpoints: include/ahmc_glm_ordinal.h
 
 end # module
