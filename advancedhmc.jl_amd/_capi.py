@@ -254,6 +254,17 @@ GLM_ORDINAL_SIGNATURES = {
     "ahmc_glm_cutpoints": (_i32, [_vp, _vp, _i64, _vp]),
 }
 
+# include/ahmc_glm_categorical.h: the categorical-logit family of the GLM target, for unordered classes (likewise: the HIP engine only)
+AHMC_GLM_CATEGORICAL_VERSION = 1
+GLM_CATEGORICAL_MAX_CATEGORIES = 16
+GLM_CATEGORICAL_LOGIT = 6
+GLM_CATEGORICAL_SIGNATURES = {
+    "ahmc_glm_categorical_version": (_i32, []),
+    "ahmc_glm_categorical_set_target": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _pi32, _pi32, _pi32, C.POINTER(_f64), _i32, _pi32, _pi32, _i32]),
+    "ahmc_glm_categorical_get_target": (_i32, [_vp, _pi32, C.POINTER(_i64)]),
+    "ahmc_glm_class_probs": (_i32, [_vp, _vp, _i64, _vp]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -357,6 +368,15 @@ class CLib:
             v = self.dll.ahmc_glm_ordinal_version()
             if v != AHMC_GLM_ORDINAL_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm_ordinal version {v}, expected {AHMC_GLM_ORDINAL_VERSION}")
+        # ahmc_glm_categorical.h: likewise
+        gcat = [getattr(self.dll, name, None) for name in GLM_CATEGORICAL_SIGNATURES]
+        self.has_glm_categorical = all(fn is not None for fn in gcat)
+        if self.has_glm_categorical:
+            for fn, (res, args) in zip(gcat, GLM_CATEGORICAL_SIGNATURES.values()):
+                fn.restype, fn.argtypes = res, args
+            v = self.dll.ahmc_glm_categorical_version()
+            if v != AHMC_GLM_CATEGORICAL_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_categorical version {v}, expected {AHMC_GLM_CATEGORICAL_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

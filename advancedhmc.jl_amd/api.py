@@ -339,6 +339,10 @@ class GLMTarget:
     P(y <= k) = σ(c_{k+1} − η).  The model has no intercept — the cutpoints take its place, and a constant column in X is not
     identified.  θ ends with C − 1 rows κ (`.cut_rows`): κ_1 = c_1, κ_j = log(c_j − c_{j−1}), with the prior `cut_prior` =
     (loc_1, scale_1, loc_gap, scale_gap) on κ itself, default (0, 2.5, 0, 1); `.cutpoints(θ)` gives c of draws.
+    `family="categorical_logit"` with `n_categories=C` (include/ahmc_glm_categorical.h): y holds UNORDERED classes 0 … C − 1, class 0
+    the reference (multinomial / softmax regression).  There are K = C − 1 coefficient blocks of `.P_b` = P_x + Σ n_levels rows
+    each, `.P` = K·P_b in all and no further rows: `.class_rows(k)` are the rows of class k = 1 … K, `.n_classes` = C; prior_scale /
+    prior_prec have P entries (or broadcast), `offset` is (n_obs, K); `.class_probs(θ)` gives (C, n_obs, n) probabilities of draws.
     The engine evaluates all chains at once, X·Θ and Xᵀ·U on the MFMA units.  HIP engine only (the CPU checker takes the same
     density as `ExternalTarget(D, lambda th: glm.logdensity(...))` or a host KernelTarget)."""
     kind = capi.TARGET_GLM
@@ -348,6 +352,7 @@ class GLMTarget:
 
     n_categories = 0
     cut_prior = None
+    n_classes = 0   # C of family "categorical_logit" (n_categories stays 0: it marks the ordinal family, which adds rows to θ)
 
     def __init__(self, X, y, family="bernoulli_logit", prior_scale=None, prior_prec=None, offset=None, scale=1.0, aux_prior=None, factors=None,
                  n_categories=None, cut_prior=None):
@@ -356,11 +361,23 @@ class GLMTarget:
         if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.size != X.shape[0]:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: X {X.shape}, y {y.shape}")
         ordinal = family in _glm.ORDINAL_FAMILIES if isinstance(family, str) else isinstance(family, (int, np.integer)) and family == _glm.ORDERED_LOGIT
+        categorical = (family in _glm.CATEGORICAL_FAMILIES if isinstance(family, str)
+                       else isinstance(family, (int, np.integer)) and family == _glm.CATEGORICAL_LOGIT)
         try:
-            self.family = _glm.ORDERED_LOGIT if ordinal else _glm.family_code(family)
+            self.family = _glm.ORDERED_LOGIT if ordinal else _glm.CATEGORICAL_LOGIT if categorical else _glm.family_code(family)
         except ValueError as e:
             raise ArgumentError(capi.ERR_ARGUMENT, str(e))
-        if not ordinal and (n_categories is not None or cut_prior is not None):
+        if categorical:
+            if scale != 1.0 or aux_prior is not None or cut_prior is not None:
+                raise ArgumentError(capi.ERR_ARGUMENT, "GLMTarget: family \"categorical_logit\" has no scale, no dispersion and no cutpoints; scale, aux_prior "
+                                                       "and cut_prior do not apply")
+            if n_categories is None:
+                raise ArgumentError(capi.ERR_ARGUMENT, "GLMTarget: family \"categorical_logit\" needs n_categories")
+            try:
+                _, self.n_classes = _glm.check_classes(y, n_categories)
+            except (ValueError, TypeError) as e:
+                raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+        elif not ordinal and (n_categories is not None or cut_prior is not None):
             raise ArgumentError(capi.ERR_ARGUMENT, f"GLMTarget: n_categories and cut_prior belong to family \"ordered_logit\", not to family {self.family}")
         if ordinal:
             if scale != 1.0 or aux_prior is not None:
@@ -394,7 +411,8 @@ class GLMTarget:
         self.factors = tuple(facs)
         self.P_x = X.shape[1]
         self.factor_ranges = _glm.factor_ranges(self.P_x, self.factors)
-        self.P = self.P_x + sum(f.n_levels for f in self.factors)
+        self.P_b = self.P_x + sum(f.n_levels for f in self.factors)    # (the rows of one block; a categorical model has C − 1 of them)
+        self.P = self.P_b * (self.n_classes - 1 if self.n_classes else 1)
         self.D = self.P + (1 if self.aux else 0) + self._n_cut
         if prior_scale is not None:
             prior_prec = 1.0 / np.square(np.asarray(prior_scale, dtype=np.float64))
@@ -402,9 +420,15 @@ class GLMTarget:
             self.prior_prec = None if prior_prec is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prior_prec, dtype=np.float64), (self.P,)))
         except ValueError:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: the prior has {np.size(prior_prec)} entries, the model P = {self.P} coefficients")
-        self.offset = None if offset is None else np.asarray(offset, dtype=np.float64).ravel()
-        if self.offset is not None and self.offset.size != self.n_obs:
-            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: offset {self.offset.shape}, n_obs {self.n_obs}")
+        if self.n_classes and offset is not None:
+            try:
+                self.offset = np.asfortranarray(_glm._class_offset(offset, self.n_obs, self.n_classes - 1))
+            except (ValueError, TypeError) as e:
+                raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+        else:
+            self.offset = None if offset is None else np.asarray(offset, dtype=np.float64).ravel()
+            if self.offset is not None and self.offset.size != self.n_obs:
+                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: offset {self.offset.shape}, n_obs {self.n_obs}")
         self.scale = float(scale)
 
     @property
@@ -423,8 +447,24 @@ class GLMTarget:
         lo, hi = self.cut_rows
         return _glm.cutpoints(np.asarray(theta, dtype=np.float64)[lo:hi])
 
+    def class_rows(self, k):
+        """(start, stop) of the coefficient rows of class k = 1 … C − 1 of a categorical model: ((k − 1)·P_b, k·P_b)"""
+        if not self.n_classes:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"class_rows: family {self.family} has no class blocks")
+        if not 1 <= int(k) < self.n_classes:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"class_rows: class {k} is outside [1, {self.n_classes}) (class 0 is the reference: it has no coefficients)")
+        return (int(k) - 1) * self.P_b, int(k) * self.P_b
+
+    def class_probs(self, theta):
+        """(C, n_obs, n) class probabilities at draws θ (D, n) by the numpy mirror (family "categorical_logit")"""
+        if not self.n_classes:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"class_probs: family {self.family} has no classes")
+        return _glm.categorical_probs(_glm.categorical_pointwise(self.X, self.y, theta, self.n_classes, self.groups, self.offset, self.factors)[0])
+
     def logdensity(self, theta):
         """(ℓπ (N,), ∇ℓπ (D, N)) by the numpy mirror: the callback of an ExternalTarget for the same model"""
+        if self.n_classes:
+            return _glm.categorical_logdensity(self.X, self.y, theta, self.n_classes, self.groups, self.offset, self.prior_prec, factors=self.factors)
         if self.n_categories:
             return _glm.ordinal_logdensity(self.X, self.y, theta, self.n_categories, self.groups, self.offset, self.prior_prec, self.cut_prior,
                                            factors=self.factors)
@@ -465,7 +505,10 @@ class HierGLMTarget(GLMTarget):
                          factors=factors, n_categories=n_categories, cut_prior=cut_prior)
         groups = [g if isinstance(g, CoefGroup) else CoefGroup(*g) for g in groups]
         try:
-            _glm.check_groups(groups, self.P)
+            if self.n_classes:
+                _glm.check_class_groups(groups, self.P_b, self.n_classes - 1)
+            else:
+                _glm.check_groups(groups, self.P)
         except (ValueError, TypeError) as e:
             raise ArgumentError(capi.ERR_ARGUMENT, str(e))
         self.groups = tuple(CoefGroup(int(g.start), int(g.stop), bool(g.centered), float(g.scale)) for g in groups)
@@ -840,6 +883,9 @@ class Engine:
         if t.n_categories:
             self._need("has_glm_ordinal", "ahmc_glm_ordinal.h", f"{type(t).__name__}(family=\"ordered_logit\")")
             model = f"the model has P + G + (C - 1) = {t.P} + {G} + {t.n_categories - 1} parameters"
+        elif t.n_classes:
+            self._need("has_glm_categorical", "ahmc_glm_categorical.h", f"{type(t).__name__}(family=\"categorical_logit\")")
+            model = f"the model has (C - 1)·P_b + G = {t.n_classes - 1}·{t.P_b} + {G} parameters"
         elif t.aux:
             self._need("has_glm_aux", "ahmc_glm_aux.h", f"GLMTarget(family={t.family})")
             model = f"the model has P + G + 1 = {t.P} + {G} + 1 parameters"
@@ -853,7 +899,7 @@ class Engine:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: {model}, the context has D = {self.D}")
         X = np.asfortranarray(t.X, dtype=self.dtype)
         y = np.ascontiguousarray(t.y, dtype=self.dtype)
-        off = None if t.offset is None else np.ascontiguousarray(t.offset, dtype=self.dtype)
+        off = None if t.offset is None else np.asfortranarray(t.offset, dtype=self.dtype)   # ((n_obs, K) column-major of a categorical model)
         p = None if t.prior_prec is None else np.ascontiguousarray(t.prior_prec, dtype=self.dtype)
         data = (capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p))
         table = (G, (C.c_int32 * max(G, 1))(*[g.start for g in t.groups]), (C.c_int32 * max(G, 1))(*[g.stop for g in t.groups]),
@@ -862,6 +908,11 @@ class Engine:
             lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32) if F else None
             self._call("ahmc_glm_ordinal_set_target", int(t.n_obs), int(t.P_x), *data, *table, F, (C.c_int32 * F)(*[f.n_levels for f in t.factors]) if F else None,
                        lev.ctypes.data_as(C.POINTER(C.c_int32)) if F else None, int(t.n_categories), (C.c_double * 4)(*t.cut_prior))
+        elif t.n_classes:
+            lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32) if F else None
+            self._call("ahmc_glm_categorical_set_target", int(t.n_obs), int(t.P_x), *data, *table, F,
+                       (C.c_int32 * F)(*[f.n_levels for f in t.factors]) if F else None, lev.ctypes.data_as(C.POINTER(C.c_int32)) if F else None,
+                       int(t.n_classes))
         elif F:
             lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32)
             aux = t.aux_prior if t.aux else (0.0, 1.0)
@@ -907,6 +958,18 @@ class Engine:
         self._call("ahmc_glm_cutpoints", ptr, n, capi.as_ptr(out) if n else None)
         return out
 
+    def glm_class_probs(self, draws=None, n_cols=None):
+        """the class probabilities (C, n_obs, n) of every observation at draws θ (D, n) of the bound categorical model — an array
+        (default: the context's current θ), or a device pointer (an int) together with `n_cols`: ahmc_glm_class_probs"""
+        self._need("has_glm_categorical", "ahmc_glm_categorical.h", "glm_class_probs")
+        nc, n_obs = C.c_int32(), C.c_int64()
+        self._call("ahmc_glm_categorical_get_target", C.byref(nc), None)
+        self._call("ahmc_get_target_glm", None, C.byref(n_obs), None)
+        ptr, n = self._draws("glm_class_probs", draws, n_cols)
+        out = np.empty((nc.value, n_obs.value, n), dtype=self.dtype, order="F")
+        self._call("ahmc_glm_class_probs", ptr, n, capi.as_ptr(out) if n else None)
+        return out
+
     def hglm_coefficients(self, theta=None, n_cols=None):
         """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer
         (an int) together with `n_cols`: ahmc_hglm_coefficients"""
@@ -927,14 +990,20 @@ class Engine:
         return Px.value, [int(L[f]) for f in range(F.value)]
 
     def glm_pointwise(self):
-        """(η, ℓ(y_i, η_i)) at the context's current θ, each (n_obs, N): ahmc_glm_pointwise"""
+        """(η, ℓ(y_i, η_i)) at the context's current θ, each (n_obs, N): ahmc_glm_pointwise.  A categorical model has a predictor per
+        non-reference class: η is then (K, n_obs, N), η[k − 1] being η_k"""
         self._need("has_glm", "ahmc_glm.h", "glm_pointwise")
-        n = C.c_int64()
-        self._call("ahmc_get_target_glm", None, C.byref(n), None)
-        eta = np.empty((n.value, self.N), dtype=self.dtype, order="F")
+        n, fam = C.c_int64(), C.c_int32()
+        self._call("ahmc_get_target_glm", C.byref(fam), C.byref(n), None)
+        K = 0
+        if fam.value == capi.GLM_CATEGORICAL_LOGIT:
+            nc = C.c_int32()
+            self._call("ahmc_glm_categorical_get_target", C.byref(nc), None)
+            K = nc.value - 1
+        eta = np.empty((n.value, self.N * max(K, 1)), dtype=self.dtype, order="F")    # (K planes of (n_obs, N), plane after plane)
         ll = np.empty((n.value, self.N), dtype=self.dtype, order="F")
         self._call("ahmc_glm_pointwise", capi.as_ptr(eta), capi.as_ptr(ll))
-        return eta, ll
+        return (np.stack([eta[:, k * self.N:(k + 1) * self.N] for k in range(K)]) if K else eta), ll
 
     def _need_rank_update(self, what):
         if not getattr(self.lib, "has_rank_update", False):

@@ -10,6 +10,7 @@
 #include "ahmc_glm_aux.h"
 #include "ahmc_glm_factor.h"
 #include "ahmc_glm_ordinal.h"
+#include "ahmc_glm_categorical.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -108,7 +109,8 @@ struct ExtRun {
 // the bound model of AHMC_TARGET_GLM (ahmc_glm_host.hpp; {} = none).  One slab at buf: X, Xᵀ, y, offset, p [, a zero precision, the
 // group table; the factor table, the level indices, the permutations by level and their row pointers], then the workspaces U,
 // partial [, partial_s], gs [, W, R] [, the cutpoint table (3, C−1, N) and partial_c (C−1, row blocks, N) of an ordinal model]; part i
-// starts at off[i]; sizes 0 where the model has none
+// starts at off[i]; sizes 0 where the model has none.  A categorical model (ahmc_glm_categorical.h, C classes, K = C − 1): offset is
+// K·n_obs, U is K planes of (n_obs, N), P = K·Pb rows in p, W and R; the factor table and the row pointers describe one block
 enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PART_S, GLM_FTAB, GLM_LEV, GLM_PERM, GLM_RP,
        GLM_CUT, GLM_PART_C, GLM_PARTS };
 template <class T>
@@ -132,8 +134,9 @@ struct GlmModel {
   double aux_loc = 0, aux_scale = 1;
   int n_cat = 0;  // the categories C of an ordinal model (ahmc_glm_ordinal.h; 0: not ordinal): θ ends with the C − 1 rows κ
   double cut_prior[4] = {0, 2.5, 0, 1};  // (loc_1, scale_1, loc_gap, scale_gap)
+  int n_cls = 0;  // the classes C of a categorical model (ahmc_glm_categorical.h; 0: not categorical): P = (C − 1)·Pb, Pb = Px + Lt
 
-  bool on_w() const { return G > 0 || aux || F > 0 || n_cat > 0; }  // the products run on the effective coefficients W, not on θ
+  bool on_w() const { return G > 0 || aux || F > 0 || n_cat > 0 || n_cls > 0; }  // the products run on the effective coefficients W, not on θ
   T* at(int part) const { return buf + off[part]; }
   const HglmTab<T>* tab() const { return reinterpret_cast<const HglmTab<T>*>(at(GLM_TAB)); }
   const GlmFacTab* ftab() const { return reinterpret_cast<const GlmFacTab*>(at(GLM_FTAB)); }
@@ -2356,6 +2359,39 @@ int32_t ahmc_glm_ordinal_get_target(ahmc_ctx* ctx, int32_t* n_categories, double
 
 int32_t ahmc_glm_cutpoints(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* out) {
   FOR_CTX_MUT(ctx, { return glm_cutpoints(c, theta, n_cols, out); });
+}
+
+// ---- include/ahmc_glm_categorical.h: the categorical-logit family for unordered outcomes ---------------------------------------------
+int32_t ahmc_glm_categorical_version(void) { return AHMC_GLM_CATEGORICAL_VERSION; }
+
+int32_t ahmc_glm_categorical_set_target(ahmc_ctx* ctx, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset, const void* prior_prec,
+                                        int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered, const double* hyper_scale,
+                                        int32_t n_factors, const int32_t* n_levels, const int32_t* levels, int32_t n_categories) {
+  FOR_CTX_MUT(ctx, {
+    HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale};
+    hs.F = (int)n_factors;
+    hs.Px = n_coef;
+    hs.n_levels = n_levels;
+    hs.levels = levels;
+    int rc = glm_categorical_set(c, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), hs,
+                                 n_categories);
+    if (rc) return rc;
+    return dn_refresh_fused(c);
+  });
+}
+
+int32_t ahmc_glm_categorical_get_target(ahmc_ctx* ctx, int32_t* n_categories, int64_t* block_len) {
+  FOR_CTX(ctx, {
+    if (c->target_kind != AHMC_TARGET_GLM || !c->glm.buf || c->glm.n_cls == 0)
+      return fail(c, AHMC_ERR_ARGUMENT, "glm_categorical_get_target: no categorical model is bound (ahmc_glm_categorical_set_target)");
+    if (n_categories) *n_categories = c->glm.n_cls;
+    if (block_len) *block_len = c->glm.P / (c->glm.n_cls - 1);
+    return AHMC_OK;
+  });
+}
+
+int32_t ahmc_glm_class_probs(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* out) {
+  FOR_CTX_MUT(ctx, { return glm_class_probs(c, theta, n_cols, out); });
 }
 
 }  // extern "C"

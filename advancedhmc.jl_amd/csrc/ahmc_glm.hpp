@@ -479,6 +479,156 @@ __global__ __launch_bounds__(256) void k_glm_eta_f(const T* __restrict__ X, cons
   glm_eta_body<T, FAM, BN, true>(X, y, off, scale, W, U, partial, n_obs, Px, ncols, N, idx, eta_out, ll_out, aux, aux_ld, partial_s, P, ft, lev);
 }
 
+// ---- include/ahmc_glm_categorical.h: the categorical-logit (softmax) family for unordered outcomes -------------------------------------
+// y ∈ {0 … C − 1}, class 0 the reference (η_0 ≡ 0); K = C − 1 coefficient blocks of Pb rows, block k of a chain at W + col·ldw + k·Pb
+// (glm.py: categorical_link).  The link of one observation of one chain, on its K predictors e[k·ps] (k = 0 … K − 1 stands for class
+// k + 1) and m = max(0, η_1, …, η_K), made by the caller as  m = 0; m = η_k > m ? η_k : m  for ascending k:
+//     e_0 = exp(−m), s = e_0, then s += exp(η_k − m) ascending;  inv = 1/s, lse = m + log(s);  ℓ = η_y − lse (η_0 = 0);
+//     p_k = exp(η_k − m)·inv (the same exp of the same argument: the same bits),  u_k = 1 − p_k if y = k, else −p_k.
+// u_k replaces η_k in place; ℓ is returned; pr (nullptr: none) receives the C probabilities p_0 … p_K.  One term of s is exactly 1, so
+// s ∈ [1, C] and everything is finite for finite η.  There is no multiply-add in it.
+constexpr int GLM_CAT_MAX_CAT = 16;  // AHMC_GLM_CATEGORICAL_MAX_CATEGORIES
+
+template <class T>
+__device__ __forceinline__ T glm_link_cat(int yi, int K, T* e, int64_t ps, T m, T* pr) {
+  const T e0 = exp(-m);
+  T s = e0, ey = T(0);
+#pragma unroll 1
+  for (int k = 0; k < K; ++k) {
+    const T eta = e[(int64_t)k * ps];
+    if (k + 1 == yi) ey = eta;
+    const T ek = exp(eta - m);
+    s += ek;
+  }
+  const T inv = T(1) / s;
+  const T lse = m + log(s);
+  if (pr) pr[0] = e0 * inv;
+#pragma unroll 1
+  for (int k = 0; k < K; ++k) {
+    const T ek = exp(e[(int64_t)k * ps] - m);
+    const T p = ek * inv;
+    const T omp = T(1) - p;
+    e[(int64_t)k * ps] = k + 1 == yi ? omp : -p;
+    if (pr) pr[k + 1] = p;
+  }
+  return ey - lse;
+}
+
+// η_k = X·W_k (+ the factors' levels of block k) + off[k·n_obs + row] for k = 0 … K − 1 and the listed chains, one class at a time
+// through ONE accumulator set: glm_tile_product with the B pointer moved to block k, then the tile leaves through LDS so that a wave
+// writes 64 consecutive observations of one chain to plane k of U (K planes of (n_obs, N)).  The thread that writes (row m0 + lane,
+// tile column w + 4·c) of plane k is the same for every k; it keeps the running m of its NS = BN/4 elements in an LDS array of its
+// own, each word touched by that thread alone (in registers they would cost the 64×64 shape its second wave per SIMD), and, after
+// the last class, runs glm_link_cat on the values it wrote itself (program order: no barrier between the two passes), which turns
+// the planes into u_k.  ℓ goes to smem[row][column] and is summed over the tile's 64 rows in ascending row order by one thread per
+// column, exactly as in k_glm_eta (rows past n_obs contribute +0).  eta_out (K planes of (n_obs, N)) / ll_out (n_obs, N) on request
+// (ahmc_glm_pointwise); prob_out (C, n_obs, ·) column-major on request (ahmc_glm_class_probs: no chain list).  No atomics, no scratch.
+template <class T, int BN, bool FAC>
+__global__ __launch_bounds__(256) void k_glm_eta_cat(const T* __restrict__ X, const T* __restrict__ y, const T* __restrict__ off, const T* __restrict__ W,
+                                                     T* U, T* __restrict__ partial, int n_obs, int Px, int Pb, int K, int64_t ldw, int64_t ncols, int64_t N,
+                                                     const int* __restrict__ idx, T* __restrict__ eta_out, T* __restrict__ ll_out, T* __restrict__ prob_out,
+                                                     const GlmFacTab* __restrict__ ft, const int* __restrict__ lev) {
+  using S = GlmShape<BN>;
+  using Mf = Mfma<T>;
+  constexpr int NS = BN / 4;  // the tile columns a thread carries through LDS: w, w + 4, …
+  __shared__ T smem[S::SMEM];
+  __shared__ T s_m[BN * S::LDE];  // max(0, η_1 … η_k), [column][row]
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nrb = (n_obs + GB_M - 1) / GB_M;
+  int rblk;
+  int64_t cb;
+  glm_block<BN>(nrb, rblk, cb);
+  const int m0 = rblk * GB_M;
+  const int64_t n0 = cb * BN;
+  if (n0 >= ncols) return;
+  const int64_t plane = (int64_t)n_obs * N;
+  const int bn = tid / (GB_K / S::BE);
+  const int64_t bcol = n0 + bn < ncols ? (idx ? (int64_t)idx[n0 + bn] : n0 + bn) : -1;
+  const int wm = (w % S::WR) * 16 * S::MI, wn = (w / S::WR) * 16 * S::MI;
+  const int row_t = m0 + lane;
+  const bool rok = row_t < n_obs;
+  int colm[S::MI];  // the chains of this thread's accumulator columns (−1: past the list)
+#pragma unroll
+  for (int tj = 0; tj < S::MI; ++tj) {
+    const int64_t j = n0 + wn + tj * 16 + (lane & 15);
+    colm[tj] = j < ncols ? (idx ? idx[j] : (int)j) : -1;
+  }
+  // the chain of tile column cl for this thread's row (−1: nothing to write)
+  auto chain_of = [&](int cl) -> int {
+    const int64_t j = n0 + cl;
+    return j < ncols && rok ? (idx ? idx[j] : (int)j) : -1;
+  };
+#pragma unroll
+  for (int c = 0; c < NS; ++c) s_m[(w + 4 * c) * S::LDE + lane] = T(0);
+#pragma unroll 1
+  for (int k = 0; k < K; ++k) {
+    typename Mf::acc_t acc[S::MI][S::MI];
+#pragma unroll
+    for (int i = 0; i < S::MI; ++i)
+#pragma unroll
+      for (int j = 0; j < S::MI; ++j) acc[i][j] = typename Mf::acc_t{0, 0, 0, 0};
+    glm_tile_product<T, BN>(X, (int64_t)n_obs, n_obs, m0, bcol >= 0 ? W + bcol * ldw + (int64_t)k * Pb : nullptr, 0, Px, smem, acc);
+    // η_k → smem[column][row]
+#pragma unroll
+    for (int ti = 0; ti < S::MI; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < S::MI; ++tj) {
+        const int cl = wn + tj * 16 + (lane & 15);
+        const int col = colm[tj];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int rl = wm + ti * 16 + Mf::row(lane, v);
+          const int row = m0 + rl;
+          T eta = T(0);
+          if (row < n_obs && col >= 0) {
+            eta = acc[ti][tj][v];
+            if constexpr (FAC) {
+              const T* wc = W + (int64_t)col * ldw + (int64_t)k * Pb;
+              const int F = ft->F;
+              for (int f = 0; f < F; ++f) eta += wc[ft->off[f] + lev[row + (int64_t)f * n_obs]];
+            }
+            if (off) eta += off[(int64_t)k * n_obs + row];
+          }
+          smem[cl * S::LDE + rl] = eta;
+        }
+      }
+    __syncthreads();
+#pragma unroll 4
+    for (int c = 0; c < NS; ++c) {  // a wave per column: 64 consecutive observations
+      const int cl = w + 4 * c, col = chain_of(cl);
+      if (col >= 0) {
+        const T eta = smem[cl * S::LDE + lane];
+        const int64_t at = (int64_t)k * plane + row_t + (int64_t)col * n_obs;
+        U[at] = eta;
+        if (eta_out) eta_out[at] = eta;
+        const T m = s_m[cl * S::LDE + lane];
+        s_m[cl * S::LDE + lane] = eta > m ? eta : m;
+      }
+    }
+    __syncthreads();  // (the next class stages its tiles in smem)
+  }
+  // the link, each thread on the elements it wrote; ℓ → smem[row][column], then the column sums
+  const int yi = rok ? (int)y[row_t] : 0;
+#pragma unroll 1
+  for (int c = 0; c < NS; ++c) {
+    const int cl = w + 4 * c, col = chain_of(cl);
+    T l = T(0);
+    if (col >= 0) {
+      const int64_t at = row_t + (int64_t)col * n_obs;
+      l = glm_link_cat<T>(yi, K, U + at, plane, s_m[cl * S::LDE + lane], prob_out ? prob_out + (int64_t)(K + 1) * at : (T*)nullptr);
+      if (ll_out) ll_out[at] = l;
+    }
+    smem[lane * (BN + 1) + cl] = l;
+  }
+  __syncthreads();
+  if (tid < BN && n0 + tid < ncols) {
+    const int64_t col = idx ? (int64_t)idx[n0 + tid] : n0 + tid;
+    T s = T(0);
+    for (int r = 0; r < GB_M; ++r) s += smem[r * (BN + 1) + tid];
+    partial[(int64_t)rblk * N + col] = s;
+  }
+}
+
 // Xᵀ·U for the listed chains.  Tile rows are coefficients, tile columns chains, K = the workgroup's slice of the observations; the
 // A operand is the transposed copy Xt (D, n_obs) made when the target was set.  One slice (n_obs <= GLM_K_SLICE): the epilogue
 // writes g = −acc + p∘θ to the chain's column of g.  More: the slice's sum goes to gs[slice][chain][d] and k_glm_gsum finishes.

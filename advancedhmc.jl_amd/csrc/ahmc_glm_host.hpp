@@ -25,6 +25,8 @@ struct HglmSpec {
   // ahmc_glm_ordinal_set_target: C categories, θ ends with the C − 1 rows κ; cut_prior = (loc_1, scale_1, loc_gap, scale_gap)
   int n_cat = 0;
   const double* cut_prior = nullptr;
+  // ahmc_glm_categorical_set_target: C classes, K = C − 1 coefficient blocks of Px + Σ n_levels rows each (P = K blocks)
+  int n_cls = 0;
 };
 
 inline bool glm_aux_family(int family) { return family == AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA || family == AHMC_GLM_NEGBINOMIAL_LOG; }
@@ -32,6 +34,15 @@ inline bool glm_aux_family(int family) { return family == AHMC_GLM_GAUSSIAN_IDEN
 // what the entry points of the older headers answer to AHMC_GLM_ORDERED_LOGIT
 inline std::string glm_ordinal_elsewhere(int family, bool aux) {
   const std::string where = "it samples its cutpoints and is bound through ahmc_glm_ordinal_set_target (include/ahmc_glm_ordinal.h)";
+  if (aux)
+    return "glm_aux_set_target: family " + std::to_string(family) +
+           " has no sampled dispersion (AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA, AHMC_GLM_NEGBINOMIAL_LOG): " + where;
+  return "set_target_glm: unknown family " + std::to_string(family) + " at this entry point: " + where;
+}
+
+// … and to AHMC_GLM_CATEGORICAL_LOGIT
+inline std::string glm_categorical_elsewhere(int family, bool aux) {
+  const std::string where = "it has a coefficient block per class and is bound through ahmc_glm_categorical_set_target (include/ahmc_glm_categorical.h)";
   if (aux)
     return "glm_aux_set_target: family " + std::to_string(family) +
            " has no sampled dispersion (AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA, AHMC_GLM_NEGBINOMIAL_LOG): " + where;
@@ -124,6 +135,34 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
   return AHMC_OK;
 }
 
+// a categorical model (include/ahmc_glm_categorical.h): the K predictors of ncols listed chains from W (P = K·Pb rows a column) into
+// the K planes of U, turned into u_k in place, and Σℓ per row block into partial; on request η (K planes), ℓ and the class
+// probabilities (C, n_obs, ncols; then without a chain list)
+template <class T>
+int glm_launch_eta_cat(Ctx<T>* c, const T* W, const int* list, int64_t ncols, bool small, T* eta_out, T* ll_out, T* prob_out) {
+  const GlmModel<T>& m = c->glm;
+  if (m.family != AHMC_GLM_CATEGORICAL_LOGIT || m.n_cls < 2) return fail(c, AHMC_ERR_STATE, "glm: the family and the class count disagree in the context");
+  if (prob_out && list) return fail(c, AHMC_ERR_STATE, "glm: class probabilities are made without a chain list");
+  const int n_obs = (int)m.n_obs, K = m.n_cls - 1, Pb = (int)(m.P / K);
+  const int64_t nrb = (n_obs + GB_M - 1) / GB_M;
+  const T* off = m.has_offset ? m.at(GLM_OFF) : nullptr;
+  const dim3 grid = small ? dim3((unsigned)nrb, (unsigned)((ncols + 15) / 16)) : dim3((unsigned)(nrb * (((ncols + GB_N - 1) / GB_N + 7) / 8 * 8)));
+#define AHMC_GLM_ETA_CAT(BN, FAC)                                                                                                                              \
+  hipLaunchKernelGGL((k_glm_eta_cat<T, BN, FAC>), grid, dim3(256), 0, c->stream, (const T*)m.at(GLM_X), (const T*)m.at(GLM_Y), off, W, m.at(GLM_U), m.at(GLM_PART), \
+                     n_obs, (int)m.Px, Pb, K, (int64_t)m.P, ncols, c->N, list, eta_out, ll_out, prob_out, m.F > 0 ? m.ftab() : (const GlmFacTab*)nullptr,           \
+                     m.F > 0 ? m.ints(GLM_LEV) : (const int*)nullptr)
+  if (m.F > 0) {
+    if (small) AHMC_GLM_ETA_CAT(16, true);
+    else AHMC_GLM_ETA_CAT(64, true);
+  } else {
+    if (small) AHMC_GLM_ETA_CAT(16, false);
+    else AHMC_GLM_ETA_CAT(64, false);
+  }
+#undef AHMC_GLM_ETA_CAT
+  HIPCHK(hipGetLastError());
+  return AHMC_OK;
+}
+
 // an ordinal model's cutpoint table (c, lg, r) of the listed chains from the κ rows of the context's θ, before k_glm_eta
 template <class T>
 void glm_launch_cut(Ctx<T>* c, const int* list, int64_t n) {
@@ -161,13 +200,34 @@ int glm_target(Ctx<T>* c, const int* list, int64_t n, bool sanitize_lp = true) {
   T* g = hier ? m.at(GLM_R) : c->g;
   if (hier) hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const T*)c->th, m.tab(), m.at(GLM_W), (T*)nullptr, D, G, c->D, n, list);
   if (m.n_cat > 0) glm_launch_cut(c, list, n);
-  int rc = glm_launch_eta(c, th, D, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr);
+  int rc = m.n_cls > 0 ? glm_launch_eta_cat(c, th, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr, (T*)nullptr)
+                       : glm_launch_eta(c, th, D, list, n, glm_small(c, nrb, n), (T*)nullptr, (T*)nullptr);
   if (rc) return rc;
   const T* Xt = m.at(GLM_XT);
   const T* U = m.at(GLM_U);
   T* gs = m.at(GLM_GS);
   const dim3 grid16((unsigned)nrbD, (unsigned)((n + 15) / 16)), grid64((unsigned)(nrbD * (((n + GB_N - 1) / GB_N + 7) / 8 * 8)));
-  if (m.F > 0) {
+  if (m.n_cls > 0) {
+    // per class k: rows [k·Pb, (k + 1)·Pb) of R = −Xᵀu_k from plane k of U, by the kernels of a model with factors (column stride P);
+    // the slice workspace is reused stream-ordered
+    const int K = m.n_cls - 1, Pb = D / K;
+    const bool small = glm_small(c, nrbD, n);
+    for (int k = 0; k < K; ++k) {
+      const T* Uk = U + (int64_t)k * n_obs * c->N;
+      const T* Wk = th + (int64_t)k * Pb;
+      T* Rk = g + (int64_t)k * Pb;
+      if (small)
+        hipLaunchKernelGGL((k_glm_grad_ld<T, 16>), grid16, dim3(256), 0, c->stream, Xt, Uk, prec, Wk, Rk, gs, n_obs, Px, (int64_t)D, n, c->N, list, ns);
+      else
+        hipLaunchKernelGGL((k_glm_grad_ld<T, 64>), grid64, dim3(256), 0, c->stream, Xt, Uk, prec, Wk, Rk, gs, n_obs, Px, (int64_t)D, n, c->N, list, ns);
+      if (ns > 1)
+        hipLaunchKernelGGL((k_glm_gsum_ld<T>), dim3((unsigned)((n * Px + 255) / 256)), dim3(256), 0, c->stream, (const T*)gs, prec, Wk, Rk, Px, (int64_t)D, n, c->N,
+                           list, ns);
+      if (m.F > 0)
+        hipLaunchKernelGGL((k_glm_fgrad<T>), dim3((unsigned)((n * m.Lt + 255) / 256)), dim3(256), 0, c->stream, Uk, m.ints(GLM_PERM), m.ints(GLM_RP), Rk, n_obs, Px,
+                           (int)m.Lt, (int64_t)D, n, list);
+    }
+  } else if (m.F > 0) {
     if (glm_small(c, nrbD, n))
       hipLaunchKernelGGL((k_glm_grad_ld<T, 16>), grid16, dim3(256), 0, c->stream, Xt, U, prec, th, g, gs, n_obs, Px, (int64_t)D, n, c->N, list, ns);
     else
@@ -208,18 +268,22 @@ template <class T>
 int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, double scale, const HglmSpec* hs = nullptr) {
   const int G = hs ? hs->G : 0;
   const int n_cat = hs ? hs->n_cat : 0;  // (> 0: checked by glm_ordinal_set)
-  const bool aux = hs && hs->aux, on_w = G > 0 || aux || (hs && hs->F > 0) || n_cat > 0;
+  const int n_cls = hs ? hs->n_cls : 0;  // (> 0: checked by glm_categorical_set)
+  const int K = n_cls > 0 ? n_cls - 1 : 1;  // predictors per observation: the planes of U, the columns of offset
+  const bool aux = hs && hs->aux, on_w = G > 0 || aux || (hs && hs->F > 0) || n_cat > 0 || n_cls > 0;
   const int64_t D = hs ? hs->P : c->D, N = c->N;  // (the coefficient rows: the record's P)
   const int F = hs ? hs->F : 0;
-  const int64_t Px = F > 0 ? hs->Px : D, Lt = D - Px;  // (the columns of X; the factors' levels together)
+  // (the columns of X; the factors' levels together — of one block, where the model has K blocks)
+  const int64_t Px = F > 0 || n_cls > 0 ? hs->Px : D, Lt = (n_cls > 0 ? D / K : D) - Px;
   if (family == AHMC_GLM_ORDERED_LOGIT && n_cat == 0) return fail(c, AHMC_ERR_ARGUMENT, glm_ordinal_elsewhere(family, aux));
+  if (family == AHMC_GLM_CATEGORICAL_LOGIT && n_cls == 0) return fail(c, AHMC_ERR_ARGUMENT, glm_categorical_elsewhere(family, aux));
   if (glm_aux_family(family) && !aux)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family) +
                                           " at this entry point: it samples its dispersion and is bound through ahmc_glm_aux_set_target (include/ahmc_glm_aux.h)");
   if (aux && !glm_aux_family(family))
     return fail(c, AHMC_ERR_ARGUMENT, "glm_aux_set_target: family " + std::to_string(family) +
                                           " has no sampled dispersion (AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA, AHMC_GLM_NEGBINOMIAL_LOG)");
-  if (!aux && n_cat == 0 && family != AHMC_GLM_BERNOULLI_LOGIT && family != AHMC_GLM_POISSON_LOG && family != AHMC_GLM_GAUSSIAN_IDENTITY)
+  if (!aux && n_cat == 0 && n_cls == 0 && family != AHMC_GLM_BERNOULLI_LOGIT && family != AHMC_GLM_POISSON_LOG && family != AHMC_GLM_GAUSSIAN_IDENTITY)
     return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: unknown family " + std::to_string(family));
   if (n_obs < 1) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: n_obs must be >= 1; got " + std::to_string(n_obs));
   if (n_obs > AHMC_GLM_MAX_OBS)
@@ -227,10 +291,11 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
                                              std::to_string((long long)AHMC_GLM_MAX_OBS));
   if (!X || !y) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: X or y is NULL");
   if (!(std::isfinite(scale) && scale > 0)) return fail(c, AHMC_ERR_ARGUMENT, "set_target_glm: scale must be finite and > 0; got " + std::to_string(scale));
-  // the slab: X, Xᵀ, y, offset, p [, a zero precision, the group table], then the workspaces U, partial [, partial_s], gs [, W, R]
+  // the slab: X, Xᵀ, y, offset, p [, a zero precision, the group table], then the workspaces U, partial [, partial_s], gs [, W, R].
+  // A categorical model: offset K·n_obs, U K·n_obs·N (a plane per class), p / W / R over its P = K·Pb rows
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M, ns = (n_obs + GLM_K_SLICE - 1) / GLM_K_SLICE;
   const int64_t tab_elems = (int64_t)((sizeof(HglmTab<T>) + sizeof(T) - 1) / sizeof(T));
-  int64_t sizes[GLM_PARTS] = {n_obs * Px, n_obs * Px, n_obs, n_obs, D, n_obs * N, nrb * N, ns > 1 ? ns * Px * N : 0, 0, 0, 0, 0, aux ? nrb * N : 0, 0, 0, 0, 0,
+  int64_t sizes[GLM_PARTS] = {n_obs * Px, n_obs * Px, n_obs, n_obs * K, D, n_obs * N * K, nrb * N, ns > 1 ? ns * Px * N : 0, 0, 0, 0, 0, aux ? nrb * N : 0, 0, 0, 0, 0,
                               n_cat > 0 ? 3 * (int64_t)(n_cat - 1) * N : 0, n_cat > 0 ? (int64_t)(n_cat - 1) * nrb * N : 0};
   if (on_w) {
     sizes[GLM_W] = sizes[GLM_R] = D * N;
@@ -256,22 +321,25 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   std::vector<T> h((size_t)n_data, T(0));
   HIPCHK(hipMemcpy(h.data() + off[GLM_X], X, sizeof(T) * n_obs * Px, hipMemcpyDefault));
   HIPCHK(hipMemcpy(h.data() + off[GLM_Y], y, sizeof(T) * n_obs, hipMemcpyDefault));
-  if (offset) HIPCHK(hipMemcpy(h.data() + off[GLM_OFF], offset, sizeof(T) * n_obs, hipMemcpyDefault));
+  if (offset) HIPCHK(hipMemcpy(h.data() + off[GLM_OFF], offset, sizeof(T) * n_obs * K, hipMemcpyDefault));
   if (prec) HIPCHK(hipMemcpy(h.data() + off[GLM_PREC], prec, sizeof(T) * D, hipMemcpyDefault));
   const T* hX = h.data() + off[GLM_X];
   for (int64_t i = 0; i < n_obs * Px; ++i)
     if (!std::isfinite((double)hX[i])) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: X holds a non-finite value");
+  for (int64_t i = n_obs; i < n_obs * K; ++i)  // (the offset's columns of the classes after the first)
+    if (!std::isfinite((double)h[off[GLM_OFF] + i])) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: offset holds a non-finite value");
+  const int n_int = n_cat > 0 ? n_cat : n_cls;  // y holds a category or a class
   for (int64_t i = 0; i < n_obs; ++i) {
     const double yi = (double)h[off[GLM_Y] + i];
     if (!std::isfinite((double)h[off[GLM_OFF] + i])) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: offset holds a non-finite value");
     const bool counts = family == AHMC_GLM_POISSON_LOG || family == AHMC_GLM_NEGBINOMIAL_LOG;
-    const bool ok = n_cat > 0                            ? (yi >= 0 && yi < n_cat && yi == std::floor(yi))
+    const bool ok = n_int > 0                            ? (yi >= 0 && yi < n_int && yi == std::floor(yi))
                     : family == AHMC_GLM_BERNOULLI_LOGIT ? (yi >= 0 && yi <= 1)
                     : counts                             ? (std::isfinite(yi) && yi >= 0)
                                                          : std::isfinite(yi);
-    if (!ok && n_cat > 0)
+    if (!ok && n_int > 0)
       return fail(c, AHMC_ERR_ARGUMENT, "DomainError: y[" + std::to_string(i + 1) + "] = " + std::to_string(yi) + " is not a category: an integer in [0, " +
-                                            std::to_string(n_cat) + ")");
+                                            std::to_string(n_int) + ")");
     if (!ok)
       return fail(c, AHMC_ERR_ARGUMENT, "DomainError: y[" + std::to_string(i + 1) + "] = " + std::to_string(yi) + " is outside the family's domain (" +
                                             (family == AHMC_GLM_BERNOULLI_LOGIT ? "0 <= y <= 1" : counts ? "y >= 0, finite" : "finite") + ")");
@@ -332,6 +400,7 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
                                          std::to_string((long long)(sizeof(T) * (size_t)n_data)) + ") and its workspaces U (n_obs × N), partial and the slice sums" +
                                          (on_w ? ", W and R (n_coef × N)" : "") + (aux ? ", partial_s" : "") +
                                          (n_cat > 0 ? ", the cutpoint table (3 × (C − 1) × N) and partial_c" : "") +
+                                         (n_cls > 0 ? "; U holds a plane per non-reference class" : "") +
                                          (F > 0 ? "; the model holds the level indices, permutations and row pointers of " + std::to_string(F) + " factors" : ""));
   }
   if (hipMemcpy(m.buf, h.data(), sizeof(T) * (size_t)n_data, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
@@ -355,6 +424,7 @@ int glm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const 
   m.n_cat = n_cat;
   if (n_cat > 0)
     for (int i = 0; i < 4; ++i) m.cut_prior[i] = hs->cut_prior[i];
+  m.n_cls = n_cls;
   c->glm = m;
   c->target_kind = AHMC_TARGET_GLM;
   c->have_point = false;
@@ -368,10 +438,11 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
   if (c->target_kind != AHMC_TARGET_GLM || !m.buf) return fail(c, AHMC_ERR_ARGUMENT, "glm_pointwise: no GLM is bound (ahmc_set_target_glm)");
   if (!eta_out && !ll_out) return AHMC_OK;
   const size_t n = (size_t)m.n_obs * (size_t)c->N;
+  const size_t n_eta = n * (size_t)(m.n_cls > 0 ? m.n_cls - 1 : 1);  // (a categorical model: a plane of η per non-reference class)
   T* tmp = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * 2 * n) != hipSuccess) {
+  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * (n_eta + n)) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(c, AHMC_ERR_RUNTIME, "glm_pointwise: cannot allocate " + std::to_string((long long)(sizeof(T) * 2 * n)) + " bytes");
+    return fail(c, AHMC_ERR_RUNTIME, "glm_pointwise: cannot allocate " + std::to_string((long long)(sizeof(T) * (n_eta + n))) + " bytes");
   }
   const int64_t nrb = (m.n_obs + GB_M - 1) / GB_M;
   const T* th = c->th;
@@ -381,10 +452,13 @@ int glm_pointwise(Ctx<T>* c, void* eta_out, void* ll_out) {
     th = m.at(GLM_W);
   }
   if (m.n_cat > 0) glm_launch_cut(c, (const int*)nullptr, c->N);
-  int rc = glm_launch_eta(c, th, (int)m.P, (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_out ? tmp : (T*)nullptr, ll_out ? tmp + n : (T*)nullptr);
+  T* const eta_tmp = eta_out ? tmp : (T*)nullptr;
+  T* const ll_tmp = ll_out ? tmp + n_eta : (T*)nullptr;
+  int rc = m.n_cls > 0 ? glm_launch_eta_cat(c, th, (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_tmp, ll_tmp, (T*)nullptr)
+                       : glm_launch_eta(c, th, (int)m.P, (const int*)nullptr, c->N, glm_small(c, nrb, c->N), eta_tmp, ll_tmp);
   hipError_t e = hipSuccess;
-  if (!rc && eta_out) e = hipMemcpyAsync(eta_out, tmp, sizeof(T) * n, hipMemcpyDefault, c->stream);
-  if (!rc && e == hipSuccess && ll_out) e = hipMemcpyAsync(ll_out, tmp + n, sizeof(T) * n, hipMemcpyDefault, c->stream);
+  if (!rc && eta_out) e = hipMemcpyAsync(eta_out, tmp, sizeof(T) * n_eta, hipMemcpyDefault, c->stream);
+  if (!rc && e == hipSuccess && ll_out) e = hipMemcpyAsync(ll_out, tmp + n_eta, sizeof(T) * n, hipMemcpyDefault, c->stream);
   const hipError_t es = hipStreamSynchronize(c->stream);
   (void)hipFree(tmp);
   if (rc) return rc;
@@ -399,6 +473,7 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const
   const int n_groups = hs.G;
   const bool aux = hs.aux;
   if (family == AHMC_GLM_ORDERED_LOGIT && hs.n_cat == 0) return fail(c, AHMC_ERR_ARGUMENT, glm_ordinal_elsewhere(family, aux));  // (whatever D is)
+  if (family == AHMC_GLM_CATEGORICAL_LOGIT && hs.n_cls == 0) return fail(c, AHMC_ERR_ARGUMENT, glm_categorical_elsewhere(family, aux));
   if (n_groups < 0) return fail(c, AHMC_ERR_ARGUMENT, "hglm_set_target: n_groups must be >= 0; got " + std::to_string(n_groups));
   if (aux && n_groups > AHMC_GLM_AUX_MAX_GROUPS)
     return fail(c, AHMC_ERR_UNSUPPORTED, "glm_aux_set_target: n_groups = " + std::to_string(n_groups) + " is beyond the engine's limit AHMC_GLM_AUX_MAX_GROUPS = " +
@@ -411,7 +486,10 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const
     return fail(c, AHMC_ERR_ARGUMENT, "DimensionMismatch: the context has D = " + std::to_string((long long)c->D) + ", the model n_coef + n_groups = " +
                                           std::to_string((long long)n_coef) + " + " + std::to_string(n_groups) + (aux ? " (+ 1: the dispersion's row)" : "") +
                                           (n_cut ? " + " + std::to_string(n_cut) + " (n_categories - 1: the cutpoints' rows)" : "") +
-                                          (hs.F > 0 ? " (n_coef: " + std::to_string((long long)hs.Px) + " columns of X and the factors' levels)" : ""));
+                                          (hs.n_cls > 0 ? " (n_coef: " + std::to_string(hs.n_cls - 1) + " blocks, one per non-reference class, of " +
+                                                              std::to_string((long long)(n_coef / (hs.n_cls - 1))) + " rows)"
+                                           : hs.F > 0   ? " (n_coef: " + std::to_string((long long)hs.Px) + " columns of X and the factors' levels)"
+                                                        : ""));
   if (aux && !std::isfinite(hs.aux_loc)) return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_loc = " + std::to_string(hs.aux_loc) + " must be finite");
   if (aux && !(std::isfinite(hs.aux_scale) && hs.aux_scale > 0))
     return fail(c, AHMC_ERR_ARGUMENT, "DomainError: aux_scale = " + std::to_string(hs.aux_scale) + " must be finite and > 0");
@@ -423,6 +501,12 @@ int hglm_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y, const
     if (lo < 0 || hi > n_coef) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is out of bounds [0, " + std::to_string((long long)n_coef) + ")");
     if (hi <= lo) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " is empty");
     if (lo < prev) return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " overlaps the group before it or is out of order");
+    if (hs.n_cls > 0) {  // a categorical model: inside one class's block, or whole blocks
+      const int64_t Pb = n_coef / (hs.n_cls - 1);
+      if (lo / Pb != (hi - 1) / Pb && (lo % Pb != 0 || hi % Pb != 0))
+        return fail(c, AHMC_ERR_ARGUMENT, "ArgumentError: " + grp + " straddles the classes' blocks of " + std::to_string((long long)Pb) +
+                                              " rows: a group lies inside one block or is a union of whole blocks");
+    }
     if (!(std::isfinite(hs.A[k]) && hs.A[k] > 0))
       return fail(c, AHMC_ERR_ARGUMENT, "DomainError: hyper_scale[" + std::to_string(k + 1) + "] = " + std::to_string(hs.A[k]) + " must be finite and > 0");
     prev = hi;
@@ -460,6 +544,8 @@ int glm_factor_set(Ctx<T>* c, int family, int64_t n_obs, const T* X, const T* y,
         return fail(c, AHMC_ERR_ARGUMENT, "DomainError: levels[" + std::to_string((long long)i + 1) + ", " + std::to_string(f + 1) + "] = " + std::to_string(l) +
                                               " is outside [0, " + std::to_string(hs.n_levels[f]) + ") (zero-based level indices)");
     }
+  if (hs.n_cls > 0) P *= hs.n_cls - 1;  // (a categorical model: a block of these rows per non-reference class)
+  if (P > INT32_MAX / 2) return fail(c, AHMC_ERR_UNSUPPORTED, "glm_categorical_set_target: " + std::to_string((long long)P) + " coefficient rows are beyond 2^30");
   hs.P = P;
   return hglm_set(c, family, n_obs, X, y, offset, prec, scale, hs);
 }
@@ -481,6 +567,20 @@ int glm_ordinal_set(Ctx<T>* c, int64_t n_obs, const T* X, const T* y, const T* o
   hs.n_cat = n_categories;
   hs.cut_prior = cut_prior;
   return glm_factor_set(c, AHMC_GLM_ORDERED_LOGIT, n_obs, X, y, offset, prec, 1.0, hs);
+}
+
+// ---- include/ahmc_glm_categorical.h ----
+// hs as glm_ordinal_set takes it; the family is AHMC_GLM_CATEGORICAL_LOGIT, there is no scale, no dispersion and no row of its own
+template <class T>
+int glm_categorical_set(Ctx<T>* c, int64_t n_obs, const T* X, const T* y, const T* offset, const T* prec, HglmSpec hs, int32_t n_categories) {
+  if (n_categories < 2)
+    return fail(c, AHMC_ERR_ARGUMENT, "DomainError: n_categories = " + std::to_string(n_categories) + "; a categorical outcome has at least 2 classes");
+  if (n_categories > AHMC_GLM_CATEGORICAL_MAX_CATEGORIES)
+    return fail(c, AHMC_ERR_UNSUPPORTED, "glm_categorical_set_target: n_categories = " + std::to_string(n_categories) +
+                                             " is beyond the engine's limit AHMC_GLM_CATEGORICAL_MAX_CATEGORIES = " +
+                                             std::to_string(AHMC_GLM_CATEGORICAL_MAX_CATEGORIES));
+  hs.n_cls = n_categories;
+  return glm_factor_set(c, AHMC_GLM_CATEGORICAL_LOGIT, n_obs, X, y, offset, prec, 1.0, hs);
 }
 
 // ahmc_hglm_coefficients and ahmc_glm_dispersion: a temporary of `elems` elements that begins with the n_theta elements of the
@@ -561,4 +661,41 @@ int glm_cutpoints(Ctx<T>* c, const void* theta, int64_t n_cols, void* out) {
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : hipMemcpyAsync(out, cut, sizeof(T) * (size_t)(Cm1 * n_cols), hipMemcpyDefault, c->stream);
   });
+}
+
+// ---- include/ahmc_glm_categorical.h ----
+// the class probabilities (C, n_obs, n_cols) at any (D, n_cols) array of draws, host or device pointers: chunks of at most N columns
+// through k_hglm_coef and k_glm_eta_cat on the model's own workspaces W, U and partial (stream-ordered with every evaluation)
+template <class T>
+int glm_class_probs(Ctx<T>* c, const void* theta, int64_t n_cols, void* out) {
+  const GlmModel<T>& m = c->glm;
+  if (c->target_kind != AHMC_TARGET_GLM || !m.buf || m.n_cls == 0)
+    return fail(c, AHMC_ERR_ARGUMENT, "glm_class_probs: no categorical model is bound (ahmc_glm_categorical_set_target)");
+  if (n_cols < 0 || (n_cols > 0 && (!theta || !out))) return fail(c, AHMC_ERR_ARGUMENT, "glm_class_probs: theta or out is NULL, or n_cols < 0");
+  if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, "glm_class_probs: n_cols beyond 2^31 - 1");
+  if (n_cols == 0) return AHMC_OK;
+  const int64_t D = c->D, chunk = n_cols < c->N ? n_cols : c->N, per_col = (int64_t)m.n_cls * m.n_obs, nrb = (m.n_obs + GB_M - 1) / GB_M;
+  const size_t elems = (size_t)((D + per_col) * chunk);
+  T* tmp = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * elems) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, AHMC_ERR_RUNTIME, "glm_class_probs: cannot allocate " + std::to_string((long long)(sizeof(T) * elems)) + " bytes");
+  }
+  T* const pr = tmp + D * chunk;
+  hipError_t e = hipSuccess;
+  int rc = AHMC_OK;
+  for (int64_t j0 = 0; j0 < n_cols && !rc && e == hipSuccess; j0 += chunk) {
+    const int64_t nc = n_cols - j0 < chunk ? n_cols - j0 : chunk;
+    e = hipMemcpyAsync(tmp, static_cast<const T*>(theta) + j0 * D, sizeof(T) * (size_t)(D * nc), hipMemcpyDefault, c->stream);
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, c->stream, (const T*)tmp, m.tab(), m.at(GLM_W), (T*)nullptr, (int)m.P, m.G, D, nc,
+                       (const int*)nullptr);
+    rc = glm_launch_eta_cat(c, (const T*)m.at(GLM_W), (const int*)nullptr, nc, glm_small(c, nrb, nc), (T*)nullptr, (T*)nullptr, pr);
+    if (!rc) e = hipMemcpyAsync(static_cast<T*>(out) + j0 * per_col, pr, sizeof(T) * (size_t)(per_col * nc), hipMemcpyDefault, c->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  (void)hipFree(tmp);
+  if (rc) return rc;
+  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("glm_class_probs: ") + hipGetErrorString(e != hipSuccess ? e : es));
+  return AHMC_OK;
 }

@@ -683,3 +683,140 @@ def ordinal_logdensity(X, y, theta, n_categories, groups=(), offset=None, prior_
             T = S[j] if j == C - 2 else S[j] + T
             g[PG + j] = (kap[j] - loc1) * (1.0 / (sc1 * sc1)) - T if j == 0 else -d[j] * T + (kap[j] - locg) * (1.0 / (scg * scg))
     return lp, -g
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# include/ahmc_glm_categorical.h: the categorical-logit family for unordered classes (csrc/ahmc_glm.hpp: glm_link_cat, k_glm_eta_cat)
+# ------------------------------------------------------------------------------------------------------------------------------
+__doc__ += """
+The categorical-logit (softmax) family (categorical_logdensity, categorical_pointwise, categorical_link, categorical_probs):
+    y_i ∈ {0, …, C − 1}, unordered; class 0 is the reference, η_0 ≡ 0; K = C − 1 coefficient blocks.  A block has P_b = P_x + Σ L_f rows
+    laid out as a non-categorical model's P rows (dense first, then factor 0's levels, …); the coefficient parameters are P = K·P_b
+    rows, block k (k = 1 … K, class k) in rows [(k−1)·P_b, k·P_b).  θ (D, N), D = P + G: no rows of the family's own.  Groups and
+    prior_prec address the P rows; a group lies inside one block or is a union of whole blocks.
+    η_k = X·W_k[0:P_x] + the factors' gathers from block k in order + offset[:, k−1] last      (offset (n_obs, K) or None)
+    Per element:  m = 0, then m = η_k if η_k > m for ascending k (a NaN never wins the comparison);
+        e_0 = exp(−m), e_k = exp(η_k − m);  s = e_0, then s = s + e_k for ascending k (one term is exactly 1: s ∈ [1, C]);
+        inv = 1/s,  lse = m + log(s);  ℓ = η_y − lse with η_0 = 0;  p_0 = e_0·inv, p_k = e_k·inv;  u_k = 1 − p_k if y = k, else −p_k.
+    Everything is finite for finite η.  η_k = NaN or +∞ makes s and so ℓ NaN; η_k = −∞ is a class of probability 0 (ℓ = −∞ if it is
+    the observed one); ℓπ is sanitised to −Inf either way.
+    ℓπ and g: Σℓ by `block_sums`; rows of block k of R = −Xᵀu_k by `_xtu` (slices of K_SLICE, slice sums ascending), class after
+    class; the prior's and the groups' terms by `_hier_finish` on the P rows.
+There is no multiply-add in the link.  A chain's bits depend on (n_obs, P_x, factors, groups, C, element type) only.
+"""
+
+CATEGORICAL_LOGIT = 6
+CATEGORICAL_FAMILIES = {"categorical_logit": CATEGORICAL_LOGIT}
+CATEGORICAL_MAX_CATEGORIES = 16   # AHMC_GLM_CATEGORICAL_MAX_CATEGORIES
+
+
+def check_classes(y, n_categories):
+    """y as int64 classes in [0, C), 2 <= C <= CATEGORICAL_MAX_CATEGORIES"""
+    C = int(n_categories)
+    if not 2 <= C <= CATEGORICAL_MAX_CATEGORIES:
+        raise ValueError(f"DomainError: n_categories = {C}; must be in [2, {CATEGORICAL_MAX_CATEGORIES}]")
+    y = np.asarray(y, dtype=np.float64).ravel()
+    bad = np.flatnonzero(~((y >= 0) & (y < C) & (y == np.floor(y))))
+    if bad.size:
+        raise ValueError(f"DomainError: y[{int(bad[0]) + 1}] = {y[bad[0]]} is not a category: an integer in [0, {C})")
+    return y.astype(np.int64), C
+
+
+def check_class_groups(groups, P_b, K):
+    """`check_groups` over the K·P_b rows, and each group inside one class's block or a union of whole blocks"""
+    groups = check_groups(groups, K * P_b)
+    for k, (lo, hi, _, _) in enumerate(groups):
+        if lo // P_b != (hi - 1) // P_b and (lo % P_b or hi % P_b):
+            raise ValueError(f"ArgumentError: group {k + 1} = [{lo}, {hi}) straddles the classes' blocks of {P_b} rows: a group lies inside one "
+                             "block or is a union of whole blocks")
+    return groups
+
+
+def categorical_link(y, eta):
+    """(ℓ (n_obs, N), u (K, n_obs, N), p (C, n_obs, N)) in η's floating type: y integer classes (n_obs,), η (K, n_obs, N) — plane
+    k − 1 is η_k"""
+    eta = np.asarray(eta)
+    eta = eta.astype(np.float64) if eta.dtype.kind != "f" else eta
+    y = np.asarray(y).astype(np.int64)
+    K = eta.shape[0]
+    yc = y.reshape(y.shape + (1,) * (eta.ndim - 1 - y.ndim))
+    one = eta.dtype.type(1)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore", divide="ignore"):
+        m = np.zeros(eta.shape[1:], dtype=eta.dtype)
+        for k in range(K):
+            m = np.where(eta[k] > m, eta[k], m)
+        e0 = np.exp(-m)
+        e = [np.exp(eta[k] - m) for k in range(K)]
+        s = e0
+        for k in range(K):
+            s = s + e[k]
+        inv = one / s
+        lse = m + np.log(s)
+        eta_y = np.zeros_like(m)
+        for k in range(K):
+            eta_y = np.where(yc == k + 1, eta[k], eta_y)
+        p = np.stack([e0 * inv] + [e[k] * inv for k in range(K)])
+        u = np.stack([np.where(yc == k + 1, one - p[k + 1], -p[k + 1]) for k in range(K)])
+    return eta_y - lse, u, p
+
+
+def categorical_probs(eta):
+    """(C, …) class probabilities at η (K, n_obs, N) [or (K, n_obs)]: `categorical_link`'s p — the mirror of ahmc_glm_class_probs"""
+    eta = np.asarray(eta, dtype=np.float64)
+    return categorical_link(np.zeros(eta.shape[1], dtype=np.int64), eta)[2]
+
+
+def _categorical_args(X, y, theta, n_categories, groups, factors):
+    y, C = check_classes(y, n_categories)
+    X = np.asarray(X, dtype=np.float64)
+    factors = check_factors(factors, X.shape[0])
+    K = C - 1
+    Pb = X.shape[1] + sum(L for _, L in factors)
+    th = np.ascontiguousarray(theta, dtype=np.float64)
+    th = th.reshape(-1, 1) if th.ndim == 1 else th
+    groups = check_class_groups(groups, Pb, K)
+    if y.size != X.shape[0]:
+        raise ValueError(f"DimensionMismatch: X {X.shape}, y {y.shape}")
+    if th.shape[0] != K * Pb + len(groups):
+        raise ValueError(f"DimensionMismatch: θ {th.shape}, (C − 1)·P_b + G = {K}·{Pb} + {len(groups)}")
+    return X, y, th, K, Pb, groups, factors
+
+
+def _class_offset(offset, n_obs, K):
+    if offset is None:
+        return None
+    off = np.asarray(offset, dtype=np.float64)
+    off = off.reshape(n_obs, 1) if off.ndim == 1 and K == 1 else off
+    if off.shape != (n_obs, K):
+        raise ValueError(f"DimensionMismatch: offset {off.shape}, expected (n_obs, C − 1) = ({n_obs}, {K})")
+    return off
+
+
+def _categorical_at(X, y, th, K, Pb, groups, factors, offset):
+    """(W, τ, η (K, n_obs, N), ℓ, u, p): each class's predictor through `_link_at`'s path on its block, with a family that ignores y"""
+    off = _class_offset(offset, X.shape[0], K)
+    W, tau = hier_coefficients(th, K * Pb, groups)
+    W = np.ascontiguousarray(W)
+    eta = np.stack([_link_at(GAUSSIAN_IDENTITY, X, W[k * Pb:(k + 1) * Pb], [], factors, np.zeros(X.shape[0]), None if off is None else off[:, k], 1.0)[2]
+                    for k in range(K)])
+    return (W, tau, eta, *categorical_link(y, eta))
+
+
+def categorical_pointwise(X, y, theta, n_categories, groups=(), offset=None, factors=None):
+    """(η (K, n_obs, N), ℓ(y_i, η_i) (n_obs, N)): the mirror of ahmc_glm_pointwise on a categorical model"""
+    X, y, th, K, Pb, groups, factors = _categorical_args(X, y, theta, n_categories, groups, factors)
+    out = _categorical_at(X, y, th, K, Pb, groups, factors, offset)
+    return out[2], out[3]
+
+
+def categorical_logdensity(X, y, theta, n_categories, groups=(), offset=None, prior_prec=None, factors=None):
+    """(ℓπ (N,), ∇ℓπ (D, N)) at θ (D, N), D = (C − 1)·P_b + G, of the categorical-logit model.  ℓπ is returned as computed (`sanitize`)."""
+    X, y, th, K, Pb, groups, factors = _categorical_args(X, y, theta, n_categories, groups, factors)
+    p = _prior_prec(prior_prec, K * Pb, groups)
+    if p.size != K * Pb:
+        raise ValueError(f"DimensionMismatch: the prior has {p.size} entries, the model (C − 1)·P_b = {K * Pb} coefficients")
+    W, tau, _, ll, u, _ = _categorical_at(X, y, th, K, Pb, groups, factors, offset)
+    with np.errstate(over="ignore", invalid="ignore"):
+        xtu = np.concatenate([_xtu(X, u[k], W[k * Pb:(k + 1) * Pb], factors) for k in range(K)])
+        lp, g = _hier_finish(th, W, tau, -xtu, block_sums(ll).sum(axis=0), p, groups)
+    return lp, -g

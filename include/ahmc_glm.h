@@ -56,7 +56,8 @@ int32_t ahmc_get_target_glm(ahmc_ctx* ctx, int32_t* family, int64_t* n_obs, doub
 
 /* At the context's current θ: the linear predictor η and / or the pointwise log-likelihood ℓ(y_i, η_i), each (n_obs, N)
  * column-major of the context's element type, into host or device buffers; either may be NULL.  What a posterior-predictive check
- * or LOO needs.  AHMC_ERR_ARGUMENT: no GLM is bound. */
+ * or LOO needs.  A categorical model (ahmc_glm_categorical.h, C classes) has K = C − 1 predictors: eta_out then holds K planes of
+ * (n_obs, N), plane k − 1 being η_k, and loglik_out (n_obs, N).  AHMC_ERR_ARGUMENT: no GLM is bound. */
 int32_t ahmc_glm_pointwise(ahmc_ctx* ctx, void* eta_out, void* loglik_out);
 
 #ifdef __cplusplus

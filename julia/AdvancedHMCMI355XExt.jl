@@ -520,5 +520,6 @@ include("AdvancedHMCMI355XGLMHier.jl")  # set_target!(z, ::HierGLMTarget), hglm_
 include("AdvancedHMCMI355XGLMAux.jl")  # set_target!(z, ::AuxGLMTarget), glm_dispersion: include/ahmc_glm_aux.h
 include("AdvancedHMCMI355XGLMFactor.jl")  # set_target!(z, ::FactorGLMTarget), get_target_glm_factor: include/ahmc_glm_factor.h
 include("AdvancedHMCMI355XGLMOrdinal.jl")  # set_target!(z, ::OrdinalGLMTarget), glm_cutpoints: include/ahmc_glm_ordinal.h
+include("AdvancedHMCMI355XGLMCategorical.jl")  # set_target!(z, ::CategoricalGLMTarget), glm_class_probs: include/ahmc_glm_categorical.h
 
 end # module
