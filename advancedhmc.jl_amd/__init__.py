@@ -15,5 +15,6 @@ from . import diagnostics  # noqa: E402,F401
 from . import rank_update  # noqa: E402,F401
 from . import glm  # noqa: E402,F401
 from .diagnostics import ess, bundle_samples, summarystats  # noqa: E402,F401
+from .glm import psis_loo, loo_summary, loo_compare  # noqa: E402,F401
 
 __version__ = "0.1.0"

@@ -265,6 +265,16 @@ GLM_CATEGORICAL_SIGNATURES = {
     "ahmc_glm_class_probs": (_i32, [_vp, _vp, _i64, _vp]),
 }
 
+# include/ahmc_glm_loo.h: the pointwise log-likelihood of the kept draws, PSIS-LOO and WAIC of a GLM target (likewise: the HIP engine only)
+AHMC_GLM_LOO_VERSION = 1
+GLM_LOO_MAX_VALUES = 2**31 - 1
+GLM_LOO_MAX_TAIL = 4096
+GLM_LOO_SIGNATURES = {
+    "ahmc_glm_loo_version": (_i32, []),
+    "ahmc_glm_loglik": (_i32, [_vp, _vp, _i64, _vp]),
+    "ahmc_glm_loo": (_i32, [_vp, _vp, _i64, C.POINTER(_f64), C.POINTER(_f64)]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -377,6 +387,15 @@ class CLib:
             v = self.dll.ahmc_glm_categorical_version()
             if v != AHMC_GLM_CATEGORICAL_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm_categorical version {v}, expected {AHMC_GLM_CATEGORICAL_VERSION}")
+        # ahmc_glm_loo.h: likewise
+        gloo = [getattr(self.dll, name, None) for name in GLM_LOO_SIGNATURES]
+        self.has_glm_loo = all(fn is not None for fn in gloo)
+        if self.has_glm_loo:
+            for fn, (res, args) in zip(gloo, GLM_LOO_SIGNATURES.values()):
+                fn.restype, fn.argtypes = res, args
+            v = self.dll.ahmc_glm_loo_version()
+            if v != AHMC_GLM_LOO_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_loo version {v}, expected {AHMC_GLM_LOO_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

@@ -970,6 +970,35 @@ class Engine:
         self._call("ahmc_glm_class_probs", ptr, n, capi.as_ptr(out) if n else None)
         return out
 
+    def glm_loglik(self, draws=None, n_cols=None):
+        """ℓ(y_i, η_i) (n_obs, n) of every observation at draws θ (D, n) of the bound GLM — an array (default: the context's current θ),
+        or a device pointer (an int) together with `n_cols`; the (D, N, K) buffer of `run(samples_out=ptr)` is passed with
+        n_cols = N·K: ahmc_glm_loglik"""
+        self._need("has_glm_loo", "ahmc_glm_loo.h", "glm_loglik")
+        n_obs = C.c_int64()
+        self._call("ahmc_get_target_glm", None, C.byref(n_obs), None)
+        ptr, n = self._draws("glm_loglik", draws, n_cols)
+        out = np.empty((n_obs.value, n), dtype=self.dtype, order="F")
+        self._call("ahmc_glm_loglik", ptr, n, capi.as_ptr(out) if n else None)
+        return out
+
+    def glm_loo(self, draws=None, n_cols=None, log_weights=False):
+        """PSIS-LOO and WAIC of the bound GLM over draws θ (D, n), passed as to `glm_loglik`: {"elpd_loo", "pareto_k", "lpd", "p_waic"},
+        each (n_obs,) float64, and with `log_weights` the normalised "log_weights" (n, n_obs) in the draws' order — what glm.psis_loo
+        returns for the same ℓ (glm.loo_summary and glm.loo_compare take either): ahmc_glm_loo"""
+        self._need("has_glm_loo", "ahmc_glm_loo.h", "glm_loo")
+        n_obs = C.c_int64()
+        self._call("ahmc_get_target_glm", None, C.byref(n_obs), None)
+        ptr, n = self._draws("glm_loo", draws, n_cols)
+        pw = np.full((4, n_obs.value), np.nan, order="F")
+        lw = np.empty((n, n_obs.value), order="F") if log_weights else None
+        pd = C.POINTER(C.c_double)
+        self._call("ahmc_glm_loo", ptr, n, pw.ctypes.data_as(pd) if n else None, lw.ctypes.data_as(pd) if (log_weights and n) else None)
+        out = {k: pw[q].copy() for q, k in enumerate(("elpd_loo", "pareto_k", "lpd", "p_waic"))}
+        if log_weights:
+            out["log_weights"] = lw
+        return out
+
     def hglm_coefficients(self, theta=None, n_cols=None):
         """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer
         (an int) together with `n_cols`: ahmc_hglm_coefficients"""

@@ -11,6 +11,7 @@
 #include "ahmc_glm_factor.h"
 #include "ahmc_glm_ordinal.h"
 #include "ahmc_glm_categorical.h"
+#include "ahmc_glm_loo.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -19,6 +20,7 @@
 #include "ahmc_diag.hpp"
 #include "ahmc_rank_update.hpp"
 #include "ahmc_glm.hpp"
+#include "ahmc_glm_loo.hpp"
 #include "ahmc_lowrank_adapt.hpp"
 #include "ahmc_draw_sched.hpp"
 
@@ -483,6 +485,7 @@ int launch_fill_caches_builtin(Ctx<T>* c) {
 #include "ahmc_ext_host.hpp"
 #include "ahmc_multi_host.hpp"
 #include "ahmc_diag_host.hpp"
+#include "ahmc_glm_loo_host.hpp"
 
 void comm_destroy_raw(void* comm) {
   if (comm && rccl_api().CommDestroy) (void)rccl_api().CommDestroy(static_cast<ncclComm_t>(comm));
@@ -2392,6 +2395,17 @@ int32_t ahmc_glm_categorical_get_target(ahmc_ctx* ctx, int32_t* n_categories, in
 
 int32_t ahmc_glm_class_probs(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* out) {
   FOR_CTX_MUT(ctx, { return glm_class_probs(c, theta, n_cols, out); });
+}
+
+// ---- include/ahmc_glm_loo.h: the pointwise log-likelihood of the kept draws, PSIS-LOO and WAIC ------------------------------------------
+int32_t ahmc_glm_loo_version(void) { return AHMC_GLM_LOO_VERSION; }
+
+int32_t ahmc_glm_loglik(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* out) {
+  FOR_CTX_MUT(ctx, { return glm_loglik(c, theta, n_cols, out); });
+}
+
+int32_t ahmc_glm_loo(ahmc_ctx* ctx, const void* theta, int64_t n_cols, double* pointwise_out, double* log_weights_out) {
+  FOR_CTX_MUT(ctx, { return glm_loo(c, theta, n_cols, pointwise_out, log_weights_out); });
 }
 
 }  // extern "C"

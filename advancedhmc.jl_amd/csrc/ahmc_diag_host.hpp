@@ -23,6 +23,22 @@ static void dg_scan(hipStream_t s, G gen, int64_t L, W wr, uint32_t* part) {
   hipLaunchKernelGGL((k_sc_apply<MAXOP, EXCL, G, W>), dim3((unsigned)P), dim3(DG_THREADS), 0, s, gen, L, part, wr);
 }
 
+// Stable ascending LSD radix sort of (key, position) in every one of `nseg` segments of S values, 8 bits per pass from bit `shift0`
+// (bits below it: the same in every key, or a function of the bits above).  Tiles never straddle a segment.  The result is in (ka, ia)
+// after an even number of passes, else in (kb, ib): the references are swapped to name it.  cnt: nseg·256·tps counters.
+template <class KT>
+static void dg_sort(hipStream_t s, KT*& ka, KT*& kb, uint32_t*& ia, uint32_t*& ib, int64_t S, int64_t nseg, int64_t tps, uint32_t* cnt, uint32_t* part,
+                    int shift0 = 0) {
+  const int64_t ntiles = nseg * tps, L = nseg * 256 * tps;
+  for (int shift = shift0; shift < (int)(8 * sizeof(KT)); shift += 8) {
+    hipLaunchKernelGGL((k_dg_hist<KT>), dim3((unsigned)ntiles), dim3(DG_THREADS), 0, s, ka, S, tps, shift, cnt);
+    dg_scan<0, true>(s, GenArray{cnt}, L, WrArray{cnt}, part);
+    hipLaunchKernelGGL((k_dg_scatter<KT>), dim3((unsigned)ntiles), dim3(DG_THREADS), 0, s, ka, ia, kb, ib, S, tps, shift, cnt);
+    std::swap(ka, kb);
+    std::swap(ia, ib);
+  }
+}
+
 // average ranks of the tie runs of a sorted batch (eq: equality of sorted neighbours) → Φ⁻¹ → z[seg·S + idx[g]]
 template <class E>
 static void dg_rank_runs(hipStream_t s, E eq, int64_t S, int64_t M, const uint32_t* idx, uint32_t* rs, uint32_t* re, uint32_t* part, double* z) {
@@ -131,14 +147,7 @@ int diag_impl(Ctx<T>* c, const void* draws, int64_t K, int64_t max_lag, int64_t 
     // 2. LSD radix sort of (key, position), 8 bits per pass; an even number of passes leaves the result in (KA, IA)
     KT *ksrc = KA, *kdst = KB;
     uint32_t *isrc = IA, *idst = IB;
-    const int64_t ntiles = (int64_t)Bb * tps, L = (int64_t)Bb * 256 * tps;
-    for (int shift = 0; shift < (int)(8 * ks); shift += 8) {
-      hipLaunchKernelGGL((k_dg_hist<KT>), dim3((unsigned)ntiles), dim3(DG_THREADS), 0, s, ksrc, S, tps, shift, cnt);
-      dg_scan<0, true>(s, GenArray{cnt}, L, WrArray{cnt}, part);
-      hipLaunchKernelGGL((k_dg_scatter<KT>), dim3((unsigned)ntiles), dim3(DG_THREADS), 0, s, ksrc, isrc, kdst, idst, S, tps, shift, cnt);
-      std::swap(ksrc, kdst);
-      std::swap(isrc, idst);
-    }
+    dg_sort<KT>(s, ksrc, kdst, isrc, idst, S, Bb, tps, cnt, part);
     // 3. order statistics; 4. z; 5. z_f
     hipLaunchKernelGGL((k_dg_segstat<KT>), dim3((unsigned)((Bb + 63) / 64)), dim3(64), 0, s, KA, S, Bb, st, split);
     dg_rank_runs(s, EqOf<KT>{KA}, S, M, IA, RS, RE, part, Z);

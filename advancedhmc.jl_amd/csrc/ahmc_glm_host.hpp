@@ -66,8 +66,9 @@ int glm_release(Ctx<T>* c) {
 
 // η (and from it U, partial; on request η and ℓ themselves) for ncols listed chains; th: the coefficients, (D, N) with column stride D.
 // A model with factors: the product over its Px dense columns, the factors' rows of th gathered in the epilogue (k_glm_eta_f).
+// theta: the (D_θ, ·) array whose last row is the dispersion (default: the context's θ; ahmc_glm_loglik: a chunk of the caller's draws).
 template <class T>
-int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols, bool small, T* eta_out, T* ll_out) {
+int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols, bool small, T* eta_out, T* ll_out, const T* theta = nullptr) {
   const GlmModel<T>& m = c->glm;
   const int n_obs = (int)m.n_obs;
   const int64_t nrb = (n_obs + GB_M - 1) / GB_M;
@@ -77,7 +78,7 @@ int glm_launch_eta(Ctx<T>* c, const T* th, int D, const int* list, int64_t ncols
   T* U = m.at(GLM_U);
   T* part = m.at(GLM_PART);
   // a sampled dispersion: s is row D − 1 of the chain's own θ (th holds W); Σ ∂ℓ/∂s per row block
-  const T* aux = m.aux ? c->th + (c->D - 1) : nullptr;
+  const T* aux = m.aux ? (theta ? theta : (const T*)c->th) + (c->D - 1) : nullptr;
   T* part_s = m.aux ? m.at(GLM_PART_S) : nullptr;
   if (glm_aux_family(m.family) != m.aux) return fail(c, AHMC_ERR_STATE, "glm: the family and the dispersion row disagree in the context");
   if ((m.family == AHMC_GLM_ORDERED_LOGIT) != (m.n_cat > 0)) return fail(c, AHMC_ERR_STATE, "glm: the family and the cutpoint rows disagree in the context");
@@ -163,11 +164,12 @@ int glm_launch_eta_cat(Ctx<T>* c, const T* W, const int* list, int64_t ncols, bo
   return AHMC_OK;
 }
 
-// an ordinal model's cutpoint table (c, lg, r) of the listed chains from the κ rows of the context's θ, before k_glm_eta
+// an ordinal model's cutpoint table (c, lg, r) of the listed chains from the κ rows of the context's θ (or of `theta`, a chunk of the
+// caller's draws), before k_glm_eta
 template <class T>
-void glm_launch_cut(Ctx<T>* c, const int* list, int64_t n) {
+void glm_launch_cut(Ctx<T>* c, const int* list, int64_t n, const T* theta = nullptr) {
   const GlmModel<T>& m = c->glm;
-  hipLaunchKernelGGL((k_glm_cut<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const T*)c->th, c->D, c->D - (m.n_cat - 1), m.n_cat - 1,
+  hipLaunchKernelGGL((k_glm_cut<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, theta ? theta : (const T*)c->th, c->D, c->D - (m.n_cat - 1), m.n_cat - 1,
                      m.at(GLM_CUT), c->N, n, list, 1);
 }
 

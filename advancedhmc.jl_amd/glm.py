@@ -820,3 +820,194 @@ def categorical_logdensity(X, y, theta, n_categories, groups=(), offset=None, pr
         xtu = np.concatenate([_xtu(X, u[k], W[k * Pb:(k + 1) * Pb], factors) for k in range(K)])
         lp, g = _hier_finish(th, W, tau, -xtu, block_sums(ll).sum(axis=0), p, groups)
     return lp, -g
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# include/ahmc_glm_loo.h: PSIS-LOO and WAIC of the kept draws (csrc/ahmc_glm_loo.hpp: k_loo_keys, k_loo_psis; the sort of csrc/ahmc_diag.hpp)
+# ------------------------------------------------------------------------------------------------------------------------------
+__doc__ += """
+Model comparison from the kept draws (psis_loo, psis_smooth_tail, gpd_fit, gpd_quantile, psis_tail_length, loo_summary, loo_compare):
+    Pareto-smoothed importance-sampling leave-one-out (Vehtari, Simpson, Gelman, Yao & Gabry; R loo::psis with r_eff = 1) of a pointwise
+    log-likelihood matrix (n_obs, S), one observation (row) at a time, in float64 (or the `dtype` asked for).
+    a_s = −ℓ_s with −0 taken as +0.  The draws are sorted by a, ascending and stably (ties keep the draws' order); the sorted position is
+    r = 0 … S − 1.  lr_r = a_r − a_{S−1} (the subtraction is monotone, so this order sorts lr too; draws whose a differ but whose lr round
+    to the same value keep the order of a).  M = ⌈min(0.2·S, 3·√S)⌉ in float64; the tail is r >= S − M, cut = lr_{S−M−1}.
+    The tail is smoothed iff M >= 5 and lr_{S−M} < lr_{S−1} (`psis_smooth_tail`): ec = exp(cut), x_j = exp(tail_j) − ec (j = 1 … M),
+    `gpd_fit`: Mg = 30 + ⌊√M⌋, x* = x[⌊M/4 + ½⌋], θ_j = 1/x_M + (1 − √(Mg/(j − ½)))/(3·x*), k_j = W(log1p(−θ_j·x_i))/M,
+    l_j = M·(log(−θ_j/k_j) − k_j − 1), w_j = 1/(Σ_i exp(l_i − l_j)) and θ̂ = Σ_j θ_j·w_j, both from +0 in ascending index, one term at a
+    time; k = W(log1p(−θ̂·x_i))/M, σ = −k/θ̂, k̂ = (M·k + 5)/(M + 10).  k̂ or σ not finite: nothing is smoothed, k̂ = +Inf.  Otherwise the
+    j-th smallest tail value becomes v = log(σ·expm1(−k̂·log1p(−p_j))/k̂ + ec), p_j = (j − ½)/M, and 0 where v > 0.
+    With lr now holding the smoothed tail:  lw_r = lr_r − (m + log B(exp(lr_r − m))), m = max lr;  elpd_loo = m₂ + log B(exp(t_r − m₂)),
+    t_r = lw_r − a_r, m₂ = max t;  lpd = (ℓ_max + log B(exp(ℓ_r − ℓ_max))) − log S, ℓ_r = −a_r, ℓ_max = −a_0;
+    p_waic = B((ℓ_r − mean)²)/(S − 1), mean = B(ℓ_r)/S (NaN at S = 1).  A row with a non-finite ℓ: NaN everywhere.
+    The sums.  W (one wave): lane l of 64 adds its elements i = l, l + 64, … from +0 in ascending order; then v_l = v_l + v_{l xor o}
+    for o = 32, 16, 8, 4, 2, 1.  B (a workgroup, over the sorted positions): thread t of 256 adds r = t, t + 256, … from +0; the butterfly
+    over each of the four waves; then ((w0 + w1) + w2) + w3.  No multiply-add.  An observation's outputs depend on its S values in the
+    draws' order alone.
+"""
+
+LOO_MAX_TAIL = 4096   # AHMC_GLM_LOO_MAX_TAIL
+
+
+def _wave_sum(v):
+    """W over the last axis"""
+    v = np.asarray(v)
+    n = v.shape[-1]
+    rows = max(1, -(-n // 64))
+    p = np.zeros(v.shape[:-1] + (rows * 64,), dtype=v.dtype)
+    p[..., :n] = v
+    p = p.reshape(v.shape[:-1] + (rows, 64))
+    acc = np.zeros(v.shape[:-1] + (64,), dtype=v.dtype)
+    for r in range(rows):
+        acc = acc + p[..., r, :]
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[..., lanes ^ o]
+    return acc[..., 0]
+
+
+def _block_sum(v):
+    """B over the last axis"""
+    v = np.asarray(v)
+    n = v.shape[-1]
+    rows = max(1, -(-n // 256))
+    p = np.zeros(v.shape[:-1] + (rows * 256,), dtype=v.dtype)
+    p[..., :n] = v
+    p = p.reshape(v.shape[:-1] + (rows, 256))
+    acc = np.zeros(v.shape[:-1] + (256,), dtype=v.dtype)
+    for r in range(rows):
+        acc = acc + p[..., r, :]
+    acc = acc.reshape(v.shape[:-1] + (4, 64))
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[..., lanes ^ o]
+    w = acc[..., 0]
+    return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
+
+
+def psis_tail_length(S):
+    """M = ⌈min(0.2·S, 3·√S)⌉"""
+    return int(np.ceil(min(0.2 * float(S), 3.0 * np.sqrt(float(S)))))
+
+
+def gpd_quantile(p, k, sigma):
+    """the quantile function of the generalised Pareto distribution with location 0: σ·expm1(−k·log1p(−p))/k"""
+    return sigma * np.expm1(-k * np.log1p(-p)) / k
+
+
+def gpd_fit(x):
+    """(k̂, σ) of Zhang & Stephens' fit to x (M,), ascending and >= 0, k̂ shrunk towards ½ with weight 10: (M·k + 5)/(M + 10)"""
+    x = np.asarray(x)
+    x = x.astype(np.float64) if x.dtype.kind != "f" else x
+    ft = x.dtype.type
+    M = x.size
+    Md = ft(M)
+    Mg = 30 + int(np.floor(np.sqrt(float(M))))
+    with np.errstate(all="ignore"):
+        xs, xM = x[int(np.floor(M / 4.0 + 0.5)) - 1], x[-1]
+        j = np.arange(1, Mg + 1).astype(x.dtype)
+        th = ft(1) / xM + (ft(1) - np.sqrt(ft(Mg) / (j - ft(0.5)))) / (ft(3) * xs)
+        kj = _wave_sum(np.log1p(-th[:, None] * x[None, :])) / Md
+        l = Md * (np.log(-th / kj) - kj - ft(1))
+        E = np.exp(l[None, :] - l[:, None])            # (j, i)
+        s = np.zeros(Mg, dtype=x.dtype)
+        for i in range(Mg):
+            s = s + E[:, i]
+        w = ft(1) / s
+        that = ft(0)
+        for q in range(Mg):
+            that = that + th[q] * w[q]
+        k = _wave_sum(np.log1p(-that * x)) / Md
+        return (Md * k + ft(5)) / (Md + ft(10)), -k / that
+
+
+def psis_smooth_tail(tail, cut):
+    """(the smoothed tail, k̂) of the M largest lr, ascending, and the value just below them; (the tail as it was, +Inf) if it is not
+    smoothed"""
+    tail = np.asarray(tail)
+    ft = tail.dtype.type
+    M = tail.size
+    if M < 5 or not tail[0] < tail[-1]:
+        return tail, ft(np.inf)
+    with np.errstate(all="ignore"):
+        ec = np.exp(cut)
+        khat, sigma = gpd_fit(np.exp(tail) - ec)
+        if not (np.isfinite(khat) and np.isfinite(sigma)):
+            return tail, ft(np.inf)
+        p = (np.arange(1, M + 1).astype(tail.dtype) - ft(0.5)) / ft(M)
+        v = np.log(gpd_quantile(p, khat, sigma) + ec)
+        return np.where(v > 0, ft(0), v), khat
+
+
+def psis_loo(loglik, dtype=np.float64, log_weights=True):
+    """{"elpd_loo", "pareto_k", "lpd", "p_waic"} (n_obs,) each, and "log_weights" (S, n_obs) in the draws' order (on request), of the
+    pointwise log-likelihood `loglik` (n_obs, S) — the mirror of ahmc_glm_loo"""
+    ll = np.asarray(loglik)
+    if ll.ndim != 2 or ll.shape[1] < 1:
+        raise ValueError(f"DimensionMismatch: loglik {ll.shape}, expected (n_obs, S) with S >= 1")
+    dt = np.dtype(dtype)
+    ft = dt.type
+    n_obs, S = ll.shape
+    M = psis_tail_length(S)
+    if M > LOO_MAX_TAIL:
+        raise ValueError(f"ArgumentError: S = {S} draws have a tail of {M} values; the limit is {LOO_MAX_TAIL}")
+    out = {k: np.full(n_obs, np.nan, dtype=dt) for k in ("elpd_loo", "pareto_k", "lpd", "p_waic")}
+    lw_all = np.full((S, n_obs), np.nan, dtype=dt) if log_weights else None
+    Sd = ft(S)
+    with np.errstate(all="ignore"):
+        for i in range(n_obs):
+            a = -ll[i].astype(dt)
+            if not np.isfinite(a).all():
+                continue
+            a = np.where(a == 0, ft(0), a)
+            order = np.argsort(a, kind="stable")
+            a = a[order]
+            lr = a - a[-1]
+            khat = ft(np.inf)
+            if M >= 5:
+                tail, khat = psis_smooth_tail(lr[S - M:], lr[S - M - 1])
+                lr = np.concatenate([lr[:S - M], tail])
+            l = -a
+            l_max = l[0]
+            s_lpd = _block_sum(np.exp(l - l_max))
+            mean = _block_sum(l) / Sd
+            m1 = lr.max()
+            s_v = _block_sum((l - mean) * (l - mean))
+            lse = m1 + np.log(_block_sum(np.exp(lr - m1)))
+            lw = lr - lse
+            t = lw - a
+            m2 = t.max()
+            out["elpd_loo"][i] = m2 + np.log(_block_sum(np.exp(t - m2)))
+            out["pareto_k"][i] = khat
+            out["lpd"][i] = (l_max + np.log(s_lpd)) - np.log(Sd)
+            out["p_waic"][i] = s_v / (Sd - ft(1))
+            if log_weights:
+                lw_all[order, i] = lw
+    if log_weights:
+        out["log_weights"] = lw_all
+    return out
+
+
+def loo_summary(pw):
+    """totals of `psis_loo`'s (or Engine.glm_loo's) pointwise numbers: Σ elpd_loo, Σ p_loo (p_loo = lpd − elpd_loo), Σ elpd_waic
+    (elpd_waic = lpd − p_waic), each with se = √(n·var) of its pointwise values (var with n − 1), and the counts of k̂ in (0.5, 0.7],
+    (0.7, 1] and (1, ∞]"""
+    elpd, lpd, pwaic, k = (np.asarray(pw[n], dtype=np.float64) for n in ("elpd_loo", "lpd", "p_waic", "pareto_k"))
+    n = elpd.size
+    out = {"n_obs": n}
+    with np.errstate(all="ignore"):
+        for name, v in (("elpd_loo", elpd), ("p_loo", lpd - elpd), ("elpd_waic", lpd - pwaic)):
+            out[name] = float(v.sum())
+            out["se_" + name] = float(np.sqrt(n * v.var(ddof=1))) if n > 1 else float("nan")
+    out["k_counts"] = {"(0.5, 0.7]": int(((k > 0.5) & (k <= 0.7)).sum()), "(0.7, 1]": int(((k > 0.7) & (k <= 1)).sum()), "(1, Inf]": int((k > 1).sum())}
+    return out
+
+
+def loo_compare(pw_a, pw_b):
+    """{"elpd_diff": Σ (elpd_loo_a − elpd_loo_b), "se_diff": √(n·var) of the pointwise differences}: positive favours model a"""
+    a, b = np.asarray(pw_a["elpd_loo"], dtype=np.float64), np.asarray(pw_b["elpd_loo"], dtype=np.float64)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError(f"DimensionMismatch: elpd_loo {a.shape} and {b.shape}: the two models must be fitted to the same observations")
+    d = a - b
+    with np.errstate(all="ignore"):
+        return {"elpd_diff": float(d.sum()), "se_diff": float(np.sqrt(d.size * d.var(ddof=1))) if d.size > 1 else float("nan")}

@@ -521,5 +521,6 @@ include("AdvancedHMCMI355XGLMAux.jl")  # set_target!(z, ::AuxGLMTarget), glm_dis
 include("AdvancedHMCMI355XGLMFactor.jl")  # set_target!(z, ::FactorGLMTarget), get_target_glm_factor: include/ahmc_glm_factor.h
 include("AdvancedHMCMI355XGLMOrdinal.jl")  # set_target!(z, ::OrdinalGLMTarget), glm_cutpoints: include/ahmc_glm_ordinal.h
 include("AdvancedHMCMI355XGLMCategorical.jl")  # set_target!(z, ::CategoricalGLMTarget), glm_class_probs: include/ahmc_glm_categorical.h
+include("AdvancedHMCMI355XGLMLoo.jl")  # glm_loglik, glm_loo: include/ahmc_glm_loo.h
 
 end # module
