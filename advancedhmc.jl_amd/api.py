@@ -904,26 +904,23 @@ class Engine:
         data = (capi.as_ptr(X), capi.as_ptr(y), capi.as_ptr(off), capi.as_ptr(p))
         table = (G, (C.c_int32 * max(G, 1))(*[g.start for g in t.groups]), (C.c_int32 * max(G, 1))(*[g.stop for g in t.groups]),
                  (C.c_int32 * max(G, 1))(*[int(g.centered) for g in t.groups]), (C.c_double * max(G, 1))(*[g.scale for g in t.groups]))
+        lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32) if F else None
+        factors = (F, (C.c_int32 * F)(*[f.n_levels for f in t.factors]) if F else None, lev.ctypes.data_as(C.POINTER(C.c_int32)) if F else None)
+        aux = tuple(float(v) for v in t.aux_prior) if t.aux else (0.0, 1.0)
+        n_obs, Px, P = int(t.n_obs), int(t.P_x), int(t.P)
         if t.n_categories:
-            lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32) if F else None
-            self._call("ahmc_glm_ordinal_set_target", int(t.n_obs), int(t.P_x), *data, *table, F, (C.c_int32 * F)(*[f.n_levels for f in t.factors]) if F else None,
-                       lev.ctypes.data_as(C.POINTER(C.c_int32)) if F else None, int(t.n_categories), (C.c_double * 4)(*t.cut_prior))
+            call = ("ahmc_glm_ordinal_set_target", n_obs, Px, *data, *table, *factors, int(t.n_categories), (C.c_double * 4)(*t.cut_prior))
         elif t.n_classes:
-            lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32) if F else None
-            self._call("ahmc_glm_categorical_set_target", int(t.n_obs), int(t.P_x), *data, *table, F,
-                       (C.c_int32 * F)(*[f.n_levels for f in t.factors]) if F else None, lev.ctypes.data_as(C.POINTER(C.c_int32)) if F else None,
-                       int(t.n_classes))
+            call = ("ahmc_glm_categorical_set_target", n_obs, Px, *data, *table, *factors, int(t.n_classes))
         elif F:
-            lev = np.asfortranarray(np.column_stack([f.index for f in t.factors]), dtype=np.int32)
-            aux = t.aux_prior if t.aux else (0.0, 1.0)
-            self._call("ahmc_glm_factor_set_target", int(t.family), int(t.n_obs), int(t.P_x), *data, float(t.scale), *table, F,
-                       (C.c_int32 * F)(*[f.n_levels for f in t.factors]), lev.ctypes.data_as(C.POINTER(C.c_int32)), int(t.aux), float(aux[0]), float(aux[1]))
+            call = ("ahmc_glm_factor_set_target", int(t.family), n_obs, Px, *data, float(t.scale), *table, *factors, int(t.aux), *aux)
         elif t.aux:
-            self._call("ahmc_glm_aux_set_target", int(t.family), int(t.n_obs), int(t.P), *data, *table, float(t.aux_prior[0]), float(t.aux_prior[1]))
+            call = ("ahmc_glm_aux_set_target", int(t.family), n_obs, P, *data, *table, *aux)
         elif hier:
-            self._call("ahmc_hglm_set_target", int(t.family), int(t.n_obs), int(t.P), *data, float(t.scale), *table)
+            call = ("ahmc_hglm_set_target", int(t.family), n_obs, P, *data, float(t.scale), *table)
         else:
-            self._call("ahmc_set_target_glm", int(t.family), int(t.n_obs), *data, float(t.scale))
+            call = ("ahmc_set_target_glm", int(t.family), n_obs, *data, float(t.scale))
+        self._call(*call)
 
     def _draws(self, who, theta, n_cols):
         """(pointer, n) of draws θ (D, n): an array (default: the context's current θ), or a device pointer (an int) together with `n_cols`"""
@@ -938,60 +935,58 @@ class Engine:
             raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: θ {th.shape}, expected ({self.D}, {n_cols if n_cols is not None else 'n'})")
         return capi.as_ptr(np.asfortranarray(th, dtype=self.dtype)), th.shape[1]   # (the pointer owns the array)
 
+    def _glm_get(self, getter, ctype, pos, n_args):
+        """one value of the bound GLM: argument `pos` of the `n_args` outputs of an ahmc_*_get_target call (the others NULL)"""
+        v = ctype()
+        self._call(getter, *[C.byref(v) if i == pos else None for i in range(n_args)])
+        return v.value
+
+    def _on_draws(self, flag, header, entry, draws, n_cols, lead):
+        """the post-processing entry points that take draws θ (D, n) — an array (default: the context's current θ), or a device
+        pointer (an int) together with `n_cols`: check the feature flag, ask the bound model for the outputs' leading axes
+        (`lead()`: one tuple per output), resolve the draws, allocate the outputs (…, n) and call `ahmc_<entry>`"""
+        self._need(flag, header, entry)
+        shapes = lead()
+        ptr, n = self._draws(entry, draws, n_cols)
+        outs = [np.empty((*sh, n), dtype=self.dtype, order="F") for sh in shapes]
+        self._call("ahmc_" + entry, ptr, n, *[capi.as_ptr(o) if o.size else None for o in outs])
+        return outs
+
     def glm_dispersion(self, theta=None, n_cols=None):
         """σ or φ = exp(s) (n_cols,) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer (an
         int) together with `n_cols`: ahmc_glm_dispersion"""
-        self._need("has_glm_aux", "ahmc_glm_aux.h", "glm_dispersion")
-        ptr, n = self._draws("glm_dispersion", theta, n_cols)
-        out = np.empty(n, dtype=self.dtype)
-        self._call("ahmc_glm_dispersion", ptr, n, capi.as_ptr(out) if n else None)
-        return out
+        return self._on_draws("has_glm_aux", "ahmc_glm_aux.h", "glm_dispersion", theta, n_cols, lambda: [()])[0]
+
+    def _glm_n_obs(self):
+        return self._glm_get("ahmc_get_target_glm", C.c_int64, 1, 3)
 
     def glm_cutpoints(self, draws=None, n_cols=None):
         """the cutpoints c (C − 1, n) of draws θ (D, n) of the bound ordinal model — an array (default: the context's current θ), or a
         device pointer (an int) together with `n_cols`: ahmc_glm_cutpoints"""
-        self._need("has_glm_ordinal", "ahmc_glm_ordinal.h", "glm_cutpoints")
-        nc = C.c_int32()
-        self._call("ahmc_glm_ordinal_get_target", C.byref(nc), None)
-        ptr, n = self._draws("glm_cutpoints", draws, n_cols)
-        out = np.empty((nc.value - 1, n), dtype=self.dtype, order="F")
-        self._call("ahmc_glm_cutpoints", ptr, n, capi.as_ptr(out) if n else None)
-        return out
+        return self._on_draws("has_glm_ordinal", "ahmc_glm_ordinal.h", "glm_cutpoints", draws, n_cols,
+                              lambda: [(self._glm_get("ahmc_glm_ordinal_get_target", C.c_int32, 0, 2) - 1,)])[0]
 
     def glm_class_probs(self, draws=None, n_cols=None):
         """the class probabilities (C, n_obs, n) of every observation at draws θ (D, n) of the bound categorical model — an array
         (default: the context's current θ), or a device pointer (an int) together with `n_cols`: ahmc_glm_class_probs"""
-        self._need("has_glm_categorical", "ahmc_glm_categorical.h", "glm_class_probs")
-        nc, n_obs = C.c_int32(), C.c_int64()
-        self._call("ahmc_glm_categorical_get_target", C.byref(nc), None)
-        self._call("ahmc_get_target_glm", None, C.byref(n_obs), None)
-        ptr, n = self._draws("glm_class_probs", draws, n_cols)
-        out = np.empty((nc.value, n_obs.value, n), dtype=self.dtype, order="F")
-        self._call("ahmc_glm_class_probs", ptr, n, capi.as_ptr(out) if n else None)
-        return out
+        return self._on_draws("has_glm_categorical", "ahmc_glm_categorical.h", "glm_class_probs", draws, n_cols,
+                              lambda: [(self._glm_get("ahmc_glm_categorical_get_target", C.c_int32, 0, 2), self._glm_n_obs())])[0]
 
     def glm_loglik(self, draws=None, n_cols=None):
         """ℓ(y_i, η_i) (n_obs, n) of every observation at draws θ (D, n) of the bound GLM — an array (default: the context's current θ),
         or a device pointer (an int) together with `n_cols`; the (D, N, K) buffer of `run(samples_out=ptr)` is passed with
         n_cols = N·K: ahmc_glm_loglik"""
-        self._need("has_glm_loo", "ahmc_glm_loo.h", "glm_loglik")
-        n_obs = C.c_int64()
-        self._call("ahmc_get_target_glm", None, C.byref(n_obs), None)
-        ptr, n = self._draws("glm_loglik", draws, n_cols)
-        out = np.empty((n_obs.value, n), dtype=self.dtype, order="F")
-        self._call("ahmc_glm_loglik", ptr, n, capi.as_ptr(out) if n else None)
-        return out
+        return self._on_draws("has_glm_loo", "ahmc_glm_loo.h", "glm_loglik", draws, n_cols, lambda: [(self._glm_n_obs(),)])[0]
 
     def glm_loo(self, draws=None, n_cols=None, log_weights=False):
         """PSIS-LOO and WAIC of the bound GLM over draws θ (D, n), passed as to `glm_loglik`: {"elpd_loo", "pareto_k", "lpd", "p_waic"},
         each (n_obs,) float64, and with `log_weights` the normalised "log_weights" (n, n_obs) in the draws' order — what glm.psis_loo
         returns for the same ℓ (glm.loo_summary and glm.loo_compare take either): ahmc_glm_loo"""
         self._need("has_glm_loo", "ahmc_glm_loo.h", "glm_loo")
-        n_obs = C.c_int64()
-        self._call("ahmc_get_target_glm", None, C.byref(n_obs), None)
+        n_obs = self._glm_n_obs()
         ptr, n = self._draws("glm_loo", draws, n_cols)
-        pw = np.full((4, n_obs.value), np.nan, order="F")
-        lw = np.empty((n, n_obs.value), order="F") if log_weights else None
+        pw = np.full((4, n_obs), np.nan, order="F")
+        lw = np.empty((n, n_obs), order="F") if log_weights else None
         pd = C.POINTER(C.c_double)
         self._call("ahmc_glm_loo", ptr, n, pw.ctypes.data_as(pd) if n else None, lw.ctypes.data_as(pd) if (log_weights and n) else None)
         out = {k: pw[q].copy() for q, k in enumerate(("elpd_loo", "pareto_k", "lpd", "p_waic"))}
@@ -1002,14 +997,8 @@ class Engine:
     def hglm_coefficients(self, theta=None, n_cols=None):
         """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer
         (an int) together with `n_cols`: ahmc_hglm_coefficients"""
-        self._need("has_hglm", "ahmc_glm_hier.h", "hglm_coefficients")
-        P, G = C.c_int64(), C.c_int32()
-        self._call("ahmc_hglm_get_target", C.byref(P), C.byref(G), None, None, None, None)
-        ptr, n = self._draws("hglm_coefficients", theta, n_cols)
-        beta = np.empty((P.value, n), dtype=self.dtype, order="F")
-        tau = np.empty((G.value, n), dtype=self.dtype, order="F")
-        self._call("ahmc_hglm_coefficients", ptr, n, capi.as_ptr(beta) if beta.size else None, capi.as_ptr(tau) if tau.size else None)
-        return beta, tau
+        return tuple(self._on_draws("has_hglm", "ahmc_glm_hier.h", "hglm_coefficients", theta, n_cols,
+                                    lambda: [(self._glm_get("ahmc_hglm_get_target", C.c_int64, 0, 6),), (self._glm_get("ahmc_hglm_get_target", C.c_int32, 1, 6),)]))
 
     def glm_factors(self):
         """(P_x, [n_levels of each factor]) of the bound GLM: ahmc_glm_factor_get_target"""

@@ -23,6 +23,7 @@
 #include "ahmc_glm_loo.hpp"
 #include "ahmc_lowrank_adapt.hpp"
 #include "ahmc_draw_sched.hpp"
+#include "ahmc_glm_spec.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: the entry points are resolved at run time (ahmc_multi_host.hpp)
@@ -108,37 +109,16 @@ struct ExtRun {
   int fe_max = 0, fe_it = 0, fe_total = 0;
 };
 
-// the bound model of AHMC_TARGET_GLM (ahmc_glm_host.hpp; {} = none).  One slab at buf: X, Xᵀ, y, offset, p [, a zero precision, the
-// group table; the factor table, the level indices, the permutations by level and their row pointers], then the workspaces U,
-// partial [, partial_s], gs [, W, R] [, the cutpoint table (3, C−1, N) and partial_c (C−1, row blocks, N) of an ordinal model]; part i
-// starts at off[i]; sizes 0 where the model has none.  A categorical model (ahmc_glm_categorical.h, C classes, K = C − 1): offset is
-// K·n_obs, U is K planes of (n_obs, N), P = K·Pb rows in p, W and R; the factor table and the row pointers describe one block
-enum { GLM_X = 0, GLM_XT, GLM_Y, GLM_OFF, GLM_PREC, GLM_U, GLM_PART, GLM_GS, GLM_W, GLM_R, GLM_ZERO, GLM_TAB, GLM_PART_S, GLM_FTAB, GLM_LEV, GLM_PERM, GLM_RP,
-       GLM_CUT, GLM_PART_C, GLM_PARTS };
+// the bound model of AHMC_TARGET_GLM ({} = none): GlmBound, the checked description and slab layout that glm_spec_check made of the
+// GlmSpec it was bound from (ahmc_glm_spec.hpp), and the slab on the device.  One slab at buf: X, Xᵀ, y, offset, p [, a zero precision,
+// the group table; the factor table, the level indices, the permutations by level and their row pointers], then the workspaces U,
+// partial [, partial_s], gs [, W, R] [, the cutpoint table (3, C−1, N) and partial_c (C−1, row blocks, N) of an ordinal model].  A
+// categorical model (ahmc_glm_categorical.h, C classes, K = C − 1): offset is K·n_obs, U is K planes of (n_obs, N), P = K·Pb rows
+// in p, W and R; the factor table and the row pointers describe one block
 template <class T>
-struct GlmModel {
+struct GlmModel : GlmBound {
   T* buf = nullptr;
-  int64_t off[GLM_PARTS] = {};
-  int family = 0;
-  int64_t n_obs = 0;
-  bool has_offset = false;
-  double scale = 1;
-  int64_t P = 0;  // the coefficient rows: the columns of X and the factors' levels; θ has D = P + G (+ 1 with aux) rows
-  int64_t Px = 0;  // the columns of X (= P without factors)
-  int F = 0;       // the factors (ahmc_glm_factor.h) and their levels; Lt = Σ levels = P − Px
-  int32_t L[GLM_MAX_FACTORS] = {};
-  int64_t Lt = 0;
-  int G = 0;      // the coefficient groups (ahmc_glm_hier.h), as received
-  int32_t lo[HGLM_MAX_GROUPS] = {}, hi[HGLM_MAX_GROUPS] = {}, centered[HGLM_MAX_GROUPS] = {};
-  double A[HGLM_MAX_GROUPS] = {};
-  bool bound_hier = false;  // bound through ahmc_hglm_set_target or ahmc_glm_aux_set_target (n_groups = 0 included)
-  bool aux = false;         // θ ends with s, the log dispersion (ahmc_glm_aux.h); its prior Normal(aux_loc, aux_scale²)
-  double aux_loc = 0, aux_scale = 1;
-  int n_cat = 0;  // the categories C of an ordinal model (ahmc_glm_ordinal.h; 0: not ordinal): θ ends with the C − 1 rows κ
-  double cut_prior[4] = {0, 2.5, 0, 1};  // (loc_1, scale_1, loc_gap, scale_gap)
-  int n_cls = 0;  // the classes C of a categorical model (ahmc_glm_categorical.h; 0: not categorical): P = (C − 1)·Pb, Pb = Px + Lt
 
-  bool on_w() const { return G > 0 || aux || F > 0 || n_cat > 0 || n_cls > 0; }  // the products run on the effective coefficients W, not on θ
   T* at(int part) const { return buf + off[part]; }
   const HglmTab<T>* tab() const { return reinterpret_cast<const HglmTab<T>*>(at(GLM_TAB)); }
   const GlmFacTab* ftab() const { return reinterpret_cast<const GlmFacTab*>(at(GLM_FTAB)); }
@@ -2215,9 +2195,9 @@ int32_t ahmc_glm_version(void) { return AHMC_GLM_VERSION; }
 
 int32_t ahmc_set_target_glm(ahmc_ctx* ctx, int32_t family, int64_t n_obs, const void* X, const void* y, const void* offset, const void* prior_prec,
                             double scale) {
+  const GlmSpec s = glm_spec(GLM_BY_PLAIN, family, n_obs, 0, X, y, offset, prior_prec, scale);
   FOR_CTX_MUT(ctx, {
-    int rc = glm_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), scale);
-    if (rc) return rc;
+    if (int rc = glm_bind(c, s)) return rc;
     return dn_refresh_fused(c);
   });
 }
@@ -2242,10 +2222,9 @@ int32_t ahmc_hglm_version(void) { return AHMC_HGLM_VERSION; }
 int32_t ahmc_hglm_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset,
                              const void* prior_prec, double scale, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
                              const double* hyper_scale) {
+  const GlmSpec s = glm_spec(GLM_BY_HIER, family, n_obs, n_coef, X, y, offset, prior_prec, scale, n_groups, lo, hi, centered, hyper_scale);
   FOR_CTX_MUT(ctx, {
-    const HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale};
-    int rc = hglm_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), scale, hs);
-    if (rc) return rc;
+    if (int rc = glm_bind(c, s)) return rc;
     return dn_refresh_fused(c);
   });
 }
@@ -2277,10 +2256,9 @@ int32_t ahmc_glm_aux_version(void) { return AHMC_GLM_AUX_VERSION; }
 int32_t ahmc_glm_aux_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset,
                                 const void* prior_prec, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
                                 const double* hyper_scale, double aux_loc, double aux_scale) {
+  const GlmSpec s = glm_spec(GLM_BY_AUX, family, n_obs, n_coef, X, y, offset, prior_prec, 1.0, n_groups, lo, hi, centered, hyper_scale, 0, nullptr, nullptr, true, aux_loc, aux_scale);
   FOR_CTX_MUT(ctx, {
-    const HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale, true, aux_loc, aux_scale};
-    int rc = hglm_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), 1.0, hs);
-    if (rc) return rc;
+    if (int rc = glm_bind(c, s)) return rc;
     return dn_refresh_fused(c);
   });
 }
@@ -2306,15 +2284,10 @@ int32_t ahmc_glm_factor_set_target(ahmc_ctx* ctx, int32_t family, int64_t n_obs,
                                    const void* prior_prec, double scale, int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered,
                                    const double* hyper_scale, int32_t n_factors, const int32_t* n_levels, const int32_t* levels, int32_t has_aux,
                                    double aux_loc, double aux_scale) {
+  const GlmSpec s = glm_spec(GLM_BY_FACTOR, family, n_obs, n_coef, X, y, offset, prior_prec, scale, n_groups, lo, hi, centered, hyper_scale, n_factors, n_levels, levels,
+                             has_aux != 0, aux_loc, aux_scale);
   FOR_CTX_MUT(ctx, {
-    HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale, has_aux != 0, aux_loc, aux_scale};
-    hs.F = (int)n_factors;
-    hs.Px = n_coef;
-    hs.n_levels = n_levels;
-    hs.levels = levels;
-    int rc = glm_factor_set(c, (int)family, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset),
-                            static_cast<const T*>(prior_prec), has_aux ? 1.0 : scale, hs);
-    if (rc) return rc;
+    if (int rc = glm_bind(c, s)) return rc;
     return dn_refresh_fused(c);
   });
 }
@@ -2336,15 +2309,10 @@ int32_t ahmc_glm_ordinal_version(void) { return AHMC_GLM_ORDINAL_VERSION; }
 int32_t ahmc_glm_ordinal_set_target(ahmc_ctx* ctx, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset, const void* prior_prec,
                                     int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered, const double* hyper_scale,
                                     int32_t n_factors, const int32_t* n_levels, const int32_t* levels, int32_t n_categories, const double* cut_prior) {
+  const GlmSpec s = glm_spec(GLM_BY_ORDINAL, AHMC_GLM_ORDERED_LOGIT, n_obs, n_coef, X, y, offset, prior_prec, 1.0, n_groups, lo, hi, centered, hyper_scale, n_factors, n_levels,
+                             levels, false, 0.0, 1.0, n_categories, cut_prior);
   FOR_CTX_MUT(ctx, {
-    HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale};
-    hs.F = (int)n_factors;
-    hs.Px = n_coef;
-    hs.n_levels = n_levels;
-    hs.levels = levels;
-    int rc = glm_ordinal_set(c, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), hs,
-                             n_categories, cut_prior);
-    if (rc) return rc;
+    if (int rc = glm_bind(c, s)) return rc;
     return dn_refresh_fused(c);
   });
 }
@@ -2370,15 +2338,10 @@ int32_t ahmc_glm_categorical_version(void) { return AHMC_GLM_CATEGORICAL_VERSION
 int32_t ahmc_glm_categorical_set_target(ahmc_ctx* ctx, int64_t n_obs, int64_t n_coef, const void* X, const void* y, const void* offset, const void* prior_prec,
                                         int32_t n_groups, const int32_t* lo, const int32_t* hi, const int32_t* centered, const double* hyper_scale,
                                         int32_t n_factors, const int32_t* n_levels, const int32_t* levels, int32_t n_categories) {
+  const GlmSpec s = glm_spec(GLM_BY_CATEGORICAL, AHMC_GLM_CATEGORICAL_LOGIT, n_obs, n_coef, X, y, offset, prior_prec, 1.0, n_groups, lo, hi, centered, hyper_scale, n_factors,
+                             n_levels, levels, false, 0.0, 1.0, n_categories);
   FOR_CTX_MUT(ctx, {
-    HglmSpec hs{n_coef, (int)n_groups, lo, hi, centered, hyper_scale};
-    hs.F = (int)n_factors;
-    hs.Px = n_coef;
-    hs.n_levels = n_levels;
-    hs.levels = levels;
-    int rc = glm_categorical_set(c, n_obs, static_cast<const T*>(X), static_cast<const T*>(y), static_cast<const T*>(offset), static_cast<const T*>(prior_prec), hs,
-                                 n_categories);
-    if (rc) return rc;
+    if (int rc = glm_bind(c, s)) return rc;
     return dn_refresh_fused(c);
   });
 }

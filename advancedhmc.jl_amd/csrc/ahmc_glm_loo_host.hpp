@@ -1,64 +1,25 @@
 // ahmc_glm_loo_host.hpp — host side of include/ahmc_glm_loo.h (kernels: ahmc_glm_loo.hpp): the pointwise log-likelihood of a bound GLM
-// at any (D, n_cols) array of draws, and PSIS-LOO / WAIC of it.  Included by ahmc_api.hip after ahmc_glm_host.hpp (the launches of the
-// model's kernels) and ahmc_diag_host.hpp (dg_sort).
+// at any (D, n_cols) array of draws, and PSIS-LOO / WAIC of it.  Included by ahmc_api.hip after ahmc_glm_host.hpp (glm_forward, the
+// draw walker and its argument check) and ahmc_diag_host.hpp (dg_sort).
 
 using namespace ahmc::loo;
 
-// ℓ (n_obs, nc) of nc <= N draws th (D, nc), device memory, into ll_out (device memory): k_hglm_coef, the cutpoints kernel and
-// k_glm_eta / k_glm_eta_cat on the model's own workspaces W, U, partial and the cutpoint table (stream-ordered with every evaluation)
-template <class T>
-int glm_loglik_chunk(Ctx<T>* c, const T* th, int64_t nc, T* ll_out) {
-  const GlmModel<T>& m = c->glm;
-  const int64_t nrb = (m.n_obs + GB_M - 1) / GB_M;
-  const T* W = th;
-  if (m.on_w()) {
-    hipLaunchKernelGGL((k_hglm_coef<T>), dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, c->stream, th, m.tab(), m.at(GLM_W), (T*)nullptr, (int)m.P, m.G, c->D, nc,
-                       (const int*)nullptr);
-    W = m.at(GLM_W);
-  }
-  if (m.n_cat > 0) glm_launch_cut(c, (const int*)nullptr, nc, th);
-  const bool small = glm_small(c, nrb, nc);
-  return m.n_cls > 0 ? glm_launch_eta_cat(c, W, (const int*)nullptr, nc, small, (T*)nullptr, ll_out, (T*)nullptr)
-                     : glm_launch_eta(c, W, (int)m.P, (const int*)nullptr, nc, small, (T*)nullptr, ll_out, th);
-}
-
 template <class T>
 int glm_loo_check(Ctx<T>* c, const char* who, const void* theta, int64_t n_cols, const void* out) {
-  const std::string w(who);
-  if (c->target_kind != AHMC_TARGET_GLM || !c->glm.buf) return fail(c, AHMC_ERR_ARGUMENT, w + ": no GLM is bound (ahmc_set_target_glm)");
-  if (n_cols < 0 || (n_cols > 0 && (!theta || !out))) return fail(c, AHMC_ERR_ARGUMENT, w + ": theta or the output is NULL, or n_cols < 0");
-  if (n_cols > INT32_MAX) return fail(c, AHMC_ERR_UNSUPPORTED, w + ": n_cols beyond 2^31 - 1");
-  return AHMC_OK;
+  return glm_draws_check(c, who, true, "no GLM is bound (ahmc_set_target_glm)", !theta || !out, "theta or the output is NULL, or", n_cols);
 }
 
-// out (n_obs, n_cols): chunks of at most N columns, as glm_class_probs walks them
+// out (n_obs, n_cols): chunks of at most N columns, each through glm_forward on the model's own workspaces W, U, partial and the
+// cutpoint table (stream-ordered with every evaluation)
 template <class T>
 int glm_loglik(Ctx<T>* c, const void* theta, int64_t n_cols, void* out) {
   if (int rc = glm_loo_check(c, "glm_loglik", theta, n_cols, out)) return rc;
   if (n_cols == 0) return AHMC_OK;
-  const GlmModel<T>& m = c->glm;
-  const int64_t D = c->D, chunk = n_cols < c->N ? n_cols : c->N, n_obs = m.n_obs;
-  const size_t elems = (size_t)((D + n_obs) * chunk);
-  T* tmp = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(T) * elems) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(c, AHMC_ERR_RUNTIME, "glm_loglik: cannot allocate " + std::to_string((long long)(sizeof(T) * elems)) + " bytes");
-  }
-  T* const ll = tmp + D * chunk;
-  hipError_t e = hipSuccess;
-  int rc = AHMC_OK;
-  for (int64_t j0 = 0; j0 < n_cols && !rc && e == hipSuccess; j0 += chunk) {
-    const int64_t nc = n_cols - j0 < chunk ? n_cols - j0 : chunk;
-    e = hipMemcpyAsync(tmp, static_cast<const T*>(theta) + j0 * D, sizeof(T) * (size_t)(D * nc), hipMemcpyDefault, c->stream);
-    if (e != hipSuccess) break;
-    rc = glm_loglik_chunk(c, (const T*)tmp, nc, ll);
-    if (!rc) e = hipMemcpyAsync(static_cast<T*>(out) + j0 * n_obs, ll, sizeof(T) * (size_t)(n_obs * nc), hipMemcpyDefault, c->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  if (rc) return rc;
-  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("glm_loglik: ") + hipGetErrorString(e != hipSuccess ? e : es));
-  return AHMC_OK;
+  const int64_t n_obs = c->glm.n_obs;
+  return glm_on_draws(c, "glm_loglik", theta, n_cols, n_cols < c->N ? n_cols : c->N, n_obs, [&](GlmWalk& w, const T* th, T* ll, int64_t j0, int64_t nc) {
+    w.rc = glm_forward(c, th, (const int*)nullptr, nc, (T*)nullptr, ll, (T*)nullptr);
+    if (!w.rc) w.e = hipMemcpyAsync(static_cast<T*>(out) + j0 * n_obs, ll, sizeof(T) * (size_t)(n_obs * nc), hipMemcpyDefault, c->stream);
+  });
 }
 
 // the tail length M = ⌈min(0.2·S, 3·√S)⌉ (glm.py: psis_tail_length — the same double operations)
@@ -104,30 +65,25 @@ int glm_loo(Ctx<T>* c, const void* theta, int64_t n_cols, double* pw_out, double
   double* pw = reinterpret_cast<double*>(base + oPw);
   double* lw = lw_out ? reinterpret_cast<double*>(base + oLw) : nullptr;
   hipStream_t s = c->stream;
-  hipError_t e = hipSuccess;
-  int rc = AHMC_OK;
   // ---- stage A
   const int64_t nbo = (n_obs + LOO_TILE - 1) / LOO_TILE;
-  for (int64_t j0 = 0; j0 < S && !rc && e == hipSuccess; j0 += chunk) {
-    const int64_t nc = S - j0 < chunk ? S - j0 : chunk;
-    e = hipMemcpyAsync(th, static_cast<const T*>(theta) + j0 * D, sizeof(T) * (size_t)(D * nc), hipMemcpyDefault, s);
-    if (e != hipSuccess) break;
-    rc = glm_loglik_chunk(c, (const T*)th, nc, ll);
-    if (rc) break;
+  GlmWalk w = glm_walk_draws(c, theta, S, chunk, th, [&](GlmWalk& st, int64_t j0, int64_t nc) {
+    st.rc = glm_forward(c, (const T*)th, (const int*)nullptr, nc, (T*)nullptr, ll, (T*)nullptr);
+    if (st.rc) return;
     hipLaunchKernelGGL((k_loo_keys<T>), dim3((unsigned)(nbo * ((nc + LOO_TILE - 1) / LOO_TILE))), dim3(LOO_THREADS), 0, s, (const T*)ll, n_obs, nc, j0, S, ka, ia);
-    e = hipGetLastError();
-  }
-  if (!rc && e == hipSuccess) {
+    st.e = hipGetLastError();
+  });
+  if (w.ok()) {
     // ---- stage B: a float's key has its low 29 bits set by its sign alone, so the passes below bit 24 would move nothing
     dg_sort<uint64_t>(s, ka, kb, ia, ib, S, n_obs, tps, cnt, part, std::is_same<T, float>::value ? 24 : 0);
     // ---- stage C
     hipLaunchKernelGGL(k_loo_psis, dim3((unsigned)n_obs), dim3(LOO_THREADS), 0, s, (const uint64_t*)ka, (const uint32_t*)ia, S, (int)M, pw, lw);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(pw_out, pw, (size_t)n_obs * 32, hipMemcpyDefault, s);
-    if (e == hipSuccess && lw_out) e = hipMemcpyAsync(lw_out, lw, (size_t)Mx * 8, hipMemcpyDefault, s);
+    w.e = hipGetLastError();
+    if (w.e == hipSuccess) w.e = hipMemcpyAsync(pw_out, pw, (size_t)n_obs * 32, hipMemcpyDefault, s);
+    if (w.e == hipSuccess && lw_out) w.e = hipMemcpyAsync(lw_out, lw, (size_t)Mx * 8, hipMemcpyDefault, s);
   }
   const hipError_t es = hipStreamSynchronize(s);
-  if (rc) return rc;
-  if (e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("glm_loo: ") + hipGetErrorString(e != hipSuccess ? e : es));
+  if (w.rc) return w.rc;
+  if (w.e != hipSuccess || es != hipSuccess) return fail(c, AHMC_ERR_RUNTIME, std::string("glm_loo: ") + hipGetErrorString(w.e != hipSuccess ? w.e : es));
   return AHMC_OK;
 }
