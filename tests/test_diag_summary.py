@@ -503,5 +503,6 @@ def test_diag_misuse_is_refused_and_the_context_still_runs(hip):
     assert rc == capi.ERR_UNSUPPORTED and b"2^31" in hip.dll.ahmc_last_error(big._ctx)
     big.close()
     transition_ok()
-    # (a communicator of more than one rank is refused with AHMC_ERR_UNSUPPORTED too; that needs two processes and is not run here)
+    # (a communicator of more than one rank is refused with AHMC_ERR_UNSUPPORTED too: two processes on one GPU,
+    # tests/test_multirank_loopback.py::test_refusals_of_a_context_with_more_than_one_rank)
     e.close()
