@@ -1116,9 +1116,41 @@ __device__ __forceinline__ void fill_caches(Point<T, E>& z, const T (&minv)[E], 
 
 // vector load/store of one chain's slice: element d0+e of chain c lives at base[off + d0 + e].
 // Full, 16-byte aligned lanes use dwordx4/dwordx2 accesses (CH elements per access).
-template <class T, int E>
+// SB (k_nuts where a chain owns a wave, AHMC_TRANS_SCALAR): `base + off` is wave-uniform — formed in 64 bits on the scalar unit — and the
+// lane adds only its BYTE offset d0·sizeof(T), a 32-bit value: the accesses take the scalar-base form (saddr + voffset) with no 64-bit
+// per-lane address arithmetic.  d0·sizeof(T) is a multiple of the 16-byte piece (E is a multiple of CH), so the alignment test is the
+// scalar base's.  Same elements, same addresses, same predicate as the per-lane form.
+template <class T, int E, bool SB = false>
 __device__ __forceinline__ void load_vec(T (&v)[E], const T* __restrict__ base, int64_t off, int d0, int D, T pad) {
   constexpr int CH = (E * sizeof(T) >= 16) ? (int)(16 / sizeof(T)) : E;
+  if constexpr (SB) {
+    const T* sb = base + off;
+    if (CH > 1 && d0 + E <= D && (reinterpret_cast<uintptr_t>(sb) % (CH * sizeof(T)) == 0)) {
+      using V = T __attribute__((ext_vector_type(CH)));
+      // (the lane's byte offset is made opaque IN the arm that uses it, each arm its own: formed in front of the branch — or once per
+      // transition — the instruction selector sees a 64-bit register in the arm, not zext(32-bit), and adds it with a vector instruction)
+      unsigned bv = (unsigned)d0 * (unsigned)sizeof(T);
+      asm("; full lane" : "+v"(bv));
+      const T* ptr = reinterpret_cast<const T*>(reinterpret_cast<const char*>(sb) + bv);
+#pragma unroll
+      for (int e = 0; e < E; e += CH) {
+        V t = *reinterpret_cast<const V*>(ptr + e);
+#pragma unroll
+        for (int k = 0; k < CH; ++k) v[e + k] = t[k];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < E; ++e) {   // (every element is an arm of its own)
+        v[e] = pad;
+        if (d0 + e < D) {
+          unsigned be = (unsigned)d0 * (unsigned)sizeof(T);
+          asm("; ragged lane" : "+v"(be));
+          v[e] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(sb + e) + be);
+        }
+      }
+    }
+    return;
+  }
   const T* ptr = base + off + d0;
   if (CH > 1 && d0 + E <= D && (reinterpret_cast<uintptr_t>(ptr) % (CH * sizeof(T)) == 0)) {
     using V = T __attribute__((ext_vector_type(CH)));
@@ -1133,9 +1165,34 @@ __device__ __forceinline__ void load_vec(T (&v)[E], const T* __restrict__ base, 
     for (int e = 0; e < E; ++e) v[e] = (d0 + e < D) ? ptr[e] : pad;
   }
 }
-template <class T, int E>
+template <class T, int E, bool SB = false>
 __device__ __forceinline__ void store_vec(const T (&v)[E], T* __restrict__ base, int64_t off, int d0, int D) {
   constexpr int CH = (E * sizeof(T) >= 16) ? (int)(16 / sizeof(T)) : E;
+  if constexpr (SB) {
+    T* sb = base + off;
+    if (CH > 1 && d0 + E <= D && (reinterpret_cast<uintptr_t>(sb) % (CH * sizeof(T)) == 0)) {
+      using V = T __attribute__((ext_vector_type(CH)));
+      unsigned bv = (unsigned)d0 * (unsigned)sizeof(T);   // (as in load_vec)
+      asm("; full lane" : "+v"(bv));
+      T* ptr = reinterpret_cast<T*>(reinterpret_cast<char*>(sb) + bv);
+#pragma unroll
+      for (int e = 0; e < E; e += CH) {
+        V t;
+#pragma unroll
+        for (int k = 0; k < CH; ++k) t[k] = v[e + k];
+        *reinterpret_cast<V*>(ptr + e) = t;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        if (d0 + e < D) {
+          unsigned be = (unsigned)d0 * (unsigned)sizeof(T);
+          asm("; ragged lane" : "+v"(be));
+          *reinterpret_cast<T*>(reinterpret_cast<char*>(sb + e) + be) = v[e];
+        }
+    }
+    return;
+  }
   T* ptr = base + off + d0;
   if (CH > 1 && d0 + E <= D && (reinterpret_cast<uintptr_t>(ptr) % (CH * sizeof(T)) == 0)) {
     using V = T __attribute__((ext_vector_type(CH)));

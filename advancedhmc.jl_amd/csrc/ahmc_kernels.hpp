@@ -131,10 +131,10 @@ __device__ __forceinline__ Rng make_rng(const KP<T>& p, int64_t c) {
   return g;
 }
 
-template <class T, int E>
+template <class T, int E, bool SB = false>   // SB: c is wave-uniform (load_vec, ahmc_device.hpp)
 __device__ __forceinline__ void load_minv(const KP<T>& p, int64_t c, int d0, T (&minv)[E]) {
   if (p.minv) {
-    load_vec<T, E>(minv, p.minv, p.minv_per_chain ? c * p.D : 0, d0, p.D, T(1));
+    load_vec<T, E, SB>(minv, p.minv, p.minv_per_chain ? c * p.D : 0, d0, p.D, T(1));
   } else {
 #pragma unroll
     for (int e = 0; e < E; ++e) minv[e] = T(1);
@@ -183,20 +183,20 @@ __device__ __forceinline__ void draw_momentum(const KP<T>& p, const Rng& rng, ui
 }
 
 // the same refresh with the standard normals read from memory (written by k_normals)
-template <class T, int E>
+template <class T, int E, bool SB = false>
 __device__ __forceinline__ void momentum_from_normals(const KP<T>& p, const T* __restrict__ zsrc, int64_t c, int d0,
                                                       T (&r)[E]) {
   T z[E];
-  load_vec<T, E>(z, zsrc, c * p.D, d0, p.D, T(0));
+  load_vec<T, E, SB>(z, zsrc, c * p.D, d0, p.D, T(0));
   if (p.minv) {
     T sq[E];
-    load_vec<T, E>(sq, p.sqrt_minv, p.minv_per_chain ? c * p.D : 0, d0, p.D, T(1));
+    load_vec<T, E, SB>(sq, p.sqrt_minv, p.minv_per_chain ? c * p.D : 0, d0, p.D, T(1));
 #pragma unroll
     for (int e = 0; e < E; ++e) z[e] = z[e] / sq[e];  // r ./= sqrtM⁻¹
   }
   if (p.refresh_alpha != T(0)) {  // PartialMomentumRefreshment: α r + sqrt(1-α²) ξ, r = the stored momentum
     T ro[E];
-    load_vec<T, E>(ro, p.r(), c * p.D, d0, p.D, T(0));
+    load_vec<T, E, SB>(ro, p.r(), c * p.D, d0, p.D, T(0));
     const T s = sqrt(1 - p.refresh_alpha * p.refresh_alpha);
 #pragma unroll
     for (int e = 0; e < E; ++e) z[e] = p.refresh_alpha * ro[e] + s * z[e];
@@ -205,11 +205,11 @@ __device__ __forceinline__ void momentum_from_normals(const KP<T>& p, const T* _
   for (int e = 0; e < E; ++e) r[e] = (d0 + e < p.D) ? z[e] : T(0);
 }
 
-template <class T, int E>
+template <class T, int E, bool SB = false>
 __device__ __forceinline__ void store_point(const KP<T>& p, int64_t c, int d0, int lane, const Point<T, E>& z) {
-  store_vec<T, E>(z.th, p.th(), c * p.D, d0, p.D);
-  store_vec<T, E>(z.r, p.r(), c * p.D, d0, p.D);
-  store_vec<T, E>(z.g, p.g(), c * p.D, d0, p.D);
+  store_vec<T, E, SB>(z.th, p.th(), c * p.D, d0, p.D);
+  store_vec<T, E, SB>(z.r, p.r(), c * p.D, d0, p.D);
+  store_vec<T, E, SB>(z.g, p.g(), c * p.D, d0, p.D);
   if (lane == 0) {
     p.lp()[c] = z.lp;
     p.lk()[c] = z.lk;
@@ -231,20 +231,20 @@ __device__ __forceinline__ void accumulate_energy(const KP<T>& p, int64_t c, T H
   ea[p.N + c] = H;
 }
 
-template <class T, int E>
+template <class T, int E, bool SB = false>
 __device__ __forceinline__ void accumulate(const KP<T>& p, int64_t c, int d0, int lane, const T (&th)[E], int n_steps,
                                            int numerr, T H) {
   if (!p.accum) return;
   T s1[E], s2[E];
-  load_vec<T, E>(s1, p.acc_sum(), c * p.D, d0, p.D, T(0));
-  load_vec<T, E>(s2, p.acc_sumsq(), c * p.D, d0, p.D, T(0));
+  load_vec<T, E, SB>(s1, p.acc_sum(), c * p.D, d0, p.D, T(0));
+  load_vec<T, E, SB>(s2, p.acc_sumsq(), c * p.D, d0, p.D, T(0));
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     s1[e] += th[e];
     s2[e] += th[e] * th[e];
   }
-  store_vec<T, E>(s1, p.acc_sum(), c * p.D, d0, p.D);
-  store_vec<T, E>(s2, p.acc_sumsq(), c * p.D, d0, p.D);
+  store_vec<T, E, SB>(s1, p.acc_sum(), c * p.D, d0, p.D);
+  store_vec<T, E, SB>(s2, p.acc_sumsq(), c * p.D, d0, p.D);
   if (lane == 0) {
     p.acc_nsteps()[c] += n_steps;
     p.acc_ndiv()[c] += numerr;

@@ -93,7 +93,64 @@
 #define AHMC_LEAF_PAIR 0
 #endif
 
+// AHMC_TRANS_SCALAR 1 (round 11): the code that runs ONCE PER TRANSITION where one chain owns one wave (G = 64, the fast kernels — MODE 0, 1, 3, 4).
+//  * The chain index is wave-uniform there but was carried per lane, so every per-chain address was a 64-bit vector add.  It is taken into
+//    scalar registers once (v_readfirstlane) and made opaque once per transition as a SCALAR ("+s"): c·D, kt·D·N and the statistics' elements
+//    are formed in 64 bits on the scalar unit, the lane adds its 32-bit byte offset (load_vec / store_vec <…, SB>, ahmc_device.hpp), and the
+//    lane-0 statistics stores take a scalar address.
+//  * The argument fields that only the prologue and the epilogue need (the slabs' bases, N, the Philox key, the normals, the draws buffer,
+//    the redo flags, …) are invariant in the transition loop: the compiler loaded them at kernel entry, could not keep them in ≈ 100 SGPRs
+//    and parked them in VGPR lanes — one v_readlane per dword in every prologue and epilogue (scripts/loop_census.py).  They are read
+//    where they are used, through a pointer to the kernel-argument segment that the optimiser cannot see through (args_reread): a few
+//    scalar loads per transition on a port that carries ≈ 1 instruction per leapfrog, and nothing live across the tree.  KP<T> is the
+//    kernels' only argument, so it starts at offset 0 of the segment (the hidden arguments follow the explicit ones).
+// No floating-point expression is touched.  0: the parent's device code, digest for digest (A/B partner; profiles/r11_experiments.md).
+#ifndef AHMC_TRANS_SCALAR
+#define AHMC_TRANS_SCALAR 1
+#endif
+
 namespace ahmc {
+
+// The kernel's argument block read again HERE: see AHMC_TRANS_SCALAR above.  args_reread<ON> gives the pointer (valid in a __global__ function
+// whose first — only — argument is the P passed by value; null when OFF), args_at<ON>(p, q) the block an expression reads: *q, or `p` itself.
+// (Two steps, and no named reference to `p`: a `const P& pa = p;` in the kernel — even an unused one — changed the register allocation of
+// the instantiations it does nothing in.)
+template <bool ON, class P>
+__device__ __forceinline__ const P* args_reread() {
+  if constexpr (ON) {
+    auto k = __builtin_amdgcn_kernarg_segment_ptr();   // (constant address space: its loads are scalar loads)
+    asm volatile("" : "+s"(k));
+    return (const P*)k;
+  } else {
+    return nullptr;
+  }
+}
+template <bool ON, class P>
+__device__ __forceinline__ const P& args_at(const P& p, const P* q) {
+  if constexpr (ON) return *q;
+  else return p;
+}
+
+// The adaptor's argument block as the warm-up epilogue reads it (AHMC_ADAPT_REREAD below).  ON: the pointer comes from the re-read kernel
+// arguments — opaque already — and the block, which no kernel writes, is read as CONSTANT memory: scalar loads, and the array pointers it
+// holds arrive in scalar registers (through the generic pointer they were per-lane values, and every Welford access a 64-bit vector add).
+template <bool ON, class A, class P>
+__device__ __forceinline__ auto adapt_block_at(const A* ak, const P* args) {
+  if constexpr (ON) return (const __attribute__((address_space(4))) A*)args->adaptk;
+  else return ak;
+}
+// ON: a pointer to device memory, said to be one (global instructions take a scalar base, flat ones do not)
+template <bool ON, class Q>
+__device__ __forceinline__ Q* as_global(Q* q) {
+  if constexpr (ON) return (Q*)(__attribute__((address_space(1))) Q*)q;
+  else return q;
+}
+
+// a 64-bit value that is the same in every lane of the wave, taken into scalar registers
+__device__ __forceinline__ int64_t wave_scalar64(int64_t x) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 
 constexpr double LINW_LIMIT = 600.0;  // exp(600)·2^10 leaves is still far from the Float64 overflow; Float32 uses 60
 enum { SL_OTH_TH = 0, SL_OTH_R = 1, SL_OTH_G = 2, SL_TREE_A = 3, SL_Z0_R = 4, SL_Z0_G = 5, SL_START_R = 6 };
@@ -368,6 +425,8 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #define S_DH(lvl) sT[((2) * NLEV + (lvl)) * CPW + gi]
 #define S_NA(lvl) sI[((0) * NLEV + (lvl)) * CPW + gi]
 #define S_CK(lvl) sI[((1) * NLEV + (lvl)) * CPW + gi]
+  // one chain per wave: the chain index and the kernel's argument fields on the scalar side (AHMC_TRANS_SCALAR above)
+  constexpr bool TSC = AHMC_TRANS_SCALAR != 0 && G == 64 && !GENERAL;
   const int64_t wave_slot = (int64_t)blockIdx.x * nwaves + wib;
   Slots<T, E> sl;
   sl.lds = (AHMC_AS_LDS T*)lds_vec;
@@ -419,17 +478,20 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   const int64_t slot = (int64_t)chunk * CPW + gi;
   const int64_t c = slot < p.N ? (p.order ? (int64_t)p.order[slot] : slot) : p.N;
   int64_t cc = c < p.N ? c : 0;  // out-of-range groups shadow chain 0 and never write
+  if constexpr (TSC) cc = wave_scalar64(cc);
   // redo pass: only the chains flagged by the linear-domain pass, from the transition they bailed at
   const int kt0 = p.redo_only ? p.redo[cc] - 1 : 0;
   bool active = c < p.N && kt0 >= 0;
   if (!AHMC_ANY(active)) return;  // (redo pass: the common case)
   T minv[E];
-  load_minv<T, E>(p, cc, d0, minv);
+  load_minv<T, E, TSC>(p, cc, d0, minv);
   T th_cur[E];  // the chain's position, carried in registers from one transition to the next
-  load_vec<T, E>(th_cur, p.th(), cc * p.D, d0, p.D, T(0));
+  load_vec<T, E, TSC>(th_cur, p.th(), cc * p.D, d0, p.D, T(0));
   // in-kernel adaptation state (MODE 3): dual averaging of this chain, its nominal step size, the Welford count
   const AdaptK<T>* ak0 = ADAPT ? static_cast<const AdaptK<T>*>(p.adaptk) : nullptr;
   const AdaptK<T>* ak = ak0;
+  // the argument block as a transition's prologue / epilogue re-reads it (args_reread; declared HERE, not in the loop: see args_at)
+  const KP<T>*pa_ = nullptr, *pe_ = nullptr;
 
   // what adapt! does at batch-local transition kt2 (the same for every chain): push / update / reset of the variance
   // estimator and reset of the dual averaging — `adapt` in ahmc_api.hip, stan_adaptor.jl:137-159
@@ -482,22 +544,25 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
     // Make the per-lane indices opaque once per transition: otherwise every address and every
     // constant derived from them is loop-invariant w.r.t. this loop, gets hoisted out of it and
     // stays live through the whole tree (measured: +50 VGPRs, one wave per SIMD less).
-    asm volatile("" : "+v"(cc), "+v"(d0), "+v"(lane), "+v"(gi), "+v"(sl.lane_off));
+    if constexpr (TSC) asm volatile("" : "+s"(cc), "+v"(d0), "+v"(lane), "+v"(gi), "+v"(sl.lane_off));   // (the chain index stays scalar)
+    else asm volatile("" : "+v"(cc), "+v"(d0), "+v"(lane), "+v"(gi), "+v"(sl.lane_off));
     const bool on = AHMC_UNI(active && kt >= kt0);
     if (!AHMC_ANY(on)) continue;
+    if constexpr (TSC) pa_ = args_reread<TSC, KP<T>>();   // the argument fields of the prologue, read here
+#define PA args_at<TSC>(p, pa_)
     // ---- transition prologue (src/sampler.jl:54-57): jitter, fresh momentum, caches.  The standard
     // normals come from k_normals (same Philox stream): keeping the f64 Box–Muller out of this
     // kernel saves ~25 VGPRs at its register peak ----
     Point<T, E> cur;
     copy_vec(cur.th, th_cur);
-    Rng rng = make_rng(p, cc);
-    rng.iter = p.iteration + (uint32_t)kt;
+    Rng rng = make_rng(PA, cc);
+    rng.iter = PA.iteration + (uint32_t)kt;
     // nominal ϵ of this transition: the adaptor's current one (LDS) while adapting, else the context's (re-read per
     // transition: two VGPRs fewer across the tree loop than carrying it)
     T eps_nom_t;
-    if constexpr (ADAPT) eps_nom_t = A_EPSNOM; else eps_nom_t = p.eps_nom()[cc];
-    const T eps = chain_eps_from(p, rng, eps_nom_t);
-    momentum_from_normals<T, E>(p, p.znorm + (int64_t)kt * p.D * p.N, cc, d0, cur.r);
+    if constexpr (ADAPT) eps_nom_t = A_EPSNOM; else eps_nom_t = PA.eps_nom()[cc];
+    const T eps = chain_eps_from(PA, rng, eps_nom_t);
+    momentum_from_normals<T, E, TSC>(PA, PA.znorm + (int64_t)kt * PA.D * PA.N, cc, d0, cur.r);
     fill_caches<T, G, E, TK>(cur, minv, p.tp, lane, d0);
     // (θ0 of this transition — what the epilogue's re-integration and the redo pass start from — is already in p.th(): the
     // launch's start point at kt = 0, the previous transition's store_point after it.  Round 4: the redundant `if (on && kt > 0)`
@@ -1095,14 +1160,16 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
       // `ce` is the chain index made opaque to the optimiser: otherwise every array address of the
       // prologue is kept alive (2 VGPRs each) across the whole tree loop just to be reused here
       int64_t ce = cc;
-      asm volatile("" : "+v"(ce));
+      if constexpr (TSC) asm volatile("" : "+s"(ce)); else asm volatile("" : "+v"(ce));
+      if constexpr (TSC) pe_ = args_reread<TSC, KP<T>>();   // the argument fields of the epilogue, read here
+#define PE args_at<TSC>(p, pe_)
       Point<T, E> zc;
       int chk = 0;
       if constexpr (CKPT) chk = A_CHK;
       const int cp = chk >> 1;
       const bool from_ck = CKPT && AHMC_UNI(on && cp != 0);
       if constexpr (!CKPT) {
-        load_vec<T, E>(zc.th, p.th(), ce * p.D, d0, p.D, T(0));
+        load_vec<T, E, TSC>(zc.th, PE.th(), ce * PE.D, d0, PE.D, T(0));
         sl.load(DS(SL_Z0_R), zc.r);
         sl.load(DS(SL_Z0_G), zc.g);
       } else if constexpr (CPW == 1) {   // (wave-uniform: a scalar branch)
@@ -1112,14 +1179,14 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           sl.load_cold(CK0 + 1, xo, zc.r);
           sl.load_cold(CK0 + 2, xo, zc.g);
         } else {
-          load_vec<T, E>(zc.th, p.th(), ce * p.D, d0, p.D, T(0));
+          load_vec<T, E, TSC>(zc.th, PE.th(), ce * PE.D, d0, PE.D, T(0));
           sl.load(DS(SL_Z0_R), zc.r);
           sl.load(DS(SL_Z0_G), zc.g);
         }
       } else {   // chains that share a wave: both starts are read and the chain's own is selected — no exec-masked block (see the save)
         Point<T, E> zk;
         const unsigned xo = (unsigned)((chk & 1) * 3 * SLOT_ELEMS);
-        load_vec<T, E>(zc.th, p.th(), ce * p.D, d0, p.D, T(0));
+        load_vec<T, E, TSC>(zc.th, PE.th(), ce * PE.D, d0, PE.D, T(0));
         sl.load(DS(SL_Z0_R), zc.r);
         sl.load(DS(SL_Z0_G), zc.g);
         sl.load_cold(CK0 + 0, xo, zk.th);
@@ -1145,28 +1212,28 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
       }
       if (on && redo) {
         // stop here: the log-domain kernel resumes this chain at transition kt (its θ0 is in p.th)
-        if (lane == 0) p.redo[ce] = kt + 1;
+        if (lane == 0) PE.redo[ce] = kt + 1;
         if constexpr (ADAPT) save_adapt_state();  // as of before this transition: the redo pass resumes from it
         active = false;
       } else if (on) {
-        if (p.redo_only && lane == 0 && kt == p.n_trans - 1) p.redo[ce] = 0;
+        if (PE.redo_only && lane == 0 && kt == PE.n_trans - 1) PE.redo[ce] = 0;
         fill_caches<T, G, E, TK>(zc, minv, p.tp, lane, d0);  // ℓπ, -∇ℓπ, ℓκ of the candidate
-        store_point<T, E>(p, ce, d0, lane, zc);
+        store_point<T, E, TSC>(PE, ce, d0, lane, zc);
         const T H = -(zc.lp + zc.lk);
         if (lane == 0) {
-          p.eps_cur()[ce] = eps;
-          p.st_nsteps()[ce] = na_tree;
-          p.st_accept()[ce] = 1;
-          p.st_accrate()[ce] = sa_tree / (T)na_tree;
-          p.st_logdens()[ce] = zc.lp;
-          p.st_H()[ce] = H;
-          p.st_Herr()[ce] = H - H0;
-          p.st_maxHerr()[ce] = dh_tree;
-          p.st_depth()[ce] = depth;
-          p.st_numerr()[ce] = numerical ? 1 : 0;
+          PE.eps_cur()[ce] = eps;
+          PE.st_nsteps()[ce] = na_tree;
+          PE.st_accept()[ce] = 1;
+          PE.st_accrate()[ce] = sa_tree / (T)na_tree;
+          PE.st_logdens()[ce] = zc.lp;
+          PE.st_H()[ce] = H;
+          PE.st_Herr()[ce] = H - H0;
+          PE.st_maxHerr()[ce] = dh_tree;
+          PE.st_depth()[ce] = depth;
+          PE.st_numerr()[ce] = numerical ? 1 : 0;
         }
-        accumulate<T, E>(p, ce, d0, lane, zc.th, na_tree, numerical ? 1 : 0, H);
-        if (p.samples_out) store_vec<T, E>(zc.th, p.samples_out + (int64_t)kt * p.D * p.N, ce * p.D, d0, p.D);
+        accumulate<T, E, TSC>(PE, ce, d0, lane, zc.th, na_tree, numerical ? 1 : 0, H);
+        if (PE.samples_out) store_vec<T, E, TSC>(zc.th, PE.samples_out + (int64_t)kt * PE.D * PE.N, ce * PE.D, d0, PE.D);
         copy_vec(th_cur, zc.th);
         if constexpr (ADAPT) {
 #if AHMC_ADAPT_REREAD
@@ -1177,31 +1244,33 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           // which the build now keeps inside the loop by compiling these kernels without machine LICM, build.py PART_B_FLAGS.  Kept:
           // without it the allocator parks a spill under a narrowed exec mask in k_nuts<float,32,4,4,1>, which isa_check refuses.)
           const AdaptK<T>* ak = ak0;
-          asm volatile("" : "+s"(ak));
+          if constexpr (!TSC) asm volatile("" : "+s"(ak));
 #endif
+          // (one chain per wave: the block's address comes from the re-read arguments — opaque already — and it is read as constant memory)
+#define AK adapt_block_at<TSC>(ak, pe_)
           // adapt!(h, κ, adaptor, i, n_adapts, z, α) + update(h/κ, adaptor) (src/sampler.jl:72-90, :3-22) for this chain —
           // the same decisions and the same arithmetic as the host path (`adapt` in ahmc_api.hip, k_adapt_da / k_adapt_wv)
-          const int64_t i = ak->i0 + kt + 1;
+          const int64_t i = AK->i0 + kt + 1;
           bool do_push, do_update, wv_reset, dareset;
           schedule(kt, do_push, do_update, wv_reset, dareset);
-          if (ak->has_ss) {
+          if (AK->has_ss) {
             DAState<T> das{A_DAM, A_DAEPS, A_DAMU, A_DAXBAR, A_DAHBAR};
-            da_step(das, sa_tree / (T)na_tree, ak->delta, ak->gamma, ak->t0, ak->kappa, ak->da_tab);
+            da_step(das, sa_tree / (T)na_tree, AK->delta, AK->gamma, AK->t0, AK->kappa, AK->da_tab);
             if (dareset) da_reset(das);
-            if (i == ak->n_adapts) das.eps = exp(das.xbar);  // finalize! (stepsize.jl:55-62)
+            if (i == AK->n_adapts) das.eps = exp(das.xbar);  // finalize! (stepsize.jl:55-62)
             A_DAM = das.m; A_DAEPS = das.eps; A_DAMU = das.mu; A_DAXBAR = das.xbar; A_DAHBAR = das.Hbar;
             A_EPSNOM = das.eps;                              // update(κ, adaptor): nominal step size ← getϵ
           }
-          if (ak->has_mm && (do_push || wv_reset)) {
+          if (AK->has_mm && (do_push || wv_reset)) {
             int wv_n = A_WVN;
             if (do_push) wv_n += 1;
             const T n = (T)wv_n;
             T mu[E], M2[E], mug[E], Mg[E];
-            load_vec<T, E>(mu, ak->wv_mu, ce * p.D, d0, p.D, T(0));
-            load_vec<T, E>(M2, ak->wv_M, ce * p.D, d0, p.D, T(0));
-            if (ak->nutpie) {
-              load_vec<T, E>(mug, ak->wg_mu, ce * p.D, d0, p.D, T(0));
-              load_vec<T, E>(Mg, ak->wg_M, ce * p.D, d0, p.D, T(0));
+            load_vec<T, E, TSC>(mu, as_global<TSC>(AK->wv_mu), ce * PE.D, d0, PE.D, T(0));
+            load_vec<T, E, TSC>(M2, as_global<TSC>(AK->wv_M), ce * PE.D, d0, PE.D, T(0));
+            if (AK->nutpie) {
+              load_vec<T, E, TSC>(mug, as_global<TSC>(AK->wg_mu), ce * PE.D, d0, PE.D, T(0));
+              load_vec<T, E, TSC>(Mg, as_global<TSC>(AK->wg_M), ce * PE.D, d0, PE.D, T(0));
             }
             // (round 3: requesting these, the accumulators and the energy sums at the top of the epilogue — one round trip with
             // the start point instead of three behind the re-integration — was measured: the warm-up instantiation went from 89
@@ -1210,22 +1279,22 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #pragma unroll
               for (int e = 0; e < E; ++e) {
                 welford_push(mu[e], M2[e], zc.th[e], n);
-                if (ak->nutpie) welford_push(mug[e], Mg[e], zc.g[e], n);
+                if (AK->nutpie) welford_push(mug[e], Mg[e], zc.g[e], n);
               }
             }
-            if (do_update && wv_n >= ak->wv_nmin) {  // update!(ve): M⁻¹ ← estimate, √M⁻¹ recomputed (metric.jl:61-63)
+            if (do_update && wv_n >= AK->wv_nmin) {  // update!(ve): M⁻¹ ← estimate, √M⁻¹ recomputed (metric.jl:61-63)
               T var[E], sq[E];
 #pragma unroll
               for (int e = 0; e < E; ++e) {
                 T v2 = welford_estimate(M2[e], n);
-                if (ak->nutpie) v2 = sqrt(v2 / welford_estimate(Mg[e], n));
+                if (AK->nutpie) v2 = sqrt(v2 / welford_estimate(Mg[e], n));
                 var[e] = v2;
                 sq[e] = sqrt(v2);
-                if (d0 + e < p.D) minv[e] = v2;
+                if (d0 + e < PE.D) minv[e] = v2;
               }
-              store_vec<T, E>(var, ak->wv_var, ce * p.D, d0, p.D);
-              store_vec<T, E>(var, ak->minv, ce * p.D, d0, p.D);
-              store_vec<T, E>(sq, ak->sqrt_minv, ce * p.D, d0, p.D);
+              store_vec<T, E, TSC>(var, as_global<TSC>(AK->wv_var), ce * PE.D, d0, PE.D);
+              store_vec<T, E, TSC>(var, as_global<TSC>(AK->minv), ce * PE.D, d0, PE.D);
+              store_vec<T, E, TSC>(sq, as_global<TSC>(AK->sqrt_minv), ce * PE.D, d0, PE.D);
             }
             if (wv_reset) {
 #pragma unroll
@@ -1233,11 +1302,11 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
               wv_n = 0;
             }
             A_WVN = wv_n;
-            store_vec<T, E>(mu, ak->wv_mu, ce * p.D, d0, p.D);
-            store_vec<T, E>(M2, ak->wv_M, ce * p.D, d0, p.D);
-            if (ak->nutpie) {
-              store_vec<T, E>(mug, ak->wg_mu, ce * p.D, d0, p.D);
-              store_vec<T, E>(Mg, ak->wg_M, ce * p.D, d0, p.D);
+            store_vec<T, E, TSC>(mu, as_global<TSC>(AK->wv_mu), ce * PE.D, d0, PE.D);
+            store_vec<T, E, TSC>(M2, as_global<TSC>(AK->wv_M), ce * PE.D, d0, PE.D);
+            if (AK->nutpie) {
+              store_vec<T, E, TSC>(mug, as_global<TSC>(AK->wg_mu), ce * PE.D, d0, PE.D);
+              store_vec<T, E, TSC>(Mg, as_global<TSC>(AK->wg_M), ce * PE.D, d0, PE.D);
             }
           }
         }
@@ -1282,6 +1351,9 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #undef A_WVN
 #undef A_CHK
 #undef AHMC_UNI
+#undef PA
+#undef AK
+#undef PE
 }
 
 }  // namespace ahmc
