@@ -275,6 +275,23 @@ GLM_LOO_SIGNATURES = {
     "ahmc_glm_loo": (_i32, [_vp, _vp, _i64, C.POINTER(_f64), C.POINTER(_f64)]),
 }
 
+# include/ahmc_glm_predict.h: predictions of a GLM target at new data, their summaries over the draws and the held-out lpd (likewise)
+AHMC_GLM_PREDICT_VERSION = 1
+GLM_PRED_LINEAR, GLM_PRED_MEAN, GLM_PRED_VARIANCE, GLM_PRED_LOGLIK = 0, 1, 2, 3
+GLM_PRED_WHAT = {"linear": GLM_PRED_LINEAR, "mean": GLM_PRED_MEAN, "variance": GLM_PRED_VARIANCE, "loglik": GLM_PRED_LOGLIK}
+
+
+class GLMNewDataRecord(C.Structure):
+    """struct ahmc_glm_newdata"""
+    _fields_ = [("n_new", _i64), ("X", _vp), ("levels", C.POINTER(_i32)), ("offset", _vp), ("y", _vp)]
+
+
+GLM_PREDICT_SIGNATURES = {
+    "ahmc_glm_predict_version": (_i32, []),
+    "ahmc_glm_predict": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "ahmc_glm_predict_summary": (_i32, [_vp, _vp, _vp, _i64, C.POINTER(_f64)]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -396,6 +413,15 @@ class CLib:
             v = self.dll.ahmc_glm_loo_version()
             if v != AHMC_GLM_LOO_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm_loo version {v}, expected {AHMC_GLM_LOO_VERSION}")
+        # ahmc_glm_predict.h: likewise
+        gpred = [getattr(self.dll, name, None) for name in GLM_PREDICT_SIGNATURES]
+        self.has_glm_predict = all(fn is not None for fn in gpred)
+        if self.has_glm_predict:
+            for fn, (res, args) in zip(gpred, GLM_PREDICT_SIGNATURES.values()):
+                fn.restype, fn.argtypes = res, args
+            v = self.dll.ahmc_glm_predict_version()
+            if v != AHMC_GLM_PREDICT_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_predict version {v}, expected {AHMC_GLM_PREDICT_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

@@ -477,8 +477,65 @@ class GLMTarget:
             raise ArgumentError(capi.ERR_ARGUMENT, f"dispersion: family {self.family} has no sampled dispersion")
         return _glm.dispersion(theta)
 
+    def predict(self, theta, newdata, what="mean"):
+        """`what` ("linear" | "mean" | "variance" | "loglik") of the model at the rows of `newdata` (a GLMNewData) and draws θ (D, n) by
+        the numpy mirror (glm.predict): what Engine.glm_predict computes on the device"""
+        try:
+            if len(newdata.factors) != len(self.factors):
+                raise ValueError(f"DimensionMismatch: the new data have {len(newdata.factors)} factors, the model {len(self.factors)}")
+            facs = [(np.asarray(idx), f.n_levels) for idx, f in zip(newdata.factors, self.factors)]
+            family = "categorical_logit" if self.n_classes else "ordered_logit" if self.n_categories else self.family
+            return _glm.predict(family, newdata.X, theta, what, factors=facs, offset=newdata.offset, y=newdata.y, groups=self.groups,
+                                n_categories=self.n_classes or self.n_categories or None, scale=self.scale)
+        except (ValueError, TypeError) as e:
+            raise ArgumentError(capi.ERR_ARGUMENT, str(e))
+
     def __repr__(self):
         return f"GLMTarget(n_obs={self.n_obs}, D={self.D}, family={self.family})"
+
+
+def glm_summary_dict(summary, K=1, n_categories=0):
+    """the rows of a (2Q + 1, n_new) summary (ahmc_glm_predict_summary, glm.predict_summary) by name; K predictors, `n_categories` of an
+    ordinal or a categorical model (0: a family with one mean)"""
+    s = np.asarray(summary)
+    Q = K + (n_categories or 2)
+    if s.ndim != 2 or s.shape[0] != 2 * Q + 1:
+        raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: summary {s.shape}, expected ({2 * Q + 1}, n_new)")
+    eta = slice(0, 2 * K, 2) if K > 1 else 0
+    out = {"eta_mean": s[eta].copy(), "eta_var": s[slice(1, 2 * K, 2) if K > 1 else 1].copy()}
+    if n_categories:
+        out["probs"], out["probs_var"] = s[2 * K:2 * Q:2].copy(), s[2 * K + 1:2 * Q:2].copy()
+    else:
+        out["mean"], out["mean_var"], out["var_within"] = s[2].copy(), s[3].copy(), s[4].copy()
+    out["lpd"] = s[2 * Q].copy()
+    return out
+
+
+class GLMNewData:
+    """New rows of data for a bound GLMTarget (include/ahmc_glm_predict.h: ahmc_glm_newdata): X (n_new, P_x); `factors`: one integer
+    array of zero-based level indices (n_new,) per factor of the model, in its order (levels the model has not seen are refused);
+    `offset` (n_new,) — (n_new, C − 1) for a categorical model — or None: zeros; `y` (n_new,) or None: the held-out outcomes, which
+    "loglik" and the summary's lpd need."""
+
+    def __init__(self, X, factors=None, offset=None, y=None):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] < 1:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: X {X.shape}, expected (n_new, P_x)")
+        self.X, self.n_new = np.asfortranarray(X), X.shape[0]
+        self.factors = tuple(np.asarray(f.index if isinstance(f, Factor) else f) for f in (factors or ()))
+        for k, idx in enumerate(self.factors):
+            if idx.shape != (self.n_new,) or not np.issubdtype(idx.dtype, np.integer):
+                raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: factor {k + 1} of the new data: an integer level per row, ({self.n_new},); got "
+                                                       f"{idx.dtype} {idx.shape}")
+        self.offset = None if offset is None else np.asfortranarray(np.asarray(offset, dtype=np.float64))
+        if self.offset is not None and (self.offset.ndim not in (1, 2) or self.offset.shape[0] != self.n_new):
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: offset {self.offset.shape}, n_new {self.n_new}")
+        self.y = None if y is None else np.asarray(y, dtype=np.float64).ravel()
+        if self.y is not None and self.y.size != self.n_new:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"DimensionMismatch: y {self.y.shape}, n_new {self.n_new}")
+
+    def __repr__(self):
+        return f"GLMNewData(n_new={self.n_new}, factors={len(self.factors)}, offset={self.offset is not None}, y={self.y is not None})"
 
 
 @dataclass(frozen=True)
@@ -993,6 +1050,60 @@ class Engine:
         if log_weights:
             out["log_weights"] = lw
         return out
+
+    def _glm_newdata(self, who, nd):
+        """(record, keep-alive arrays) of a GLMNewData in the context's element type: struct ahmc_glm_newdata"""
+        self._need("has_glm_predict", "ahmc_glm_predict.h", who)
+        if not isinstance(nd, GLMNewData):
+            raise ArgumentError(capi.ERR_ARGUMENT, f"{who}: newdata must be a GLMNewData, not {type(nd).__name__}")
+        X = np.asfortranarray(nd.X, dtype=self.dtype)
+        lev = np.asfortranarray(np.column_stack(nd.factors), dtype=np.int32) if nd.factors else None
+        off = None if nd.offset is None else np.asfortranarray(nd.offset, dtype=self.dtype)
+        y = None if nd.y is None else np.ascontiguousarray(nd.y, dtype=self.dtype)
+        rec = capi.GLMNewDataRecord(nd.n_new, capi.as_ptr(X), None if lev is None else lev.ctypes.data_as(C.POINTER(C.c_int32)), capi.as_ptr(off), capi.as_ptr(y))
+        return rec, (X, lev, off, y)
+
+    def _glm_quantities(self):
+        """(K predictors, C categories or classes — 0 for the families with one mean) of the bound GLM"""
+        fam = self._glm_get("ahmc_get_target_glm", C.c_int32, 0, 3)
+        if fam == _glm.CATEGORICAL_LOGIT:
+            Ccl = self._glm_get("ahmc_glm_categorical_get_target", C.c_int32, 0, 2)
+            return Ccl - 1, Ccl
+        if fam == _glm.ORDERED_LOGIT:
+            return 1, self._glm_get("ahmc_glm_ordinal_get_target", C.c_int32, 0, 2)
+        return 1, 0
+
+    def glm_predict(self, newdata, draws=None, n_cols=None, what="mean"):
+        """`what` of the bound GLM at the rows of `newdata` (a GLMNewData) and draws θ (D, n), passed as to `glm_loglik`: "linear" η
+        (n_new, n) — (K, n_new, n) of a categorical model; "mean" μ (n_new, n), or the probabilities (C, n_new, n) of an ordinal or a
+        categorical model; "variance" (n_new, n); "loglik" ℓ(y_new, η) (n_new, n): ahmc_glm_predict.  The matrix is written whole:
+        for the S = N·K draws of a run use `glm_predict_summary`."""
+        rec, keep = self._glm_newdata("glm_predict", newdata)
+        if what not in capi.GLM_PRED_WHAT:
+            raise ArgumentError(capi.ERR_ARGUMENT, f"glm_predict: what = {what!r}; one of {sorted(capi.GLM_PRED_WHAT)}")
+        K, Ccl = self._glm_quantities()
+        planes = {"linear": K, "mean": Ccl or 1}.get(what, 1)
+        ptr, n = self._draws("glm_predict", draws, n_cols)
+        out = np.empty((planes, newdata.n_new, n), dtype=self.dtype, order="F")
+        self._call("ahmc_glm_predict", C.byref(rec), ptr, n, capi.GLM_PRED_WHAT[what], capi.as_ptr(out) if out.size else None)
+        del keep
+        return out if (what == "linear" and K > 1) or (what == "mean" and Ccl) else out[0]
+
+    def glm_predict_summary(self, newdata, draws=None, n_cols=None):
+        """per new observation, over draws θ (D, n) passed as to `glm_loglik` — the (D, N, K) buffer of `run(samples_out=ptr)` with
+        n_cols = N·K — the posterior mean and variance of every predicted quantity and the log predictive density at `newdata.y`, with
+        the draws reduced on the device (the (n_new, n) matrix is never written): ahmc_glm_predict_summary.  A dict of float64 arrays:
+        "eta_mean", "eta_var", "mean", "mean_var", "var_within" (the mean over the draws of Var[y | θ]) and "lpd", each (n_new,), for the
+        families with one mean; "eta_mean", "eta_var" ((K, n_new) of a categorical model), "probs", "probs_var" (C, n_new) and "lpd"
+        otherwise.  lpd is NaN without `newdata.y`; the variances are NaN for a single draw."""
+        rec, keep = self._glm_newdata("glm_predict_summary", newdata)
+        K, Ccl = self._glm_quantities()
+        Q = K + (Ccl or 2)
+        ptr, n = self._draws("glm_predict_summary", draws, n_cols)
+        s = np.full((2 * Q + 1, newdata.n_new), np.nan, order="F")
+        self._call("ahmc_glm_predict_summary", C.byref(rec), ptr, n, s.ctypes.data_as(C.POINTER(C.c_double)) if (n and s.size) else None)
+        del keep
+        return glm_summary_dict(s, K, Ccl)
 
     def hglm_coefficients(self, theta=None, n_cols=None):
         """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer

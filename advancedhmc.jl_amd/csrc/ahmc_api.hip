@@ -12,6 +12,7 @@
 #include "ahmc_glm_ordinal.h"
 #include "ahmc_glm_categorical.h"
 #include "ahmc_glm_loo.h"
+#include "ahmc_glm_predict.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -21,9 +22,11 @@
 #include "ahmc_rank_update.hpp"
 #include "ahmc_glm.hpp"
 #include "ahmc_glm_loo.hpp"
+#include "ahmc_glm_predict.hpp"
 #include "ahmc_lowrank_adapt.hpp"
 #include "ahmc_draw_sched.hpp"
 #include "ahmc_glm_spec.hpp"
+#include "ahmc_glm_predict_spec.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: the entry points are resolved at run time (ahmc_multi_host.hpp)
@@ -466,6 +469,7 @@ int launch_fill_caches_builtin(Ctx<T>* c) {
 #include "ahmc_multi_host.hpp"
 #include "ahmc_diag_host.hpp"
 #include "ahmc_glm_loo_host.hpp"
+#include "ahmc_glm_predict_host.hpp"
 
 void comm_destroy_raw(void* comm) {
   if (comm && rccl_api().CommDestroy) (void)rccl_api().CommDestroy(static_cast<ncclComm_t>(comm));
@@ -2369,6 +2373,17 @@ int32_t ahmc_glm_loglik(ahmc_ctx* ctx, const void* theta, int64_t n_cols, void* 
 
 int32_t ahmc_glm_loo(ahmc_ctx* ctx, const void* theta, int64_t n_cols, double* pointwise_out, double* log_weights_out) {
   FOR_CTX_MUT(ctx, { return glm_loo(c, theta, n_cols, pointwise_out, log_weights_out); });
+}
+
+// ---- include/ahmc_glm_predict.h: predictions at new data, their summaries over the draws and the held-out lpd -------------------------
+int32_t ahmc_glm_predict_version(void) { return AHMC_GLM_PREDICT_VERSION; }
+
+int32_t ahmc_glm_predict(ahmc_ctx* ctx, const ahmc_glm_newdata* newdata, const void* theta, int64_t n_cols, int32_t what, void* out) {
+  FOR_CTX_MUT(ctx, { return glm_predict_run(c, "glm_predict", newdata, theta, n_cols, what, out, false); });
+}
+
+int32_t ahmc_glm_predict_summary(ahmc_ctx* ctx, const ahmc_glm_newdata* newdata, const void* theta, int64_t n_cols, double* summary_out) {
+  FOR_CTX_MUT(ctx, { return glm_predict_run(c, "glm_predict_summary", newdata, theta, n_cols, 0, summary_out, true); });
 }
 
 }  // extern "C"

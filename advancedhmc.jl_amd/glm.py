@@ -1011,3 +1011,150 @@ def loo_compare(pw_a, pw_b):
     d = a - b
     with np.errstate(all="ignore"):
         return {"elpd_diff": float(d.sum()), "se_diff": float(np.sqrt(d.size * d.var(ddof=1))) if d.size > 1 else float("nan")}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# include/ahmc_glm_predict.h: predictions at new data, their summaries over the draws and the held-out lpd (csrc/ahmc_glm_predict.hpp)
+# ------------------------------------------------------------------------------------------------------------------------------
+__doc__ += """
+Predictions at new rows of data (predict, predict_summary): the model's full path at X_new — the effective coefficients W, the
+factors' levels gathered after the product, the offset last — and from η, per observation and draw, the Q quantities
+    families 0 – 4:  η, μ = E[y|θ], v = Var[y|θ]     Bernoulli σ(η), μ(1 − μ);  Poisson exp(η), μ;  Gaussian η, 1/scale;
+                                                       Gaussian with σ sampled η, exp(2s);  negative binomial exp(η), μ + μ²·exp(−s)
+    ordered logit:   η, p_0 … p_{C−1} (`ordinal_probs`)          categorical logit:  η_1 … η_K, p_0 … p_{C−1} (`categorical_probs`)
+and ℓ(y_new, η) where outcomes are given.  Summary over the S draws, per observation: mean and variance (divisor S − 1) of every
+quantity and lpd = logsumexp_s ℓ − log S.  Order of the sums: the draws in blocks of PRED_BLOCK = 64 — block b holds draws 64b … 64b + 63
+whatever the chunking; inside a block, ascending from +0: n_b, mean_b = (Σx)/n_b, M2_b = Σ(x − mean_b)², and for ℓ m_b = max,
+s_b = Σ exp(ℓ − m_b); the blocks in ascending order:  δ = mean_b − mean, n′ = n + n_b, mean = mean + δ·(n_b/n′),
+M2 = M2 + (M2_b + (((δ·δ)·n)·n_b)/n′)  and  m′ = max(m, m_b), s = s·exp(m − m′) + s_b·exp(m_b − m′)  from (−Inf, 0) — every
+operation rounded on its own.  A block with a non-finite value is (NaN, NaN), which the updates carry to the end.
+"""
+
+PRED_BLOCK = 64   # GLM_PRED_BLOCK of csrc/ahmc_glm_predict_spec.hpp: the draws of one block of the summary's sums
+PRED_WHAT = ("linear", "mean", "variance", "loglik")
+
+
+def predict(family, X_new, theta, what="mean", factors=None, offset=None, y=None, groups=(), n_categories=None, scale=1.0):
+    """The mirror of ahmc_glm_predict at new rows X_new (n_new, P_x) and draws θ (D, n), D as the bound model has it (coefficient rows,
+    log-scales of the groups, then s or κ).  `what`: "linear" η (n_new, n) — (K, n_new, n) of a categorical model; "mean" μ (n_new, n),
+    or the probabilities (C, n_new, n) of an ordinal or a categorical model; "variance" v (n_new, n), families 0 – 4 only; "loglik"
+    ℓ(y, η) (n_new, n), which needs `y`.  `factors`: the new rows' level indices with the bound model's level counts."""
+    if what not in PRED_WHAT:
+        raise ValueError(f"ArgumentError: what = {what!r}; one of {PRED_WHAT}")
+    if what == "loglik" and y is None:
+        raise ValueError("ArgumentError: what = 'loglik' needs y, the outcomes to evaluate")
+    ordinal = family in ORDINAL_FAMILIES or family == ORDERED_LOGIT
+    categorical = family in CATEGORICAL_FAMILIES or family == CATEGORICAL_LOGIT
+    n_new = np.asarray(X_new).shape[0]
+    y0 = np.zeros(n_new) if y is None else y
+    if ordinal or categorical:
+        if what == "variance":
+            raise ValueError("ArgumentError: what = 'variance' of a model whose outcome is a category; 'mean' gives the probabilities")
+        if n_categories is None:
+            raise ValueError("ArgumentError: the family needs n_categories")
+    if ordinal:
+        X, yi, th, C, grp, fac, PG = _ordinal_args(X_new, y0, theta, n_categories, groups, factors)
+        out = _ordinal_at(X, yi, th, PG, grp, fac, offset)
+        return {"linear": out[2], "loglik": out[7]}[what] if what != "mean" else ordinal_probs(out[2], out[3])
+    if categorical:
+        X, yi, th, K, Pb, grp, fac = _categorical_args(X_new, y0, theta, n_categories, groups, factors)
+        out = _categorical_at(X, yi, th, K, Pb, grp, fac, offset)
+        return {"linear": out[2], "mean": out[5], "loglik": out[3]}[what]
+    fam = family_code(family)
+    X, th, grp, fac = _hier_pointwise_args(fam, X_new, theta, groups, factors)
+    eta, ll = _link_at(fam, X, th, grp, fac, y0, offset, scale)[2:4]
+    if what in ("linear", "loglik"):
+        return eta if what == "linear" else ll
+    s = th[-1:] if fam in AUX_FAMILIES else None
+    with np.errstate(over="ignore", invalid="ignore"):
+        if fam == BERNOULLI_LOGIT:
+            e = np.exp(-np.abs(eta))
+            d = 1.0 + e
+            mu = np.where(eta >= 0, 1.0 / d, e / d)
+            v = mu * (1.0 - mu)
+        elif fam == POISSON_LOG:
+            mu = np.exp(eta)
+            v = mu
+        elif fam == GAUSSIAN_IDENTITY:
+            mu, v = eta, np.full_like(eta, 1.0 / scale)
+        elif fam == GAUSSIAN_IDENTITY_SIGMA:
+            mu, v = eta, np.broadcast_to(np.exp(2.0 * s), eta.shape).copy()
+        else:
+            mu = np.exp(eta)
+            v = (mu * mu) * np.exp(-s) + mu
+    return mu if what == "mean" else v
+
+
+def _pred_blocks(x, lse):
+    """the block partials of x (…, nc), nc draws that begin at a block's first: (…, nblk, 2) — (mean_b, M2_b), or (m_b, s_b) with `lse`"""
+    nc = x.shape[-1]
+    out = np.empty(x.shape[:-1] + ((nc + PRED_BLOCK - 1) // PRED_BLOCK, 2))
+    zero = np.zeros(x.shape[:-1] + (1,))
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for b in range(out.shape[-2]):
+            xb = x[..., b * PRED_BLOCK:(b + 1) * PRED_BLOCK].astype(np.float64)
+            bad = ~np.isfinite(xb).all(axis=-1)
+            if lse:
+                m = np.maximum.accumulate(xb, axis=-1)[..., -1]
+                first, second = m, np.add.accumulate(np.concatenate([zero, np.exp(xb - m[..., None])], axis=-1), axis=-1)[..., -1]
+            else:
+                first = np.add.accumulate(np.concatenate([zero, xb], axis=-1), axis=-1)[..., -1] / float(xb.shape[-1])
+                d = xb - first[..., None]
+                second = np.add.accumulate(np.concatenate([zero, d * d], axis=-1), axis=-1)[..., -1]
+            out[..., b, 0] = np.where(bad, np.nan, first)
+            out[..., b, 1] = np.where(bad, np.nan, second)
+    return out
+
+
+def _pred_fold(state, part, b0, S, lse):
+    """the running state (…, 2) after the block partials `part` (…, nblk, 2) of blocks b0, b0 + 1, … of S draws"""
+    a, c = state[..., 0].copy(), state[..., 1].copy()
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for b in range(part.shape[-2]):
+            pa, pc = part[..., b, 0], part[..., b, 1]
+            if lse:
+                mn = np.where(pa > a, pa, a)
+                c = c * np.exp(a - mn) + pc * np.exp(pa - mn)
+                a = mn
+            else:
+                n = float(PRED_BLOCK * (b0 + b))
+                nb = float(min(PRED_BLOCK, S - PRED_BLOCK * (b0 + b)))
+                npr = n + nb
+                d = pa - a
+                a = a + d * (nb / npr)
+                c = c + (pc + (((d * d) * n) * nb) / npr)
+    return np.stack([a, c], axis=-1)
+
+
+def predict_summary(values, loglik=None, chunk=None):
+    """(2Q + 1, n_new) float64 from values (Q, n_new, S) — the quantities of every observation at S draws, in the header's order — and
+    ℓ (n_new, S) or None: rows 2q, 2q + 1 the mean and the variance (divisor S − 1; NaN at S = 1) of quantity q, the last row
+    lpd = logsumexp_s ℓ − log S (NaN without ℓ).  The mirror of ahmc_glm_predict_summary: this function DEFINES the order of its sums
+    (the module docstring).  `chunk`: the draws are taken in pieces of this many (a multiple of PRED_BLOCK), as the device takes them; the
+    result does not depend on it."""
+    v = np.asarray(values)
+    if v.ndim != 3:
+        raise ValueError(f"DimensionMismatch: values {v.shape}, expected (Q, n_new, S)")
+    Q, n_new, S = v.shape
+    ll = None if loglik is None else np.asarray(loglik)
+    if ll is not None and ll.shape != (n_new, S):
+        raise ValueError(f"DimensionMismatch: loglik {ll.shape}, expected {(n_new, S)}")
+    chunk = (S + PRED_BLOCK - 1) // PRED_BLOCK * PRED_BLOCK if chunk is None else int(chunk)
+    if chunk < PRED_BLOCK or chunk % PRED_BLOCK:
+        raise ValueError(f"ArgumentError: chunk = {chunk} is no multiple of {PRED_BLOCK}")
+    out = np.full((2 * Q + 1, n_new), np.nan)
+    if S == 0:
+        return out
+    st = np.zeros((Q, n_new, 2))
+    sl = np.stack([np.full(n_new, -np.inf), np.zeros(n_new)], axis=-1)
+    for j0 in range(0, S, chunk):
+        st = _pred_fold(st, _pred_blocks(v[..., j0:j0 + chunk], False), j0 // PRED_BLOCK, S, False)
+        if ll is not None:
+            sl = _pred_fold(sl, _pred_blocks(ll[..., j0:j0 + chunk], True), j0 // PRED_BLOCK, S, True)
+    out[0:2 * Q:2] = st[..., 0]
+    if S > 1:
+        out[1:2 * Q:2] = st[..., 1] / float(S - 1)
+    if ll is not None:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[2 * Q] = (sl[:, 0] + np.log(sl[:, 1])) - np.log(float(S))
+    return out

@@ -522,5 +522,6 @@ include("AdvancedHMCMI355XGLMFactor.jl")  # set_target!(z, ::FactorGLMTarget), g
 include("AdvancedHMCMI355XGLMOrdinal.jl")  # set_target!(z, ::OrdinalGLMTarget), glm_cutpoints: include/ahmc_glm_ordinal.h
 include("AdvancedHMCMI355XGLMCategorical.jl")  # set_target!(z, ::CategoricalGLMTarget), glm_class_probs: include/ahmc_glm_categorical.h
 include("AdvancedHMCMI355XGLMLoo.jl")  # glm_loglik, glm_loo: include/ahmc_glm_loo.h
+include("AdvancedHMCMI355XGLMPredict.jl")  # glm_predict, glm_predict_summary: include/ahmc_glm_predict.h
 
 end # module
