@@ -292,6 +292,15 @@ GLM_PREDICT_SIGNATURES = {
     "ahmc_glm_predict_summary": (_i32, [_vp, _vp, _vp, _i64, C.POINTER(_f64)]),
 }
 
+# include/ahmc_glm_yrep.h: posterior-predictive draws y_rep of a GLM target and their per-observation summaries (likewise)
+AHMC_GLM_YREP_VERSION = 1
+GLM_YREP_SIGNATURES = {
+    "ahmc_glm_yrep_version": (_i32, []),
+    "ahmc_glm_yrep_at": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _pi32, _pi32, _u64, _vp]),
+    "ahmc_glm_yrep": (_i32, [_vp, _vp, _vp, _i64, _u64, _vp]),
+    "ahmc_glm_yrep_summary": (_i32, [_vp, _vp, _vp, _i64, _u64, C.POINTER(_f64)]),
+}
+
 
 class CLib:
     """One loaded implementation of the ABI."""
@@ -422,6 +431,15 @@ class CLib:
             v = self.dll.ahmc_glm_predict_version()
             if v != AHMC_GLM_PREDICT_VERSION:
                 raise ImportError(f"{self.path}: ahmc_glm_predict version {v}, expected {AHMC_GLM_PREDICT_VERSION}")
+        # ahmc_glm_yrep.h: likewise
+        gyrep = [getattr(self.dll, name, None) for name in GLM_YREP_SIGNATURES]
+        self.has_glm_yrep = all(fn is not None for fn in gyrep)
+        if self.has_glm_yrep:
+            for fn, (res, args) in zip(gyrep, GLM_YREP_SIGNATURES.values()):
+                fn.restype, fn.argtypes = res, args
+            v = self.dll.ahmc_glm_yrep_version()
+            if v != AHMC_GLM_YREP_VERSION:
+                raise ImportError(f"{self.path}: ahmc_glm_yrep version {v}, expected {AHMC_GLM_YREP_VERSION}")
 
     def check(self, code: int, ctx=None):
         if code == OK:

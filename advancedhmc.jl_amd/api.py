@@ -494,6 +494,11 @@ class GLMTarget:
         return f"GLMTarget(n_obs={self.n_obs}, D={self.D}, family={self.family})"
 
 
+def glm_yrep_at(engine, family, q, aux=None, row=None, col=None, seed=0, n_categories=0):
+    """`engine.glm_yrep_at(...)`: the device's outcome sampler on the caller's planes (include/ahmc_glm_yrep.h)"""
+    return engine.glm_yrep_at(family, q, aux=aux, row=row, col=col, seed=seed, n_categories=n_categories)
+
+
 def glm_summary_dict(summary, K=1, n_categories=0):
     """the rows of a (2Q + 1, n_new) summary (ahmc_glm_predict_summary, glm.predict_summary) by name; K predictors, `n_categories` of an
     ordinal or a categorical model (0: a family with one mean)"""
@@ -916,8 +921,10 @@ class Engine:
                                                  n_params=-1 if p is None else p.size)
             self._call("ahmc_set_target_plugin", so.encode(), capi.as_ptr(p), 0 if p is None else p.size)
             return
+        self._glm_target = None
         if isinstance(target, GLMTarget):
             self._set_glm(target)
+            self._glm_target = target   # (glm_yrep(newdata=None): the target's own rows)
             return
         if isinstance(target, KernelTarget):
             h = target.handle
@@ -1104,6 +1111,55 @@ class Engine:
         self._call("ahmc_glm_predict_summary", C.byref(rec), ptr, n, s.ctypes.data_as(C.POINTER(C.c_double)) if (n and s.size) else None)
         del keep
         return glm_summary_dict(s, K, Ccl)
+
+    def _glm_yrep_newdata(self, who, newdata):
+        self._need("has_glm_yrep", "ahmc_glm_yrep.h", who)
+        if newdata is None:
+            t = getattr(self, "_glm_target", None)
+            if t is None:
+                raise ArgumentError(capi.ERR_ARGUMENT, f"{who}: newdata=None means the rows of the bound GLMTarget, and none was bound through set_target")
+            newdata = GLMNewData(t.X, factors=[f.index for f in t.factors], offset=t.offset, y=t.y)
+        return newdata, self._glm_newdata(who, newdata)
+
+    def glm_yrep(self, newdata=None, draws=None, n_cols=None, seed=0):
+        """posterior-predictive draws y_rep (n_new, n) of the bound GLM: one outcome y ~ p(y | θ_j) per row of `newdata` (a GLMNewData;
+        None: the bound target's own rows) and draw θ_j of `draws` (D, n), passed as to `glm_loglik`: ahmc_glm_yrep.  Reproducible:
+        element (i, j) depends on its row, its draw, (i, j) and `seed` alone (glm.yrep_at is the sampler's definition).  The matrix is
+        written whole: for the S = N·K draws of a run use `glm_yrep_summary`."""
+        nd, (rec, keep) = self._glm_yrep_newdata("glm_yrep", newdata)
+        ptr, n = self._draws("glm_yrep", draws, n_cols)
+        out = np.empty((nd.n_new, n), dtype=self.dtype, order="F")
+        self._call("ahmc_glm_yrep", C.byref(rec), ptr, n, int(seed) & (2 ** 64 - 1), capi.as_ptr(out) if out.size else None)
+        del keep
+        return out
+
+    def glm_yrep_summary(self, newdata=None, draws=None, n_cols=None, seed=0):
+        """per row of `newdata` (None: the bound target's own rows), over draws θ (D, n) passed as to `glm_loglik` — the (D, N, K) buffer
+        of `run(samples_out=ptr)` with n_cols = N·K — {"mean", "var", "p_less", "p_equal"}, each (n_new,) float64: the mean and the
+        variance of the y_rep that `glm_yrep` gives for the same seed, and the shares of them below and at `newdata.y` (NaN without
+        it), with the draws reduced on the device: ahmc_glm_yrep_summary"""
+        nd, (rec, keep) = self._glm_yrep_newdata("glm_yrep_summary", newdata)
+        ptr, n = self._draws("glm_yrep_summary", draws, n_cols)
+        s = np.full((4, nd.n_new), np.nan, order="F")
+        self._call("ahmc_glm_yrep_summary", C.byref(rec), ptr, n, int(seed) & (2 ** 64 - 1), s.ctypes.data_as(C.POINTER(C.c_double)) if (n and s.size) else None)
+        del keep
+        return {k: s[i].copy() for i, k in enumerate(("mean", "var", "p_less", "p_equal"))}
+
+    def glm_yrep_at(self, family, q, aux=None, row=None, col=None, seed=0, n_categories=0):
+        """y (n,) in the context's element type: one outcome per element from the family's sampler given its planes q (planes, n), the
+        log-dispersion `aux` (n,) of a negative binomial and the counters `row`, `col` (n,) (None: 0 … n − 1 and 0): ahmc_glm_yrep_at,
+        the device's form of glm.yrep_at.  No GLM need be bound."""
+        self._need("has_glm_yrep", "ahmc_glm_yrep.h", "glm_yrep_at")
+        fam = _glm._yrep_family(family)
+        qa = np.asfortranarray(np.atleast_2d(np.asarray(q)), dtype=self.dtype)
+        n = qa.shape[1]
+        vec = lambda a, dt: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a), (n,)), dtype=dt)  # noqa: E731
+        au, ro, co = vec(aux, self.dtype), vec(row, np.int32), vec(col, np.int32)
+        y = np.empty(n, dtype=self.dtype)
+        pi = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        self._call("ahmc_glm_yrep_at", int(fam), int(n_categories or 0), n, capi.as_ptr(qa) if n else None, capi.as_ptr(au), pi(ro), pi(co), int(seed) & (2 ** 64 - 1),
+                   capi.as_ptr(y) if n else None)
+        return y
 
     def hglm_coefficients(self, theta=None, n_cols=None):
         """(β (P, n_cols), τ (G, n_cols)) of draws θ (D, n_cols) — an array (default: the context's current θ), or a device pointer

@@ -74,7 +74,7 @@ def _sources_digest() -> str:
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
     for hdr in ("ahmc_hip.h", "ahmc_diag.h", "ahmc_rank_update.h", "ahmc_lowrank_adapt.h", "ahmc_glm.h", "ahmc_glm_hier.h", "ahmc_glm_aux.h", "ahmc_glm_factor.h",
-                "ahmc_glm_ordinal.h", "ahmc_glm_categorical.h", "ahmc_glm_loo.h", "ahmc_glm_predict.h"):
+                "ahmc_glm_ordinal.h", "ahmc_glm_categorical.h", "ahmc_glm_loo.h", "ahmc_glm_predict.h", "ahmc_glm_yrep.h"):
         h.update(open(os.path.join(INCLUDE, hdr), "rb").read())
     h.update(" ".join(FLAGS + PART_B_FLAGS).encode())
     return h.hexdigest()

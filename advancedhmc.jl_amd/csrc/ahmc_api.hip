@@ -13,6 +13,7 @@
 #include "ahmc_glm_categorical.h"
 #include "ahmc_glm_loo.h"
 #include "ahmc_glm_predict.h"
+#include "ahmc_glm_yrep.h"
 #include "ahmc_lowrank_adapt.h"
 #include "ahmc_inst.hpp"
 #include "ahmc_dense.hpp"
@@ -23,6 +24,7 @@
 #include "ahmc_glm.hpp"
 #include "ahmc_glm_loo.hpp"
 #include "ahmc_glm_predict.hpp"
+#include "ahmc_glm_yrep.hpp"
 #include "ahmc_lowrank_adapt.hpp"
 #include "ahmc_draw_sched.hpp"
 #include "ahmc_glm_spec.hpp"
@@ -469,6 +471,7 @@ int launch_fill_caches_builtin(Ctx<T>* c) {
 #include "ahmc_multi_host.hpp"
 #include "ahmc_diag_host.hpp"
 #include "ahmc_glm_loo_host.hpp"
+#include "ahmc_glm_yrep_host.hpp"
 #include "ahmc_glm_predict_host.hpp"
 
 void comm_destroy_raw(void* comm) {
@@ -2384,6 +2387,24 @@ int32_t ahmc_glm_predict(ahmc_ctx* ctx, const ahmc_glm_newdata* newdata, const v
 
 int32_t ahmc_glm_predict_summary(ahmc_ctx* ctx, const ahmc_glm_newdata* newdata, const void* theta, int64_t n_cols, double* summary_out) {
   FOR_CTX_MUT(ctx, { return glm_predict_run(c, "glm_predict_summary", newdata, theta, n_cols, 0, summary_out, true); });
+}
+
+// ---- include/ahmc_glm_yrep.h: posterior-predictive draws of the outcome and their per-observation summaries -----------------------------
+int32_t ahmc_glm_yrep_version(void) { return AHMC_GLM_YREP_VERSION; }
+
+int32_t ahmc_glm_yrep_at(ahmc_ctx* ctx, int32_t family, int32_t n_categories, int64_t n, const void* q, const void* aux, const int32_t* row, const int32_t* col,
+                         uint64_t seed, void* y_out) {
+  FOR_CTX_MUT(ctx, { return glm_yrep_at(c, family, n_categories, n, q, aux, row, col, seed, y_out); });
+}
+
+int32_t ahmc_glm_yrep(ahmc_ctx* ctx, const ahmc_glm_newdata* newdata, const void* theta, int64_t n_cols, uint64_t seed, void* out) {
+  const GlmYrepCall yr{seed, false};
+  FOR_CTX_MUT(ctx, { return glm_predict_run(c, "glm_yrep", newdata, theta, n_cols, AHMC_GLM_PRED_MEAN, out, false, &yr); });
+}
+
+int32_t ahmc_glm_yrep_summary(ahmc_ctx* ctx, const ahmc_glm_newdata* newdata, const void* theta, int64_t n_cols, uint64_t seed, double* summary_out) {
+  const GlmYrepCall yr{seed, true};
+  FOR_CTX_MUT(ctx, { return glm_predict_run(c, "glm_yrep_summary", newdata, theta, n_cols, AHMC_GLM_PRED_MEAN, summary_out, false, &yr); });
 }
 
 }  // extern "C"

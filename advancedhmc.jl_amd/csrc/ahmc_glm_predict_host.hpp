@@ -2,8 +2,10 @@
 // ahmc_glm_predict_spec.hpp).  One function serves both calls: check, stage and check the new data, lay out and allocate the working
 // set, then walk the draws in chunks (glm_walk_draws): the chunk's effective coefficients and cutpoint table on the working set's own
 // arrays (the bound model's are sized by N and belong to the evaluations), k_glm_pred, and either the copy of the chunk's planes to the
-// caller or k_glm_pred_fold.  Of the bound model's slab only the tables of the groups and the factors are read.  Included by
-// ahmc_api.hip after ahmc_glm_host.hpp.
+// caller or k_glm_pred_fold.  Of the bound model's slab only the tables of the groups and the factors are read.  With a GlmYrepCall
+// (ahmc_glm_yrep_host.hpp) the same walk serves include/ahmc_glm_yrep.h: the chunk's planes are those the family's sampler reads, they
+// stay in the working set, k_glm_yrep draws from them, and the chunk's y_rep is copied to the caller or reduced per observation.
+// Included by ahmc_api.hip after ahmc_glm_host.hpp and ahmc_glm_yrep_host.hpp.
 #pragma once
 
 static_assert(GLM_PRED_BLOCK == GLM_PRED_BN && GLM_PRED_BN == GB_N, "a block of the summary is the tile's 64 draws");
@@ -18,13 +20,16 @@ inline int64_t glm_predict_env(const char* name) {
 }
 
 template <class T>
-int glm_predict_run(Ctx<T>* c, const char* who, const ahmc_glm_newdata* nd, const void* theta, int64_t n_cols, int what, void* out, bool summary) {
+int glm_predict_run(Ctx<T>* c, const char* who, const ahmc_glm_newdata* nd, const void* theta, int64_t n_cols, int what, void* out, bool summary,
+                    const GlmYrepCall* yr = nullptr) {
   const GlmModel<T>& m = c->glm;
   const bool bound = c->target_kind == AHMC_TARGET_GLM && m.buf;
   GlmPredPlan p;
   std::string err;
   if (int rc = glm_predict_spec_check(who, bound, m, nd, theta, n_cols, out, what, summary, p, err)) return fail(c, rc, err);
   if (p.n_new == 0) return AHMC_OK;
+  const bool ysum = yr && yr->summary;
+  if (yr && (m.family == AHMC_GLM_GAUSSIAN_IDENTITY || m.family == AHMC_GLM_GAUSSIAN_IDENTITY_SIGMA) && m.n_cat == 0 && m.n_cls == 0) p.q1 = p.Q;  // (μ, v)
   const int64_t n = p.n_new, K = m.K(), Px = m.Px, D = c->D, P = m.P, S = n_cols;
   // ---- the new data on the host, checked
   std::vector<T> hX((size_t)(n * Px)), hoff(p.has_offset ? (size_t)(n * K) : 0), hy(p.has_y ? (size_t)n : 0);
@@ -35,8 +40,8 @@ int glm_predict_run(Ctx<T>* c, const char* who, const ahmc_glm_newdata* nd, cons
   if (S == 0) return AHMC_OK;
   // ---- the chunk and the working set: one allocation
   const int64_t nq = p.planes(), Q = p.Q, Cm1 = m.n_cat > 0 ? m.n_cat - 1 : 0, nrb = (n + GB_M - 1) / GB_M;
-  const int64_t col_elems = D + (m.on_w() ? P : 0) + 3 * Cm1 + (m.n_cls > 0 ? K * n : 0) + (summary ? 0 : nq * n);
-  const double col_bytes = (double)sizeof(T) * (double)col_elems + (summary ? (double)(nq * n) * 16.0 / 64.0 : 0.0);
+  const int64_t col_elems = D + (m.on_w() ? P : 0) + 3 * Cm1 + (m.n_cls > 0 ? K * n : 0) + (summary ? 0 : nq * n) + (yr ? n : 0);
+  const double col_bytes = (double)sizeof(T) * (double)col_elems + (summary ? (double)(nq * n) * 16.0 / 64.0 : 0.0) + (ysum ? (double)(n * sizeof(GlmYrepPart)) / 64.0 : 0.0);
   const auto layout = [&](int64_t chunk, size_t* o) {
     size_t off = 0;
     const auto take = [&off](size_t bytes) {
@@ -56,9 +61,13 @@ int glm_predict_run(Ctx<T>* c, const char* who, const ahmc_glm_newdata* nd, cons
     o[9] = take(summary ? (size_t)(nq * n * (chunk / 64)) * 16 : 0);        // the block partials
     o[10] = take(summary ? (size_t)(nq * n) * 16 : 0);                      // the running state
     o[11] = take(summary ? (size_t)((2 * Q + 1) * n) * 8 : 0);              // the summary
+    o[12] = take(yr ? sizeof(T) * (size_t)(n * chunk) : 0);                 // y_rep of the chunk
+    o[13] = take(ysum ? (size_t)(n * (chunk / 64)) * sizeof(GlmYrepPart) : 0);  // its block partials
+    o[14] = take(ysum ? (size_t)n * sizeof(GlmYrepPart) : 0);               // the running state of y_rep's summary
+    o[15] = take(ysum ? (size_t)(4 * n) * 8 : 0);                           // y_rep's summary
     return off;
   };
-  size_t o[12];
+  size_t o[16];
   const int64_t env_budget = glm_predict_env("AHMC_GLM_PREDICT_BUDGET"), env_chunk = glm_predict_env("AHMC_GLM_PREDICT_CHUNK");
   const double budget = env_budget >= 0 ? (double)env_budget : 256.0 * 1024 * 1024;
   int64_t chunk = 64;
@@ -74,7 +83,8 @@ int glm_predict_run(Ctx<T>* c, const char* who, const ahmc_glm_newdata* nd, cons
   const size_t total = layout(chunk, o);
   const std::string parts = std::string(" bytes for the new data, one chunk of ") + std::to_string((long long)chunk) + " draws (θ" + (m.on_w() ? ", W" : "") +
                             (Cm1 ? ", the cutpoint table" : "") + (m.n_cls > 0 ? ", the classes' predictors" : "") +
-                            (summary ? "), the block partials and the running state" : ") and its planes of the matrix");
+                            (summary ? "), the block partials and the running state" : ") and its planes of the matrix") +
+                            (ysum ? ", y_rep of the chunk, its block partials and running state" : yr ? " and y_rep of the chunk" : "");
   if (env_budget >= 0 && (double)total > budget)
     return fail(c, AHMC_ERR_RUNTIME, std::string(who) + ": cannot allocate " + std::to_string((long long)total) + parts + " within AHMC_GLM_PREDICT_BUDGET = " +
                                          std::to_string((long long)env_budget));
@@ -157,10 +167,35 @@ int glm_predict_run(Ctx<T>* c, const char* who, const ahmc_glm_newdata* nd, cons
         hipLaunchKernelGGL(k_glm_pred_fold, dim3((unsigned)((nq * n + 255) / 256)), dim3(256), 0, s, (const double2*)part, state, sum, (int)n, (int)Q, (int)nq, nblk,
                            chunk / 64, j0 / 64, S, j0 == 0 ? 1 : 0, j0 + nc == S ? 1 : 0);
         st.e = hipGetLastError();
+      } else if (yr) {
+        GlmYrepArgs<T> ya{};
+        ya.q = at(8);
+        ya.aux = a.aux;
+        ya.y = at(12);
+        ya.n_rows = n;
+        ya.n_cols = nc;
+        ya.aux_ld = D;
+        ya.col0 = j0;
+        ya.planes = (int)nq;
+        ya.C = m.n_cat > 0 ? m.n_cat : m.n_cls;
+        ya.k0 = (uint32_t)yr->seed;
+        ya.k1 = (uint32_t)(yr->seed >> 32);
+        st.e = glm_yrep_launch<T>(s, fam, ya);
+        if (st.e != hipSuccess) return;
+        if (ysum) {
+          GlmYrepPart* ypart = reinterpret_cast<GlmYrepPart*>(base + o[13]);
+          hipLaunchKernelGGL((k_glm_yrep_blocks<T>), dim3((unsigned)(nrb * nblk)), dim3(256), 0, s, (const T*)at(12), (const T*)a.y, ypart, (int)n, nc, chunk / 64);
+          hipLaunchKernelGGL(k_glm_yrep_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const GlmYrepPart*)ypart, reinterpret_cast<GlmYrepPart*>(base + o[14]),
+                             reinterpret_cast<double*>(base + o[15]), (int)n, nblk, chunk / 64, j0 / 64, S, j0 == 0 ? 1 : 0, j0 + nc == S ? 1 : 0, p.has_y ? 1 : 0);
+          st.e = hipGetLastError();
+        } else {
+          st.e = hipMemcpyAsync(static_cast<T*>(out) + j0 * n, at(12), sizeof(T) * (size_t)(n * nc), hipMemcpyDefault, s);
+        }
       } else {
         st.e = hipMemcpyAsync(static_cast<T*>(out) + j0 * nq * n, at(8), sizeof(T) * (size_t)(nq * n * nc), hipMemcpyDefault, s);
       }
     });
+  if (w.ok() && ysum) w.e = hipMemcpyAsync(out, base + o[15], (size_t)(4 * n) * 8, hipMemcpyDefault, s);
   if (w.ok() && summary) {
     if (!p.has_y) hipLaunchKernelGGL(k_glm_pred_no_lpd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sum, (int)n, (int)Q);
     w.e = hipGetLastError();

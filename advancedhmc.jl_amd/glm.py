@@ -19,6 +19,8 @@ Order of the sums — what fixes a chain's bits on the device, whatever N, the c
   * ½ Σ p_d θ_d²: lane-strided fma((p_d·θ_d), θ_d, ·), then the same butterfly;  ℓπ = fma(−½, Σ_prior, Σ_ℓ).
 The functions below follow the block and slice structure; numpy's own dot products stand in for the fma chains.
 """
+import math
+
 import numpy as np
 
 BERNOULLI_LOGIT, POISSON_LOG, GAUSSIAN_IDENTITY = 0, 1, 2
@@ -1157,4 +1159,314 @@ def predict_summary(values, loglik=None, chunk=None):
     if ll is not None:
         with np.errstate(divide="ignore", invalid="ignore"):
             out[2 * Q] = (sl[:, 0] + np.log(sl[:, 1])) - np.log(float(S))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# include/ahmc_glm_yrep.h: posterior-predictive draws y_rep ~ p(y | θ_s) and their per-observation summaries
+# ---------------------------------------------------------------------------------------------------------------------
+"""
+yrep_at is the CONTRACT of the device sampler (csrc/ahmc_glm_yrep_draw.hpp).  Arithmetic is float64 whatever the element type: planes are
+converted on entry, y on exit.  Randomness: Philox4x32-10 under key = seed (lo, hi) at counter (row, col, YREP_PURPOSE, slot); slot
+counts the 4-word blocks the element has taken, from 0; a block gives u = u53(v0, v1), u′ = u53(v2, v3) in (0, 1] and, where a normal is
+asked for, z = sqrt(−2·log u)·cos(2π·u′).  So an element's y depends on its quantities, its (row, col) and the seed alone.
+    0 Bernoulli (μ):            y = [u <= μ]
+    2, 3 Gaussian (μ, v):       y = fma(√v, z, μ)          (numpy has no fma: the mirror rounds the product, at most 1 u apart)
+    5, 6 (p_0 … p_{C−1}):       F ascending from +0, each add rounded on its own; y = #{c <= C − 2 : u > F_c}
+    1 Poisson (λ = μ) λ < 10:   one u;  p = exp(−λ), F = p, k = 0;  while u > F and k < 200: k += 1, p = (p·λ)/k, F = F + p
+                      λ >= 10:  Hörmann's PTRS, one block (u, u′) a round:  b = 0.931 + 2.53√λ, a = −0.059 + 0.02483·b,
+                                1/α = 1.1239 + 1.1328/(b − 3.4), v_r = 0.9277 − 3.6224/(b − 2);  U = u − ½, V = u′, us = ½ − |U|,
+                                k = floor((((2a)/us + b)·U + λ) + 0.43);  accept if us >= 0.07 and V <= v_r;  reject if k < 0 or
+                                (us < 0.013 and V > us);  else accept iff
+                                (log V + log(1/α)) − log(a/(us·us) + b) <= (−λ + k·log λ) − lgamma(k + 1)
+    4 negative binomial (μ, s): φ = exp(s);  g ~ Gamma(φ, 1) by Marsaglia–Tsang: φ < 1 takes a block FIRST for the boost u^(1/φ) and
+                                uses shape φ + 1;  d = shape − 1/3, c = 1/sqrt(9d);  a round takes a normal block, then a uniform
+                                block: w = 1 + c·z, t = (w·w)·w, reject if t <= 0, accept iff
+                                log u < ((((½·z)·z) + d) − d·t) + d·log t, then g = d·t;  y ~ Poisson(((g·boost)·μ)/φ), slots running on
+Every rejection loop stops after YREP_MAX_ROUNDS = 64 rounds with NaN (P < 1e-40).  A non-finite (or negative) quantity, or a dispersion
+that makes λ non-finite, gives NaN; λ = 0 gives 0.  The margin of an element is the smallest, over the decisions it took, of
+|lhs − rhs|/max(|lhs|, |rhs|, 1) of a comparison and of (distance to the nearest integer)/max(|x|, 1) of the floor.
+"""
+
+YREP_PURPOSE = 0x59524550
+YREP_MAX_ROUNDS = 64
+YREP_INVERSION_MAX = 200
+YREP_INVERSION_BELOW = 10.0
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 of csrc/ahmc_device.hpp on arrays of counters (uint64 holding 32-bit words): the four output words"""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & _M32 for c in (c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0) & _M32, np.uint64(k1) & _M32
+    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2
+        n0, n2 = (p1 >> s32) ^ c1 ^ k0, (p0 >> s32) ^ c3 ^ k1
+        c0, c1, c2, c3 = n0, p1 & _M32, n2, p0 & _M32
+        k0, k1 = (k0 + W0) & _M32, (k1 + W1) & _M32
+    return c0, c1, c2, c3
+
+
+def u53(hi, lo):
+    """the 53-bit uniform in (0, 1] of csrc/ahmc_device.hpp"""
+    b = ((hi >> np.uint64(5)) << np.uint64(26)) | (lo >> np.uint64(6))
+    return (b.astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+
+
+class _YrepState:
+    """the elements of one yrep_at call: their counters, the blocks taken, the outcome and the margin"""
+
+    def __init__(self, row, col, seed, n, ones):
+        self.row, self.col = row.astype(np.uint64), col.astype(np.uint64)
+        self.k0, self.k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+        self.slot = np.zeros(n, dtype=np.uint64)
+        self.y = np.full(n, np.nan)
+        self.margin = np.full(n, np.inf)
+        self.ones = ones
+
+    def block(self, idx):
+        """(u, u′) of the next block of the elements idx"""
+        if self.ones:                                     # the driver's test hook: every uniform is 1
+            u = up = np.ones(len(idx))
+        else:
+            v = philox4x32_10(self.row[idx], self.col[idx], np.full(len(idx), YREP_PURPOSE, dtype=np.uint64), self.slot[idx], self.k0, self.k1)
+            u, up = u53(v[0], v[1]), u53(v[2], v[3])
+        self.slot[idx] += np.uint64(1)
+        return u, up
+
+    def cmp(self, idx, lhs, rhs, threshold=False):
+        """`threshold`: a branch threshold of the sampler (λ against 10, φ against 1); a quantity that EQUALS it — λ = 10 given as a
+        plane, s = 0 — is decided alike everywhere and is not counted"""
+        lhs, rhs = np.broadcast_to(np.asarray(lhs, dtype=np.float64), idx.shape), np.broadcast_to(np.asarray(rhs, dtype=np.float64), idx.shape)
+        with np.errstate(invalid="ignore"):
+            m = np.abs(lhs - rhs) / np.maximum(np.maximum(np.abs(lhs), np.abs(rhs)), 1.0)
+        if threshold:
+            m = np.where(lhs == rhs, np.inf, m)
+        self.margin[idx] = np.fmin(self.margin[idx], m)
+
+    def floor(self, idx, x):
+        with np.errstate(invalid="ignore"):
+            m = np.abs(x - np.rint(x)) / np.maximum(np.abs(x), 1.0)
+        self.margin[idx] = np.fmin(self.margin[idx], m)
+
+
+def _yrep_normal(u, up):
+    return np.sqrt(-2.0 * np.log(u)) * np.cos(6.283185307179586476925286766559 * up)
+
+
+def _lgamma1(x):
+    try:
+        return math.lgamma(x)
+    except OverflowError:
+        return math.inf
+
+
+_lgamma = np.frompyfunc(_lgamma1, 1, 1)
+
+
+def _yrep_poisson(st, idx, lam, plant):
+    """y ~ Poisson(λ) for the elements idx (λ aligned with idx), written to st.y"""
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(lam) & (lam >= 0.0)
+        idx, lam = idx[ok], lam[ok]
+        st.cmp(idx, lam, YREP_INVERSION_BELOW, threshold=True)
+        small = lam < YREP_INVERSION_BELOW
+        # ---- inversion
+        i, l = idx[small], lam[small]
+        if len(i):
+            u, _ = st.block(i)
+            p = np.exp(-l)
+            F = p.copy()
+            k = np.zeros(len(i))
+            if plant == "inversion-from-1":
+                k += 1.0
+            live = np.arange(len(i))
+            for _ in range(YREP_INVERSION_MAX):
+                st.cmp(i[live], u[live], F[live])
+                stop = (u[live] < F[live]) if plant == "strict" else (u[live] <= F[live])
+                live = live[~stop]
+                if not len(live):
+                    break
+                k[live] += 1.0
+                p[live] = p[live] * l[live] / k[live]
+                F[live] = F[live] + p[live]
+            k = np.minimum(k, float(YREP_INVERSION_MAX))
+            st.y[i] = k
+        # ---- PTRS
+        i, l = idx[~small], lam[~small]
+        if not len(i):
+            return
+        b = 0.931 + 2.53 * np.sqrt(l)
+        a = -0.059 + 0.02483 * b
+        inv_alpha = 1.1239 + 1.1328 / (b - 3.4)
+        vr = 0.9277 - 3.6224 / (b - 2.0)
+        log_l = np.log(l)
+        shift = 0.0 if plant == "ptrs-no-shift" else 0.43
+        live = np.arange(len(i))
+        for _ in range(YREP_MAX_ROUNDS):
+            if not len(live):
+                break
+            j = i[live]
+            u, V = st.block(j)
+            U = u - 0.5
+            us = 0.5 - np.abs(U)
+            x = (2.0 * a[live] / us + b[live]) * U + l[live] + shift
+            k = np.floor(x)
+            st.floor(j, x)
+            st.cmp(j, us, 0.07)
+            big = us >= 0.07
+            st.cmp(j[big], V[big], vr[live][big])
+            acc = big & (V <= vr[live])
+            rest = ~acc
+            tiny = rest & (us < 0.013)
+            st.cmp(j[rest], us[rest], 0.013)
+            st.cmp(j[tiny], V[tiny], us[tiny])
+            rej = rest & ((k < 0.0) | (tiny & (V > us)))
+            test = rest & ~rej
+            if test.any():
+                lv = live[test]
+                lhs = np.log(V[test]) + np.log(inv_alpha[lv]) - np.log(a[lv] / (us[test] * us[test]) + b[lv])
+                rhs = -l[lv] + k[test] * log_l[lv] - _lgamma(k[test] + 1.0).astype(np.float64)
+                st.cmp(j[test], lhs, rhs)
+                acc[np.flatnonzero(test)[lhs <= rhs]] = True
+            st.y[j[acc]] = k[acc]
+            live = live[~acc]
+
+
+def _yrep_negbinomial(st, idx, mu, s, plant):
+    with np.errstate(all="ignore"):
+        phi = np.exp(s)
+        ok = np.isfinite(mu) & np.isfinite(phi) & (phi > 0.0) & (mu >= 0.0)
+        idx, mu, phi = idx[ok], mu[ok], phi[ok]
+        n = len(idx)
+        st.cmp(idx, phi, 1.0, threshold=True)
+        low = phi < 1.0
+        boost = np.ones(n)
+        if low.any():
+            u, _ = st.block(idx[low])
+            if plant != "gamma-no-boost":
+                boost[low] = np.power(u, 1.0 / phi[low])
+        shape = np.where(low, phi + 1.0, phi)
+        d = shape - 1.0 / 3.0
+        c = 1.0 / np.sqrt(9.0 * d)
+        g = np.full(n, np.nan)
+        live = np.arange(n)
+        for _ in range(YREP_MAX_ROUNDS):
+            if not len(live):
+                break
+            j = idx[live]
+            z = _yrep_normal(*st.block(j))
+            u, _ = st.block(j)
+            w = 1.0 + c[live] * z
+            t = w * w * w
+            st.cmp(j, t, 0.0)
+            pos = t > 0.0
+            dl, tl, zl = d[live][pos], t[pos], z[pos]
+            lhs = np.log(u[pos])
+            rhs = 0.5 * zl * zl + dl - dl * tl + dl * np.log(tl)
+            st.cmp(j[pos], lhs, rhs)
+            acc = np.zeros(len(live), dtype=bool)
+            acc[np.flatnonzero(pos)[lhs < rhs]] = True
+            g[live[acc]] = (d[live] * t)[acc]
+            live = live[~acc]
+        done = g == g
+        _yrep_poisson(st, idx[done], g[done] * boost[done] * mu[done] / phi[done], plant)
+
+
+def _yrep_family(family):
+    if family in ORDINAL_FAMILIES or family in CATEGORICAL_FAMILIES:
+        return {**ORDINAL_FAMILIES, **CATEGORICAL_FAMILIES}[family]
+    if not isinstance(family, str) and int(family) in (ORDERED_LOGIT, CATEGORICAL_LOGIT):
+        return int(family)
+    return family_code(family)
+
+
+def yrep_at(family, q, aux=None, row=None, col=None, seed=0, n_categories=None, _plant=None, _ones=False):
+    """(y, margin), each (n,) float64: one outcome per element from the family's sampler given the element's planes q (planes, n) —
+    μ; (μ, v) of a Gaussian; the C probabilities of an ordinal or a categorical model — `aux` (n,), the log-dispersion of a negative
+    binomial, and the element's counter (row, col) (default 0 … n − 1 and 0) under `seed`.  The mirror of ahmc_glm_yrep_at: this
+    function DEFINES the sampler (the section's docstring).  `_plant` plants one of the defects the tests must catch; `_ones` makes every
+    uniform 1, as the C++ driver's hook does."""
+    fam = _yrep_family(family)
+    q = np.asarray(q, dtype=np.float64)
+    if q.ndim == 1:
+        q = q[None]
+    classes = fam in (ORDERED_LOGIT, CATEGORICAL_LOGIT)
+    if classes and (n_categories is None or not 2 <= int(n_categories) <= CATEGORICAL_MAX_CATEGORIES):
+        raise ValueError(f"ArgumentError: n_categories = {n_categories} is outside 2 … {CATEGORICAL_MAX_CATEGORIES}")
+    planes = int(n_categories) if classes else 2 if fam in (GAUSSIAN_IDENTITY, GAUSSIAN_IDENTITY_SIGMA) else 1
+    if q.ndim != 2 or q.shape[0] != planes:
+        raise ValueError(f"DimensionMismatch: q {q.shape}, expected ({planes}, n)")
+    n = q.shape[1]
+    if fam == NEGBINOMIAL_LOG:
+        if aux is None:
+            raise ValueError("ArgumentError: the negative binomial needs aux, the log-dispersion of every element")
+        aux = np.broadcast_to(np.asarray(aux, dtype=np.float64), (n,))
+    row = np.arange(n, dtype=np.uint64) if row is None else np.broadcast_to(np.asarray(row), (n,))
+    col = np.zeros(n, dtype=np.uint64) if col is None else np.broadcast_to(np.asarray(col), (n,))
+    st = _YrepState(row, col, seed, n, _ones)
+    idx = np.arange(n)
+    with np.errstate(all="ignore"):
+        if fam == BERNOULLI_LOGIT:
+            u, _ = st.block(idx)
+            fin = np.isfinite(q[0])
+            st.cmp(idx, u, q[0])
+            st.y[fin] = ((u < q[0]) if _plant == "strict" else (u <= q[0]))[fin].astype(np.float64)
+        elif not classes and planes == 2:
+            z = _yrep_normal(*st.block(idx))
+            fin = np.isfinite(q[0]) & np.isfinite(q[1])
+            st.y[fin] = (np.sqrt(q[1]) * z + q[0])[fin]
+        elif classes:
+            u, _ = st.block(idx)
+            F = np.zeros(n)
+            y = np.zeros(n)
+            for c in range(planes - 1):
+                F = F + q[c]
+                st.cmp(idx, u, F)
+                y += ~(u < F) if _plant == "strict" else (u > F)
+            fin = np.isfinite(q).all(axis=0)
+            st.y[fin] = y[fin]
+        elif fam == POISSON_LOG:
+            _yrep_poisson(st, idx, q[0], _plant)
+        else:
+            _yrep_negbinomial(st, idx, q[0], aux, _plant)
+    return st.y, st.margin
+
+
+def yrep(family, planes, aux=None, seed=0, n_categories=None):
+    """(y_rep, margin), each (n_new, S): yrep_at for the planes (planes, n_new, S) of every new observation and draw — what
+    ahmc_glm_predict gives for "mean" (and "variance" after it, for a Gaussian) — with `aux` (S,) the draws' log-dispersion; element
+    (i, j) has the counter (row, col) = (i, j).  The mirror of ahmc_glm_yrep."""
+    p = np.asarray(planes, dtype=np.float64)
+    if p.ndim == 2:
+        p = p[None]
+    _, n_new, S = p.shape
+    row, col = np.broadcast_to(np.arange(n_new)[:, None], (n_new, S)).ravel(), np.broadcast_to(np.arange(S)[None, :], (n_new, S)).ravel()
+    a = None if aux is None else np.broadcast_to(np.asarray(aux, dtype=np.float64)[None, :], (n_new, S)).ravel()
+    y, m = yrep_at(family, p.reshape(p.shape[0], -1), a, row, col, seed, n_categories)
+    return y.reshape(n_new, S), m.reshape(n_new, S)
+
+
+def yrep_summary(y_rep, y=None, chunk=None):
+    """(4, n_new) float64 from y_rep (n_new, S): the mean and the variance (divisor S − 1; NaN at S = 1) of every observation's draws in
+    the order of predict_summary's sums (blocks of PRED_BLOCK draws, ascending, whatever the chunk), and with the outcomes y (n_new)
+    p_less = #(y_rep < y)/S and p_equal = #(y_rep == y)/S, the counts exact integers (NaN rows without y).  An observation with a
+    NaN draw has NaN moments; a NaN draw counts as neither less nor equal.  The mirror of ahmc_glm_yrep_summary: this function DEFINES
+    the order of its sums."""
+    v = np.asarray(y_rep)
+    if v.ndim != 2:
+        raise ValueError(f"DimensionMismatch: y_rep {v.shape}, expected (n_new, S)")
+    n_new, S = v.shape
+    out = np.full((4, n_new), np.nan)
+    if S == 0:
+        return out
+    out[0:2] = predict_summary(v[None], None, chunk)[0:2]
+    if y is not None:
+        yy = np.asarray(y, dtype=np.float64).reshape(n_new, 1)
+        vd = v.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            out[2] = (vd < yy).sum(axis=1, dtype=np.int64) / float(S)
+            out[3] = (vd == yy).sum(axis=1, dtype=np.int64) / float(S)
     return out

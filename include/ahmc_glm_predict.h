@@ -23,8 +23,8 @@
  * if it cannot be had the call fails with AHMC_ERR_RUNTIME naming the bytes, and nothing has changed.  The chunk is a multiple of 64
  * draws chosen from a byte budget (AHMC_GLM_PREDICT_BUDGET, bytes, read at every call; default 256 MiB), not from N.
  *
- * Out of scope: random draws y_rep of the outcome (the next step: an epilogue on μ and the dispersion, which this header puts on the
- * device); factor levels the bound model has not seen; quantiles of the predictions; observation weights; and a matrix larger than the
+ * Out of scope: factor levels the bound model has not seen (random draws y_rep of the outcome are ahmc_glm_yrep.h, a second kernel on the
+ * planes this header puts on the device); quantiles of the predictions; observation weights; and a matrix larger than the
  * caller's `out` can hold — ahmc_glm_predict writes planes·n_new·n_cols elements, the summary is what serves large n_cols.
  *
  * Kept apart like ahmc_glm_loo.h: exported by libahmc_hip.so only; the versions of the other headers do not change.

@@ -523,5 +523,6 @@ include("AdvancedHMCMI355XGLMOrdinal.jl")  # set_target!(z, ::OrdinalGLMTarget),
 include("AdvancedHMCMI355XGLMCategorical.jl")  # set_target!(z, ::CategoricalGLMTarget), glm_class_probs: include/ahmc_glm_categorical.h
 include("AdvancedHMCMI355XGLMLoo.jl")  # glm_loglik, glm_loo: include/ahmc_glm_loo.h
 include("AdvancedHMCMI355XGLMPredict.jl")  # glm_predict, glm_predict_summary: include/ahmc_glm_predict.h
+include("AdvancedHMCMI355XGLMYrep.jl")  # glm_yrep_at, glm_yrep, glm_yrep_summary: include/ahmc_glm_yrep.h
 
 end # module
