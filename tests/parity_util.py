@@ -34,6 +34,14 @@ MARGIN_BOUND = {np.dtype(np.float64): 1e-9, np.dtype(np.float32): 1e-4}
 # iteration of cfg2's Float32 pipeline) while NOT ONE of them flipped: the cap only guards against a bound that explains everything.
 MAX_NEAR_TIES = {np.dtype(np.float64): 0.002, np.dtype(np.float32): 0.15}
 
+# The thread geometries (G lanes per chain, E elements per lane) of the HIP engine, held to the sources by
+# tests/test_geometry_matrix.py: test_tables_equal_the_sources.  AHMC_GEOMETRIES (csrc/ahmc_inst.hpp), in its order …
+ALL_GEOMETRIES = [(4, 1), (8, 1), (16, 1), (32, 1), (64, 1), (4, 2), (8, 2), (16, 2), (32, 2), (64, 2), (32, 4), (64, 4), (64, 8),
+                  (128, 4), (256, 4), (512, 4), (128, 8), (256, 8), (512, 8)]
+# … and pick_geometry (csrc/ahmc_api.hip): (smallest D, largest D, G, E)
+DEFAULT_GEOMETRIES = [(1, 4, 4, 1), (5, 8, 4, 2), (9, 16, 8, 2), (17, 32, 16, 2), (33, 64, 32, 2), (65, 128, 64, 2), (129, 256, 64, 4),
+                      (257, 512, 64, 8), (513, 1024, 128, 8), (1025, 2048, 256, 8), (2049, 4096, 512, 8)]
+
 RECORDS = []  # (what, dtype name, n_chains, n_differ, n_near_tie, max margin among differing, min margin among agreeing)
 
 
