@@ -620,9 +620,7 @@ int launch_nuts(Ctx<T>* c, KP<T> p, int max_depth) {
   }
 #endif
   // (the waves that make the next launch's normals: behind the last chain's, in workgroups of the same size)
-#if AHMC_TAIL_NORMALS
   if (p.tail_waves) blocks = (int)(((int64_t)p.n_chunks + p.tail_waves + wpb - 1) / wpb);
-#endif
   if (const TargetOps<T>* o = ops_for(c)) o->nuts(c->G, c->E, MODE, (unsigned)blocks, wpb, smem, c->stream, p);
   HIPCHK(hipGetLastError());
 #if AHMC_WAVE_TIMELINE
@@ -698,10 +696,8 @@ int nuts_event_begin(Ctx<T>* c, std::pair<hipEvent_t, hipEvent_t>& ev) {
 
 template <class T>
 void set_tail(KP<T>& p, const KP<T>& from) {  // the tail job of a k_nuts launch (KP::tail_*), or none
-#if AHMC_TAIL_NORMALS
   p.tail_out = from.tail_out; p.tail_n_trans = from.tail_n_trans; p.tail_iteration = from.tail_iteration;
   p.tail_rows = from.tail_rows; p.tail_waves = from.tail_waves;
-#endif
 }
 
 template <class T>

@@ -531,7 +531,7 @@ struct DP2 {
   T *da_eps, *da_mu, *da_xbar, *da_Hbar;
   const T* da_tab;
   int lazy_gw;      // 1: a point's g′, w′ are on record only where a leapfrog can START from it (k_dense_epoch); a transition then begins with the motionless step
-  unsigned long long* prof;  // k_dense_epoch built with -DAHMC_EPOCH_PROF: Σ cycles in the products / the epilogue / the trees, Σ steps
+  unsigned long long* prof;  // k_dense_epoch built with -DAHMC_EPOCH_PROF (kept: the measurement build behind scripts/dbg_dense_epoch.py): Σ cycles in the products / the epilogue / the trees, Σ steps
 };
 
 template <class T>
@@ -1261,14 +1261,8 @@ __global__ __launch_bounds__(DT) void k_d_tree2(KP<T> p, DP2<T> q, const T* __re
 // decisions of the step-synchronous kernels (tests/test_gpu_parity.py: test_dense_epoch_kernel_equals_step_synchronous_kernels).
 // ================================================================================================
 constexpr int DE_WAVES = 8, DE_NCT = 2, DE_CHAINS = 16 * DE_NCT;
-#ifndef AHMC_EPOCH_NT
-#define AHMC_EPOCH_NT 1  // the epilogue's stores are non-temporal (cfg4 42.5 -> 42.9 TFLOP/s); 0: plain stores
-#endif
-#if AHMC_EPOCH_NT
+// the epilogue's stores are non-temporal (cfg4 42.5 -> 42.9 TFLOP/s against plain stores)
 #define DE_STORE(ptr, val) __builtin_nontemporal_store(val, reinterpret_cast<T2*>(ptr))
-#else
-#define DE_STORE(ptr, val) (*reinterpret_cast<T2*>(ptr) = (val))
-#endif
 #ifndef AHMC_EPOCH_NB
 #define AHMC_EPOCH_NB 8  // (cfg4: 4 → 8 chains per batch of the epilogue 35.7 → 36.1 TFLOP/s)
 #endif

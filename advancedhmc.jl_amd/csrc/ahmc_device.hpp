@@ -124,6 +124,8 @@ __device__ __forceinline__ double fma3(double a, double b, double c) {
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
   return d;
 }
+// (The engine no longer calls leaf_exp — the leaf weight is leaf_weight_exp below.  It stays as the reference the device probe
+// tests/device_probe/prims.hip holds the Horner form to, tests/test_device_primitives.py.)
 __device__ __forceinline__ double leaf_exp(double x) {
   constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
   const double dn = __builtin_rint(x * C(0x3ff71547652b82feULL));                 // x·log2(e)
@@ -149,16 +151,15 @@ __device__ __forceinline__ float leaf_exp(float x) { return exp(x); }
 
 // The weight of a NUTS leaf in the linear-domain kernels: W = exp(ℓw) for ℓw <= LINW_LIMIT (a larger ℓw flags the chain
 // for the log-domain redo pass and its W is never used), so the overflow branch of exp is dead; ℓw = -Inf (a divergent
-// leaf) must give exactly 0.  AHMC_LEAF_EXP = 0: leaf_exp (the device library's algorithm, 11 Horner steps);
-// 1: the same without the overflow select (3 VALU less, same bits where it matters);
-// 2: table-assisted — x = (64 n + j)·ln2/64 + t, |t| <= ln2/128: exp(x) = 2^n · T[j] · (1 + (e^t − 1)) with a 64-entry
-//    table of 2^(j/64) (a scalar load when the chain owns the wave) and a degree-5 polynomial: ≈9 VALU less than the
+// leaf) must give exactly 0.  Two forms:
+//  * a chain that owns the wave (UNIFORM): table-assisted — x = (64 n + j)·ln2/64 + t, |t| <= ln2/128: exp(x) = 2^n · T[j] · (1 + (e^t − 1))
+//    with a 64-entry table of 2^(j/64) (a scalar load) and a degree-5 polynomial: ≈9 VALU less than the
 //    Horner-11 form; ≤ 1.34 ulp against the exact value (½ ulp of the rounded table entry, ≤ 0.32 ulp from truncating
 //    e^t − 1 after t^5 at |t| = ln2/128, ½ ulp for the final fma; tests/test_device_primitives.py, > 2^22 arguments with both
 //    edges of every table bucket: 1.27 ulp measured), i.e. last-ulp differences against the device library's exp().
-#ifndef AHMC_LEAF_EXP
-#define AHMC_LEAF_EXP 2   // measured on cfg2 (sampling phase, in-kernel leapfrog/s): 1: 2.654e9, 2: 2.718e9
-#endif
+//    Measured on cfg2 (sampling phase, in-kernel leapfrog/s): Horner 2.654e9, table 2.718e9.
+//  * chains that SHARE a wave (G < 64): leaf_exp's algorithm (the device library's, 11 Horner steps) without the overflow and
+//    underflow selects (same bits where it matters) — see below why not the table.
 // 2^(j/64), j = 0..63, correctly rounded (generated with 60-digit decimal arithmetic)
 static __device__ const unsigned long long EXP2_64_BITS[64] = {
     0x3ff0000000000000ULL, 0x3ff02c9a3e778061ULL, 0x3ff059b0d3158574ULL, 0x3ff0874518759bc8ULL,
@@ -177,24 +178,17 @@ static __device__ const unsigned long long EXP2_64_BITS[64] = {
     0x3ffc199bdd85529cULL, 0x3ffc67f12e57d14bULL, 0x3ffcb720dcef9069ULL, 0x3ffd072d4a07897cULL,
     0x3ffd5818dcfba487ULL, 0x3ffda9e603db3285ULL, 0x3ffdfc97337b9b5fULL, 0x3ffe502ee78b3ff6ULL,
     0x3ffea4afa2a490daULL, 0x3ffefa1bee615a27ULL, 0x3fff50765b6e4540ULL, 0x3fffa7c1819e90d8ULL};
-#ifndef AHMC_LEAF_EXP_NARROW_TABLE
-// Chains that SHARE a wave (G < 64): the table entry is a per-lane GLOBAL load in the middle of the leaf's chain of dependent stages — and
+// Chains that SHARE a wave (G < 64): the table entry would be a per-lane GLOBAL load in the middle of the leaf's chain of dependent stages — and
 // its s_waitcnt vmcnt(0) also waits for every slot store still in flight.  Round 5, stage stamps of a measurement build
 // (profiles/r5_leaf_latency_cfg3.json): the weight stage took 1 112 of a lone wave's 2 905 cycles per leaf step on cfg3 (1 830 of 4 023 at
-// the bench's occupancy) against 310 of 1 571 on cfg2, where the entry is a scalar load.  0: those kernels evaluate the Horner-11 form
-// (no memory access: 9 more VALU, ≈ 700 fewer cycles); 1: the table for every geometry (rounds 3–4).
-#define AHMC_LEAF_EXP_NARROW_TABLE 0
-#endif
-#ifndef AHMC_LEAF_MICRO
-#define AHMC_LEAF_MICRO 1   // round 5's two instruction cuts in the leaf (no underflow select in the weight's exp; ΔH_max by a scalar branch on the direction); 0: round 4's forms, for A/B runs
-#endif
+// the bench's occupancy) against 310 of 1 571 on cfg2, where the entry is a scalar load.  Those kernels evaluate the Horner-11 form
+// (no memory access: 9 more VALU, ≈ 700 fewer cycles).
 // (TWIN: leaf_weight_exp_pair below repeats the table form of this function, statement for statement, for two leaves in the two lane
 // parities of a wave — change both)
 template <bool UNIFORM>
 __device__ __forceinline__ double leaf_weight_exp(double x) {
   constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
-#if AHMC_LEAF_EXP == 2
-  if constexpr (UNIFORM || AHMC_LEAF_EXP_NARROW_TABLE) {
+  if constexpr (UNIFORM) {
   // (clamped first: ℓw = −Inf is a routine input — every divergent leaf — and a float-to-int conversion of ±Inf is undefined
   // behaviour, however the hardware's v_cvt_i32_f64 saturates; the final select still returns 0 below −1075)
   const double xc = x < -1100.0 ? -1100.0 : x;
@@ -202,7 +196,7 @@ __device__ __forceinline__ double leaf_weight_exp(double x) {
   double t = __builtin_fma(dk, -0x1.62e42fef00000p-7, xc);                  // − k·ln2/64: high part (20 trailing zero bits: exact product)
   t = __builtin_fma(dk, -0x1.473de6af278edp-40, t);                         // low part
   int k = (int)dk;
-  if constexpr (UNIFORM) k = __builtin_amdgcn_readfirstlane(k);             // a chain owns the wave: scalar table load
+  k = __builtin_amdgcn_readfirstlane(k);                                    // a chain owns the wave: scalar table load
   const double tj = C(EXP2_64_BITS[k & 63]);
   double q = __builtin_fma(t, 8.3333333333333332e-03, 4.1666666666666664e-02);  // 1/120, 1/24
   q = fma3(t, q, 1.6666666666666666e-01);
@@ -211,15 +205,8 @@ __device__ __forceinline__ double leaf_weight_exp(double x) {
   q = q * t;                                                                // e^t − 1
   // (no select for the underflow: x is clamped at −1100 above — ℓw = −Inf included — and from −1075 down ldexp's exponent is ≤ −1551, below
   // the smallest subnormal: the result IS 0 there; a NaN x fails the clamp's compare and propagates.  Round 5: three VALU per leaf fewer.)
-#if AHMC_LEAF_MICRO
   return __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
-#else
-  double z = __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
-  z = x < -1075.0 ? 0.0 : z;
-  return z;
-#endif
   }
-#endif
   {
   const double xh = x < -1100.0 ? -1100.0 : x;                                    // (as above: −Inf is a routine input; ldexp underflows to 0 for it)
   const double dn = __builtin_rint(xh * C(0x3ff71547652b82feULL));                // x·log2(e)
@@ -237,12 +224,6 @@ __device__ __forceinline__ double leaf_weight_exp(double x) {
   q = __builtin_fma(t, q, 1.0);
   q = __builtin_fma(t, q, 1.0);
   double z = __builtin_ldexp(q, (int)dn);
-#if AHMC_LEAF_EXP == 0
-  z = x > 1024.0 ? Lim<double>::inf() : z;
-#endif
-#if !AHMC_LEAF_MICRO
-  z = x < -1075.0 ? 0.0 : z;
-#endif
   return z;   // (the underflow needs no select either: clamped at −1100, ldexp's exponent −1587 gives 0)
   }
 }
@@ -265,7 +246,6 @@ __device__ __forceinline__ T alpha_from_logweight(T lw) {
 // (int)dk is defined (the caller hands every lane one of the two leaves' arguments, so it is wherever leaf_weight_exp's own is).
 template <int LA, int LB>
 __device__ __forceinline__ double leaf_weight_exp_pair(double x, bool odd) {
-#if AHMC_LEAF_EXP == 2
   constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
   const double xc = x < -1100.0 ? -1100.0 : x;
   const double dk = __builtin_rint(xc * 92.33248261689366);                // 64 / ln 2
@@ -280,16 +260,7 @@ __device__ __forceinline__ double leaf_weight_exp_pair(double x, bool odd) {
   q = fma3(t, q, 0.5);
   q = fma3(t, q, 1.0);
   q = q * t;                                                                // e^t − 1
-#if AHMC_LEAF_MICRO
   return __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
-#else
-  double z = __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
-  z = x < -1075.0 ? 0.0 : z;
-  return z;
-#endif
-#else
-  return leaf_weight_exp<true>(x);   // (the Horner forms read no table: already lane-local)
-#endif
 }
 template <int LA, int LB>
 __device__ __forceinline__ float leaf_weight_exp_pair(float x, bool) { return exp(x); }
@@ -360,6 +331,7 @@ __device__ __forceinline__ double xor32_sum(double v) {
 // 3 MFMA + 6 adds + 2 selects instead of 30 VALU; all lanes receive the same bits (every output element goes through
 // the same FMA chain on the same inputs).  The summation ORDER differs from the DPP butterfly, i.e. last-ulp
 // differences against it — inside the 1e-9 parity tolerance against the oracle, which sums in index order anyway.
+// (AHMC_MFMA_REDUCE is kept: tests/test_device_primitives.py builds the probe with it)
 #ifndef AHMC_MFMA_REDUCE
 #define AHMC_MFMA_REDUCE 0
 #endif
@@ -403,6 +375,7 @@ __device__ __forceinline__ void wave64_allsum2_mfma(T& a, T& b) {
 // these kernels (≈17 of ≈900 wave-cycles per leapfrog), the VALU port is the bottleneck.  The price is latency
 // (≈60-100 cycles per exchange against 8): it pays only while the other waves of the SIMD fill the gap.
 // AHMC_DS_REDUCE: bit 0 = the xor-16 / xor-32 stages, bit 1 = also the four in-row stages, bit 2 = the final broadcast.
+// (kept: tests/test_device_primitives.py builds the probe with it)
 #ifndef AHMC_DS_REDUCE
 #define AHMC_DS_REDUCE 0
 #endif
@@ -469,18 +442,13 @@ __device__ __forceinline__ void wave_allsum2(T& a, T& b) {
 // to quad ((Q0 + Q3) + (Q2 + Q1) in quad 0, (Q1 + Q0) + (Q3 + Q2) in quad 1: row_ror:n reads lane l − n), so another even lane may hold Σa rounded differently —
 // wave_allsum2 returns lane 0's and lane 1's bits, and so must this.  Rows need no care: xor16 / xor32 add {lower, upper} in the
 // same order on both sides.  NaN: `<=` is false, as in the two compares this replaces.
-// 0: wave_allsum2 + two compares, the form of rounds 1–6, for A/B runs.
-// (Who reaches the first arm below: k_nuts calls this function only when AHMC_UTURN_ANY != 0, so in the engine it is the arm of the
-// experimental reductions alone — -DAHMC_MFMA_REDUCE=1, or -DAHMC_DS_REDUCE with bit 0 or 1, whose additions differ from the DPP
-// butterfly's and which therefore go through their own wave_allsum2.  AHMC_DS_REDUCE=4 moves only the final broadcast to the LDS pipe,
-// which this predicate does not make: it takes the second arm.  A direct caller built with -DAHMC_UTURN_ANY=0, such as the device
-// probe, gets the old form.)
-#ifndef AHMC_UTURN_ANY
-#define AHMC_UTURN_ANY 1
-#endif
+// (The first arm below — wave_allsum2 + two compares — is the arm of the experimental reductions alone: -DAHMC_MFMA_REDUCE=1, or
+// -DAHMC_DS_REDUCE with bit 0 or 1, whose additions differ from the DPP butterfly's and which therefore go through their own
+// wave_allsum2.  AHMC_DS_REDUCE=4 moves only the final broadcast to the LDS pipe, which this predicate does not make: it takes the
+// second arm.)
 template <class T>
 __device__ __forceinline__ bool wave64_any_le0_pair(T a, T b) {
-  if constexpr (!AHMC_UTURN_ANY || AHMC_MFMA_REDUCE || (AHMC_DS_REDUCE & 3) != 0) {
+  if constexpr (AHMC_MFMA_REDUCE || (AHMC_DS_REDUCE & 3) != 0) {
     wave_allsum2<64>(a, b);
     return (__builtin_amdgcn_ballot_w64(a <= T(0)) != 0) || (__builtin_amdgcn_ballot_w64(b <= T(0)) != 0);
   } else {
@@ -516,7 +484,7 @@ __device__ __forceinline__ void wave_allsum4(T& a, T& b, T& c, T& d) {
   d = dpp_mov<0x153>(z);
 }
 
-// What a PAIR of consecutive NUTS leaves and their level-0 merge need from the wave, in ONE reduction (k_nuts, AHMC_LEAF_PAIR): the two
+// What a PAIR of consecutive NUTS leaves and their level-0 merge need from the wave, in ONE reduction (the pair step of k_nuts): the two
 // leaves' energies ea, eb (lane partials in, sums out, the same bits in every lane) and the generalised U-turn decision
 // Σda <= 0 || Σdb <= 0 of the merged pair as one wave-uniform predicate.  The lane exchanges are wave_allsum4<64>'s with (da, db) as its
 // first pair and (ea, eb) as its second:
@@ -529,6 +497,8 @@ __device__ __forceinline__ void wave_allsum4(T& a, T& b, T& c, T& d) {
 //     are 1 and 3, and the energies are broadcast from lanes 6 / 7 of the row.  AHMC_PAIR_RED_QUAD names the quad (the probe
 //     builds the other one as well).
 // f64: 14 + 7 + 3 + 3 + 5 + 5 + 1 + 4 = 42 VALU, against 22 + 22 + 27 for two leaves' wave_allsum and the merge's predicate.
+// (The engine calls only wave64_pair_reduce_t below.  This function stays because tests/device_probe/pair_red.hip and pair_stats.hip
+// call it: it is what they hold the transposed form to.  TWIN of wave64_pair_reduce_t up to `le0`: change both.)
 #ifndef AHMC_PAIR_RED_QUAD
 #define AHMC_PAIR_RED_QUAD 1
 #endif
@@ -552,10 +522,6 @@ __device__ __forceinline__ bool wave64_pair_reduce(T da, T db, T& ea, T& eb) {
 // comes back in z — lanes 0 / 1 of a row hold Σda / Σdb, lanes 4q + 2 / 4q + 3 hold Σea / Σeb (with the butterfly's bits in quads 1 and 3,
 // as above).  For pair_leaf_stats (below), which does both leaves' scalar work in the two lane parities instead of once per broadcast
 // value.  TWIN of wave64_pair_reduce up to `le0`: change both (tests/device_probe/pair_stats.hip runs them on the same data).
-// AHMC_PAIR_LANE_STATS 0: k_nuts keeps wave64_pair_reduce and the serial leaf_stats — the parent's device code, for A/B runs.
-#ifndef AHMC_PAIR_LANE_STATS
-#define AHMC_PAIR_LANE_STATS 1
-#endif
 template <class T>
 __device__ __forceinline__ bool wave64_pair_reduce_t(T da, T db, T ea, T eb, T& z) {
   const bool odd = (threadIdx.x & 1u) != 0, up = (threadIdx.x & 2u) != 0;
@@ -1009,7 +975,7 @@ __device__ __forceinline__ T leapfrog_step_ne(Point<T, E>& z, const T (&minv)[E]
 // The vector work of leapfrog_step_ne alone (the same expressions): returns this lane's partial of ℓπ − ½ rᵀM⁻¹r, NOT reduced (the pair step of k_nuts
 // carries two leaves' partials through one reduction).
 // TWIN of leapfrog_step_ne above, line for line up to the reduction: change both.  (Two texts on purpose: with leapfrog_step_ne written as a call of this one AND
-// the leaf's scalar work of k_nuts in a shared lambda, the -DAHMC_LEAF_PAIR=0 build no longer had the parent's device code — 760 kernels differed; the
+// the leaf's scalar work of k_nuts in a shared lambda, the single-leaf loop no longer compiled to the device code it had before — 760 kernels differed; the
 // two rewrites were not tried one by one.  tests/test_leaf_pairs.py holds the twins together.)
 template <class T, int G, int E, int TK>
 __device__ __forceinline__ T leapfrog_step_ne_partial(Point<T, E>& z, const T (&minv)[E], T eps, const TargetP<T>& tp, int lane, int d0) {
@@ -1033,15 +999,16 @@ template <int L> __device__ __forceinline__ double readlane_t(double v) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), L), __builtin_amdgcn_readlane(__double2loint(v), L));
 }
 
-// The order-independent scalar work of the TWO leaves of a pair step of k_nuts (AHMC_PAIR_LANE_STATS), once, with lane parity picking
-// the leaf — in k_nuts' leaf_stats it runs once per leaf in all 64 lanes on a wave-uniform value, the second run behind the first.
+// The order-independent scalar work of the TWO leaves of a pair step of k_nuts, once, with lane parity picking
+// the leaf — in the single-leaf arm of k_nuts it runs once per leaf in all 64 lanes on a wave-uniform value.
 // z is wave64_pair_reduce_t's transposed register.  One quad_perm [2,3,2,3] gives EVERY lane an energy (even lanes Σea, odd lanes
 // Σeb): lanes 0 / 1 of a quad hold dot-product sums, which may be ±Inf or NaN, and (int)dk of the weight's exp on those is undefined
 // behaviour.  Quads 0 and 2 then hold the energies in another rounding (wave64_pair_reduce); nothing reads them.  Lanes 4Q + 2 / 4Q + 3
-// (6 / 7) take leaf a's / leaf b's value through the expressions of leaf_stats, in its order, and v_readlane and the compares' lane
+// (6 / 7) take leaf a's / leaf b's value through the expressions of the single-leaf arm's scalar block, in its order, and v_readlane and the compares' lane
 // masks hand the results back as scalars.  No exec-masked region.  What depends on the ORDER of the two leaves (the running sums, maxabs,
 // redo / numerical / sub_term, the branch that drops leaf b) stays with the caller.
-// TWIN of leaf_stats in the pair arm of k_nuts (ahmc_nuts.hpp): a change to a leaf's scalar work is made in both and in the single-leaf arm.
+// TWIN of the single-leaf arm's scalar block in k_nuts (ahmc_nuts.hpp, from `pos_cur += v;` to the running statistics): a change to a
+// leaf's scalar work is made in both (tests/device_probe/pair_stats.hip repeats those lines as its serial reference).
 template <class T> struct PairLeafStats {
   T w[2], sa[2], dH[2];     // leaf weight (LINW: W, else ℓw), α = min(1, W), ΔH
   bool redo[2], div[2];     // ℓw above the linear domain's limit; the divergence test !(−H0 < Δ_max + ne)
@@ -1116,7 +1083,7 @@ __device__ __forceinline__ void fill_caches(Point<T, E>& z, const T (&minv)[E], 
 
 // vector load/store of one chain's slice: element d0+e of chain c lives at base[off + d0 + e].
 // Full, 16-byte aligned lanes use dwordx4/dwordx2 accesses (CH elements per access).
-// SB (k_nuts where a chain owns a wave, AHMC_TRANS_SCALAR): `base + off` is wave-uniform — formed in 64 bits on the scalar unit — and the
+// SB (k_nuts where a chain owns a wave, its TSC): `base + off` is wave-uniform — formed in 64 bits on the scalar unit — and the
 // lane adds only its BYTE offset d0·sizeof(T), a 32-bit value: the accesses take the scalar-base form (saddr + voffset) with no 64-bit
 // per-lane address arithmetic.  d0·sizeof(T) is a multiple of the 16-byte piece (E is a multiple of CH), so the alignment test is the
 // scalar base's.  Same elements, same addresses, same predicate as the per-lane form.

@@ -7,13 +7,9 @@
 
 namespace ahmc {
 
-#ifndef AHMC_TAIL_NORMALS
-// 1: the sampling and warm-up kernels of a chain that owns one wave (G = 64, MODE 0 / 3) accept waves BEHIND their chain waves that make
+// Tail normals: the sampling and warm-up kernels of a chain that owns one wave (G = 64, MODE 0 / 3) accept waves BEHIND their chain waves that make
 // the momentum normals of the launch that follows (KP::tail_*, k_nuts in ahmc_nuts.hpp; the host side: tail_normals_plan).  Workgroups are dealt in block order, so
 // those waves start when no chain is left to start: they run in the slots the launch's tail leaves empty, beside its oldest waves.
-// 0: the kernels of round 7, instruction for instruction.
-#define AHMC_TAIL_NORMALS 1
-#endif
 
 // Everything a kernel needs, passed by value.  Arrays are (D,N) column-major / (N,).
 // The context keeps its per-chain arrays in four slabs so that the kernel arguments stay small
@@ -88,26 +84,24 @@ struct KP {
   T init_eps;
   int max_iters;
   // k_nuts, G = 64, MODE 0 / 3: the standard normals of the launch that FOLLOWS this one, made by extra waves behind the chain waves
-  // (normals_rows, ahmc_nuts.hpp).  All zero: no such waves.  At the END of the struct: the offsets of everything above are round 7's
-  // (and with AHMC_TAIL_NORMALS = 0 so is its size, which places the kernels' hidden arguments).
-#if AHMC_TAIL_NORMALS
+  // (normals_rows, ahmc_nuts.hpp).  All zero: no such waves.  At the END of the struct: the offsets of everything above are round 7's.
   T* tail_out;              // (tail_n_trans, N, D): the context's second normals buffer, which no wave of this launch reads
   int tail_n_trans;         // transitions of the following launch
   uint32_t tail_iteration;  // its first Philox iteration
   int tail_rows;            // rows (one transition of one chain) per tail wave
   unsigned int tail_waves;  // waves appended to the grid
-#endif
 };
-// LDS / scratch layout of k_nuts (ahmc_nuts.hpp), needed by the host launch plan as well
-constexpr int NUTS_NSC = 3;      // T scalars per pending level: w, Σα, ΔH_max
-constexpr int NUTS_NSI = 2;      // int scalars per pending level: nα, candidate leaf index
+// LDS / scratch layout of k_nuts (ahmc_nuts.hpp), needed by the host launch plan as well.
+// Of the scalars per pending level only w and the candidate leaf index are used: Σα, ΔH_max and nα became running values in registers
+// (k_nuts), and their slots are UNUSED.  They remain because NUTS_NSC / NUTS_NSI size the LDS carve-up, the launch plan and the
+// plugin ABI word (nuts_scratch_layout): shrinking them changes occupancy and speed, which needs a measured change of its own.
+constexpr int NUTS_NSC = 3;      // T scalars per pending level: w, (unused: Σα), (unused: ΔH_max)
+constexpr int NUTS_NSI = 2;      // int scalars per pending level: (unused: nα), candidate leaf index
 constexpr int NUTS_NAT = 5;      // per chain, T: the adaptor's state while a warm-up batch runs (nominal ϵ, DAState ϵ, μ, x̄, H̄)
 constexpr int NUTS_NAI = 3;      // per chain, int: DAState m, Welford count, the re-integration checkpoint (position << 1 | triple)
 constexpr int NUTS_DORMANT = 7;  // vector slots OTH_TH, OTH_R, OTH_G, TREE_A, Z0_R, Z0_G, START_R (strict)
-#ifndef AHMC_CKPT
-#define AHMC_CKPT 1              // k_nuts re-integrates to the candidate from the EDGE its subtree grew from instead of from z0 (ahmc_nuts.hpp); 0: from z0 (rounds 1–4)
-#endif
-constexpr int NUTS_CKPT = AHMC_CKPT ? 6 : 0;   // two (θ, r, g) triples behind the dormant slots, always in global scratch
+// (k_nuts re-integrates to the candidate from the EDGE its subtree grew from instead of from z0: the checkpoint, ahmc_nuts.hpp)
+constexpr int NUTS_CKPT = 6;     // two (θ, r, g) triples behind the dormant slots, always in global scratch
 // The layout as ONE number: the host's launch plan (ahmc_api.hip, plan_nuts) sizes the scratch the kernels index, and the two may
 // come from different compilations (the instantiation units of a variant build with other -D flags; a target plugin built on
 // another machine).  Every launch table carries the word of ITS translation unit; plan_nuts refuses a table whose word is not the host's.

@@ -17,28 +17,14 @@
 //               every wave access is 64 consecutive 16-B pieces): the pending subtree of every
 //               level (A, RF), the dormant edge of the tree (θ, r, g), the whole-tree ρ, and
 //               (r0, g0) of the start point
-//   LDS scalars: per pending level {w = ℓw or n, Σα, nα, ΔH_max, candidate leaf index}
+//   LDS scalars: per pending level {w = ℓw or n, candidate leaf index} (Σα, nα, ΔH_max are running values in registers)
 // The multinomial/slice candidate is carried as a LEAF INDEX (signed distance from the start
 // point along the trajectory), not as a phase point: the selected point is re-integrated from the
 // start at the end (vector work only, no reductions, no RNG), which halves the pending state and
 // removes every candidate copy from the merge path.
 #pragma once
-#ifndef AHMC_SCALAR_ANY
-#define AHMC_SCALAR_ANY 1      // loop-control predicates of a wave-owning chain are tested directly instead of through a ballot (0: ballot)
-#endif
 
-#ifndef AHMC_ADAPT_REREAD
-#define AHMC_ADAPT_REREAD 1   // the warm-up kernels re-read the adaptor's argument block in every epilogue instead of carrying it (below)
-#endif
-#ifndef AHMC_RUNNING_STATS
-// 1: Σα, nα and ΔH_max of the subtree a doubling builds are RUNNING values over its leaves in build order — the statistics the
-// reference carries through every `combine` (src/trajectory.jl:533-542) are a sum, a count and a maximum of |·| over the same
-// leaves, so only the order of the additions changes (acceptance_rate in the last bit; no decision depends on it): no per-level
-// Σα / nα / ΔH_max in LDS, nothing to fold in at a merge, at a park or when a subtree ends early.  0: through every merge.
-#define AHMC_RUNNING_STATS 1
-#endif
-
-// AHMC_LEAF_PROF (measurement build only, scripts/leaf_latency.py; implies the per-wave timeline record): where a leaf step's cycles go.
+// AHMC_LEAF_PROF (kept: it is the measurement build behind scripts/leaf_latency.py; implies the per-wave timeline record): where a leaf step's cycles go.
 // Every wave reads the shader-clock counter (s_memtime) at the stage boundaries of the leaf loop — fenced by scheduling barriers, so no
 // instruction moves across a stamp — and sums the differences per stage: [0] leapfrog vector work (half-steps, density and its
 // gradient), [1] the energy all-reduce, [2] leaf weight / exp, divergence test, running statistics, [3] merges (operand loads, dot
@@ -60,11 +46,9 @@
 #define AHMC_LP_TICK(i)
 #define AHMC_LP_COUNT(i, n)
 #endif
-#ifndef AHMC_HIER_PRE
-#define AHMC_HIER_PRE 1   // multi-wave hierarchical target: μ, log τ of the next leaf ride on this leaf's energy exchange (0: round 5's broadcast per leaf)
-#endif
-#ifndef AHMC_CKPT_G64
-#define AHMC_CKPT_G64 0   // 1: the checkpoint also where one chain fills one wave (experiment)
+// AHMC_WAVE_TIMELINE (kept: it is the measurement build behind scripts/wave_timeline.py): when each wave ran and how full its leaf steps were
+#ifndef AHMC_WAVE_TIMELINE
+#define AHMC_WAVE_TIMELINE 0
 #endif
 #ifndef AHMC_TL_WORDS
 #define AHMC_TL_WORDS 8
@@ -74,7 +58,7 @@
 
 #include "ahmc_kernels.hpp"
 
-// AHMC_LEAF_PAIR 1: where ONE chain owns ONE wave (G = 64) the fast kernels (MODE 0, 1, 3, 4) build the subtree of every doubling but
+// The pair step: where ONE chain owns ONE wave (G = 64) the fast kernels (MODE 0, 1, 3, 4) build the subtree of every doubling but
 // the first TWO LEAVES PER STEP.  Leaf 2k needs nothing from leaf 2k − 1's energy, so both leapfrogs' vector work runs first — the odd
 // leaf's r stays in registers: it is the level-0 pending half (ρ and first-built r are that one vector), which the single-leaf loop
 // parks in the level-0 slot and fetches back one leaf later — then ρ = r_a + r_b and the two U-turn dot products of the pair's level-0
@@ -83,17 +67,9 @@
 // single-leaf loop's order — leaf a, leaf b, the merge's draw and select — so the tree draws are consumed in the same order and number;
 // if leaf a diverges nothing of leaf b is used (its leapfrog was speculative: at most once per transition).  Every number takes the
 // additions it takes in the single-leaf loop: the results are bit-identical (tests/test_leaf_pairs.py).
-// 0: the single-leaf loop everywhere, instruction for instruction (A/B runs).  The measurement builds keep the single-leaf loop: their
-// stage stamps describe it.
-#ifndef AHMC_LEAF_PAIR
-#define AHMC_LEAF_PAIR 1
-#endif
-#if AHMC_LEAF_PROF || AHMC_WAVE_TIMELINE
-#undef AHMC_LEAF_PAIR
-#define AHMC_LEAF_PAIR 0
-#endif
+// The measurement builds (AHMC_LEAF_PROF, AHMC_WAVE_TIMELINE) keep the single-leaf loop: their stage stamps describe it.
 
-// AHMC_TRANS_SCALAR 1 (round 11): the code that runs ONCE PER TRANSITION where one chain owns one wave (G = 64, the fast kernels — MODE 0, 1, 3, 4).
+// Once per transition (round 11; TSC in k_nuts): the code that runs ONCE PER TRANSITION where one chain owns one wave (G = 64, the fast kernels — MODE 0, 1, 3, 4).
 //  * The chain index is wave-uniform there but was carried per lane, so every per-chain address was a 64-bit vector add.  It is taken into
 //    scalar registers once (v_readfirstlane) and made opaque once per transition as a SCALAR ("+s"): c·D, kt·D·N and the statistics' elements
 //    are formed in 64 bits on the scalar unit, the lane adds its 32-bit byte offset (load_vec / store_vec <…, SB>, ahmc_device.hpp), and the
@@ -104,14 +80,11 @@
 //    where they are used, through a pointer to the kernel-argument segment that the optimiser cannot see through (args_reread): a few
 //    scalar loads per transition on a port that carries ≈ 1 instruction per leapfrog, and nothing live across the tree.  KP<T> is the
 //    kernels' only argument, so it starts at offset 0 of the segment (the hidden arguments follow the explicit ones).
-// No floating-point expression is touched.  0: the parent's device code, digest for digest (A/B partner; profiles/r11_experiments.md).
-#ifndef AHMC_TRANS_SCALAR
-#define AHMC_TRANS_SCALAR 1
-#endif
+// No floating-point expression is touched (profiles/r11_experiments.md).
 
 namespace ahmc {
 
-// The kernel's argument block read again HERE: see AHMC_TRANS_SCALAR above.  args_reread<ON> gives the pointer (valid in a __global__ function
+// The kernel's argument block read again HERE: see "once per transition" above.  args_reread<ON> gives the pointer (valid in a __global__ function
 // whose first — only — argument is the P passed by value; null when OFF), args_at<ON>(p, q) the block an expression reads: *q, or `p` itself.
 // (Two steps, and no named reference to `p`: a `const P& pa = p;` in the kernel — even an unused one — changed the register allocation of
 // the instantiations it does nothing in.)
@@ -131,7 +104,7 @@ __device__ __forceinline__ const P& args_at(const P& p, const P* q) {
   else return p;
 }
 
-// The adaptor's argument block as the warm-up epilogue reads it (AHMC_ADAPT_REREAD below).  ON: the pointer comes from the re-read kernel
+// The adaptor's argument block as the warm-up epilogue reads it (k_nuts, the ADAPT epilogue).  ON: the pointer comes from the re-read kernel
 // arguments — opaque already — and the block, which no kernel writes, is read as CONSTANT memory: scalar loads, and the array pointers it
 // holds arrive in scalar registers (through the generic pointer they were per-lane values, and every Welford access a 64-bit vector add).
 template <bool ON, class A, class P>
@@ -169,16 +142,8 @@ struct Chunking {
 // address arithmetic per access, the LDS slots reached through the flat path (longer latency, counted on vmcnt AND lgkmcnt,
 // so a wait for one slot also waited for every scratch store in flight).  Now the choice is a scalar branch between a
 // ds_read / ds_write with an immediate offset and a global access in the saddr form.
-#ifndef AHMC_SLOTS_ADDRSPACE
-#define AHMC_SLOTS_ADDRSPACE 1   // 0: generic pointers (rounds 1–4)
-#endif
-#if AHMC_SLOTS_ADDRSPACE
 #define AHMC_AS_LDS __attribute__((address_space(3)))
 #define AHMC_AS_GLB __attribute__((address_space(1)))
-#else
-#define AHMC_AS_LDS
-#define AHMC_AS_GLB
-#endif
 template <class T, int E>
 struct Slots {
   AHMC_AS_LDS T* lds;   // first n_lds slots
@@ -212,12 +177,8 @@ struct Slots {
       _Pragma("unroll") for (int c = 0; c < NCH; ++c) v[c] = sb[off + (unsigned)(c * 64)];                  \
     }                                                                                                       \
   }
-#if AHMC_SLOTS_ADDRSPACE
   AHMC_SLOT_PUT(AHMC_AS_LDS)
   AHMC_SLOT_PUT(AHMC_AS_GLB)
-#else
-  AHMC_SLOT_PUT()
-#endif
 #undef AHMC_SLOT_PUT
   __device__ __forceinline__ void store(int slot, const T (&v)[E]) const {
     constexpr int SE = Chunking<T, E>::NCH * 64 * Chunking<T, E>::CH;
@@ -263,31 +224,22 @@ __device__ __forceinline__ void leapfrog_core(Point<T, E>& z, const T (&minv)[E]
 // (the momentum normals, jitter and the static-HMC draws keep 53-bit uniforms).
 // WIDE (a chain owns whole wavefronts, G >= 64): the lanes of the wave run Philox on consecutive blocks at once and a draw is one
 // v_readlane from a lane that holds its block.  Same blocks, same words, same draw order as the narrow form — only who computes what.
-//   AHMC_DRAWS_PER_LANE 1 (round 7): lane ℓ computes block base + ℓ, so one Philox evaluation (≈ 85 VALU) serves 256 draws — one
-//     evaluation for every tree below 255 draws, where the row form below made one per 16 draws with the 16 lanes of a row all
-//     computing the SAME block.  Draw k reads word k & 3 of lane (k >> 2) & 63; refill when k & 255 == 0.
-//   AHMC_DRAWS_PER_LANE 0 (rounds 3–6, for A/B runs): the four 16-lane rows compute four consecutive blocks, refill when k & 15 == 0.
-//   AHMC_DRAW_SCALAR_WORD 0 (default): the draw's word is selected per lane first (three v_cndmask), then read.  1 (round 7, measured
-//     and NOT taken): k is wave-uniform, so which of the block's four registers a draw reads can be a scalar branch around the
-//     v_readlane — three VALU fewer per draw, and slower: cfg2 2.966e9 against 3.004e9 leapfrog/s with the selects.  The selects are
-//     issue slots the other waves fill; the branch (readfirstlane -> s_cmp -> s_cbranch -> v_readlane) is latency on the chain of
-//     dependent stages every draw sits on (profiles/r7_experiments.md r7d).
-#ifndef AHMC_DRAWS_PER_LANE
-#define AHMC_DRAWS_PER_LANE 1
-#endif
-#ifndef AHMC_DRAW_SCALAR_WORD
-#define AHMC_DRAW_SCALAR_WORD 0
-#endif
+//   Lane ℓ computes block base + ℓ (round 7), so one Philox evaluation (≈ 85 VALU) serves 256 draws — one evaluation for every tree
+//     below 255 draws.  Draw k reads word k & 3 of lane (k >> 2) & 63; refill when k & 255 == 0.
+//   The draw's word is selected per lane first (three v_cndmask), then read.  (Round 7, measured and NOT taken: k is wave-uniform, so
+//     which of the block's four registers a draw reads can be a scalar branch around the v_readlane — three VALU fewer per draw, and
+//     slower: cfg2 2.966e9 against 3.004e9 leapfrog/s with the selects.  The selects are issue slots the other waves fill; the branch
+//     (readfirstlane -> s_cmp -> s_cbranch -> v_readlane) is latency on the chain of dependent stages every draw sits on: DESIGN.md §9,
+//     profiles/r7_experiments.md r7d.)
 template <bool WIDE>
 struct DrawStreamT {
-  static constexpr uint32_t PERIOD = !WIDE ? 4u : (AHMC_DRAWS_PER_LANE ? 256u : 16u);  // draws per refill
+  static constexpr uint32_t PERIOD = !WIDE ? 4u : 256u;  // draws per refill
   Rng rng;
   uint32_t k;
   Philox4 blk;
   __device__ __forceinline__ uint32_t lane_block() const {  // which of the refill's blocks this lane computes
     if constexpr (!WIDE) return 0u;
-    else if constexpr (AHMC_DRAWS_PER_LANE) return threadIdx.x & 63u;
-    else return (threadIdx.x & 63u) >> 4;
+    else return threadIdx.x & 63u;
   }
   __device__ __forceinline__ void init(const Rng& r) { rng = r; k = 0; }
   __device__ __forceinline__ void resume(const Rng& r, uint32_t k0) {  // continue a stream at draw k0
@@ -297,27 +249,12 @@ struct DrawStreamT {
   }
   __device__ __forceinline__ uint32_t word() {
     if ((k & (PERIOD - 1u)) == 0u) blk = rng.raw(RNG_TRANSITION, (k >> 2) + lane_block());
-    uint32_t w;
-    if constexpr (WIDE && AHMC_DRAW_SCALAR_WORD) {
-      w = 0;
-    } else {
-      const uint32_t lo = (k & 1u) ? blk.v[1] : blk.v[0], hi = (k & 1u) ? blk.v[3] : blk.v[2];
-      w = (k & 2u) ? hi : lo;
-    }
+    const uint32_t lo = (k & 1u) ? blk.v[1] : blk.v[0], hi = (k & 1u) ? blk.v[3] : blk.v[2];
+    uint32_t w = (k & 2u) ? hi : lo;
     if constexpr (WIDE) {
       const uint32_t ks = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);  // k is the same in every lane of the chain
-      const int src = AHMC_DRAWS_PER_LANE ? (int)((ks >> 2) & 63u) : (int)(((ks >> 2) & 3u) * 16u);
-      if constexpr (AHMC_DRAW_SCALAR_WORD) {
-        // (the empty asm keeps the four arms a scalar branch: merged, they are four v_readlane and a scalar select)
-        switch (ks & 3u) {
-          case 0u: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[0], src); asm volatile(""); break;
-          case 1u: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[1], src); asm volatile(""); break;
-          case 2u: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[2], src); asm volatile(""); break;
-          default: w = (uint32_t)__builtin_amdgcn_readlane((int)blk.v[3], src); asm volatile(""); break;
-        }
-      } else {
-        w = (uint32_t)__builtin_amdgcn_readlane((int)w, src);
-      }
+      const int src = (int)((ks >> 2) & 63u);
+      w = (uint32_t)__builtin_amdgcn_readlane((int)w, src);
     }
     ++k;
     return w;
@@ -349,7 +286,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   // A chain that owns whole waves makes every per-chain predicate wave-uniform; saying so (a ballot is uniform by
   // construction) turns the exec-mask save/restore of divergent branches into scalar branches and keeps the
   // predicates in SGPRs instead of VGPR 0/1 values.
-#if AHMC_TAIL_NORMALS
   // Before anything of a chain is live: a wave behind the last chunk makes its rows of the NEXT launch's normals and is done.  It writes a
   // buffer that no wave of this launch reads, and the launch that reads it is ordered behind this one on the stream: nothing to synchronise.
   if constexpr (G == 64 && (MODE == 0 || MODE == 3)) {
@@ -362,16 +298,11 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
       return;
     }
   }
-#endif
 #define AHMC_UNI(b) (CPW == 1 ? (__builtin_amdgcn_ballot_w64(b) != 0) : (b))
   // any lane of the wave?  For a chain that owns the wave the predicate is already wave-uniform (built from AHMC_UNI values):
   // testing it directly is a scalar branch, a ballot of it would re-materialise the lane mask (v_cndmask + v_cmp).
   // Measured (round 3, cfg2, A/B on one box, two runs each): whole loop 2.36e9 -> 2.43e9, warm-up 1.97e9 -> 2.06e9.
-#if AHMC_SCALAR_ANY
 #define AHMC_ANY(b) (CPW == 1 ? (bool)(b) : (__builtin_amdgcn_ballot_w64(b) != 0))
-#else
-#define AHMC_ANY(b) (__builtin_amdgcn_ballot_w64(b) != 0)
-#endif
   constexpr int NCH = Chunking<T, E>::NCH, CH = Chunking<T, E>::CH;
   constexpr int SLOT_ELEMS = NCH * 64 * CH;  // elements per vector slot (= 64 * E)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -391,11 +322,11 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   constexpr bool ADAPT = MODE >= 3;  // MODE 0 / 1 + adapt!(…) after every transition, inside the kernel (AdaptK)
   // Round 7: a chain that owns ONE wave takes the generalised U-turn decision as a scalar predicate straight from the reduction
   // (ahmc_device.hpp: wave64_any_le0_pair).  G < 64 needs it per lane, G > 64 needs the sums themselves for the cross-wave exchange.
-  constexpr bool UTURN_ANY = G == 64 && AHMC_UTURN_ANY != 0;
-  // two leaves per step (AHMC_LEAF_PAIR above).  Its reduction is the DPP butterfly's and its statistics are the running ones: the
-  // experimental reductions and the per-level statistics keep the single-leaf loop.
-  constexpr bool PAIR = AHMC_LEAF_PAIR != 0 && G == 64 && !GENERAL && UTURN_ANY && !AHMC_MFMA_REDUCE && (AHMC_DS_REDUCE & 3) == 0 &&
-                        AHMC_RUNNING_STATS != 0;
+  constexpr bool UTURN_ANY = G == 64;
+  // two leaves per step (the pair step above).  Its reduction is the DPP butterfly's: the experimental reductions keep the single-leaf
+  // loop, and so do the measurement builds, whose stage stamps describe it.
+  constexpr bool PAIR = G == 64 && !GENERAL && UTURN_ANY && !AHMC_MFMA_REDUCE && (AHMC_DS_REDUCE & 3) == 0 &&
+                        !AHMC_LEAF_PROF && !AHMC_WAVE_TIMELINE;
   const bool strict = GENERAL && p.criterion == 2;
   const int NV = strict ? 3 : 2;  // vectors per pending level: A, RF (, RL)
   const int n_slots = NV * NLEV + NUTS_DORMANT + NUTS_CKPT;
@@ -420,13 +351,12 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #define A_DAM sAI[0 * CPW + gi]
 #define A_WVN sAI[1 * CPW + gi]
 #define A_CHK sAI[2 * CPW + gi]   // the checkpoint of the re-integration: touched at the top of a doubling only, so it lives in LDS, not in a register
+  // (rows 1, 2 of sT and row 0 of sI — the per-level Σα, ΔH_max and nα of the statistics carried through every merge — are unused: the
+  // statistics are running values now; the rows remain because NUTS_NSC / NUTS_NSI size the LDS carve-up, ahmc_kernels.hpp)
 #define S_W(lvl) sT[((0) * NLEV + (lvl)) * CPW + gi]
-#define S_SA(lvl) sT[((1) * NLEV + (lvl)) * CPW + gi]
-#define S_DH(lvl) sT[((2) * NLEV + (lvl)) * CPW + gi]
-#define S_NA(lvl) sI[((0) * NLEV + (lvl)) * CPW + gi]
 #define S_CK(lvl) sI[((1) * NLEV + (lvl)) * CPW + gi]
-  // one chain per wave: the chain index and the kernel's argument fields on the scalar side (AHMC_TRANS_SCALAR above)
-  constexpr bool TSC = AHMC_TRANS_SCALAR != 0 && G == 64 && !GENERAL;
+  // one chain per wave: the chain index and the kernel's argument fields on the scalar side ("once per transition" above)
+  constexpr bool TSC = G == 64 && !GENERAL;
   const int64_t wave_slot = (int64_t)blockIdx.x * nwaves + wib;
   Slots<T, E> sl;
   sl.lds = (AHMC_AS_LDS T*)lds_vec;
@@ -589,7 +519,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
     }
     bool cur_is_left = false;
     int pos_cur = 0, pos_oth = 0;  // leaf index (signed distance from z0) of the two edges
-#if AHMC_CKPT
     // Checkpoint of the re-integration (round 5).  The candidate is carried as a leaf index and re-integrated at the end — from z0 that
     // is ≈ 0.5 leapfrogs per leaf step (0.37 / 0.51 / 0.48 measured on cfg2 / cfg3 / cfg5: 9 / 14 / 18 % of a leaf step's cycles).  The state
     // of the EDGE a doubling grows from is in registers when the doubling starts, and every leaf of that doubling lies beyond it: saved
@@ -598,21 +527,14 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
     // chk = (position << 1) | triple of the COMMITTED checkpoint (position 0: none, replay from z0); a doubling saves into the other triple.
     // (not in the Float32 warm-up kernels: with it the register allocator parks a spill under a narrowed exec mask in k_nuts<float,32,4,3,·> and
     // <float,16|32,2,3,·>, which isa_check refuses; the replay there starts at z0 as before — same results either way)
-#ifndef AHMC_CKPT_MIN_JW
-#define AHMC_CKPT_MIN_JW 2
-#endif
-    constexpr int CKPT_MIN_JW = AHMC_CKPT_MIN_JW;   // subtrees of 4 leaves and more
+    constexpr int CKPT_MIN_JW = 2;   // subtrees of 4 leaves and more
     // … and not where ONE chain fills ONE wave (G = 64: cfg2's (64,2), and (64,4), (64,8)): those kernels are bound by VALU issue at their
     // register caps, the replay is ≈ 3 % of their instructions, and the checkpoint's extra live value costs them spilled registers — measured
     // with / without: (64,2) 2.851e9 / 2.881e9, (64,4) at D = 256 1.587e9 / 1.603e9, (64,8) at D = 512 7.78e8 / 8.08e8 leapfrog/s.  The chains
     // that share a wave (cfg3 +7 %) and the multi-wave chains (cfg5 +6.7 %) are bound by the latency of their dependent stages, where half
     // the replay is half the time (profiles/r5_experiments.md r5i, r5j).
-    constexpr bool CKPT = !(sizeof(T) == 4 && ADAPT) && (G != 64 || AHMC_CKPT_G64);
+    constexpr bool CKPT = !(sizeof(T) == 4 && ADAPT) && G != 64;
     if constexpr (CKPT) A_CHK = 0;
-#else
-    constexpr int CKPT_MIN_JW = 2;
-    constexpr bool CKPT = false;
-#endif
     bool numerical = false;
     bool redo = false;  // LINW only: a weight came too close to overflow
     int depth = 0;
@@ -680,8 +602,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
         tl_steps += 1;
         tl_alive += (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(alive && lane == 0));
 #endif
-        int merged = 0;
-        // pair step (AHMC_LEAF_PAIR): from the second doubling on an iteration builds the odd leaf `leaf` AND the even leaf behind it with
+        // pair step (PAIR): from the second doubling on an iteration builds the odd leaf `leaf` AND the even leaf behind it with
         // their level-0 merge; `leaf` is the even one from here on — its trailing zero bits are the merges that follow
         bool pair = false;
         if constexpr (PAIR) {
@@ -706,12 +627,12 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
               dots[0] += A_c[e] * (minv[e] * r_a[e]);
               dots[1] += A_c[e] * (minv[e] * cur.r[e]);
             }
-#if AHMC_PAIR_LANE_STATS
             // The reduction hands back its transposed register, and what the two leaves' scalar work computes that does not depend on
             // their order — sanitised energy, ΔH, ℓw, the weight's exp, min(1, W), the redo and divergence compares — runs ONCE, leaf a in
-            // the even lanes and leaf b in the odd ones (ahmc_device.hpp: pair_leaf_stats, the TWIN of leaf_stats below): one exp chain
-            // with its scalar table load on the leaf loop's chain of dependent stages instead of two back to back.  What depends on the
-            // order is applied here, in leaf_stats' order; if leaf a diverges nothing of leaf b is applied, its redo bit included.
+            // the even lanes and leaf b in the odd ones (ahmc_device.hpp: pair_leaf_stats, the TWIN of the single-leaf arm's scalar block
+            // below): one exp chain with its scalar table load on the leaf loop's chain of dependent stages instead of two back to back.
+            // What depends on the order is applied here, in the single-leaf arm's order; if leaf a diverges nothing of leaf b is applied,
+            // its redo bit included.
             T z_t;
             const bool turn_ab = wave64_pair_reduce_t(dots[0], dots[1], ea, eb, z_t);
             PairLeafStats<T> ps;
@@ -725,58 +646,14 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
               numerical = numerical || sub_term;
               sa_c = sa_c + ps.sa[i];
               na_c = na_c + 1;
-              if constexpr (AHMC_LEAF_MICRO) {
-                if (v > 0) { dh_c = maxabs(dh_c, ps.dH[i]); asm volatile(""); }
-                else { dh_c = maxabs(ps.dH[i], dh_c); asm volatile(""); }
-              } else {
-                dh_c = v > 0 ? maxabs(dh_c, ps.dH[i]) : maxabs(ps.dH[i], dh_c);
-              }
+              if (v > 0) { dh_c = maxabs(dh_c, ps.dH[i]); asm volatile(""); }
+              else { dh_c = maxabs(ps.dH[i], dh_c); asm volatile(""); }
             };
             leaf_apply(0);
             if (!sub_term) {
               const T w_p = w_c;
               const int ck_p = ck_c;
               leaf_apply(1);
-#else
-            const bool turn_ab = wave64_pair_reduce(dots[0], dots[1], ea, eb);
-            // a leaf's scalar work — weight, divergence test, running statistics, candidate = this leaf: the lines of the single-leaf
-            // form below that a fast kernel whose chain owns the wave executes, in their order.
-            // TWIN of the block from `pos_cur += v;` to the running statistics in the single-leaf arm below ("TWIN of leaf_stats"): a change to
-            // the leaf's scalar work is made in BOTH, or the first doubling's leaf (single-leaf arm) and the later ones (here) stop
-            // agreeing bit for bit — tests/test_leaf_pairs.py's fixture is what notices.  They are two texts, not one lambda, because with the
-            // single-leaf arm compiled through a shared lambda the -DAHMC_LEAF_PAIR=0 build no longer had the parent's device code (ahmc_device.hpp:
-            // leapfrog_step_ne_partial).  (-DAHMC_PAIR_LANE_STATS=0 only: the arm above does this work through its TWIN pair_leaf_stats.)
-            auto leaf_stats = [&](const T ne) {
-              pos_cur += v;
-              const T dH = -ne - H0;
-              T sa_leaf = 0;
-              if constexpr (!LINW) sa_leaf = alpha_from_logweight<T, true>(H0 + ne);
-              ck_c = pos_cur;
-              if constexpr (LINW) {
-                const T lw = H0 + ne;
-                w_c = leaf_weight_exp<true>(lw);
-                sa_leaf = w_c >= T(1) ? T(1) : w_c;
-                redo = redo || AHMC_UNI(lw > (sizeof(T) == 4 ? T(60) : T(LINW_LIMIT)));
-              } else {
-                w_c = H0 + ne;
-              }
-              sub_term = AHMC_UNI(!(-H0 < p.delta_max + ne));
-              numerical = numerical || sub_term;
-              sa_c = sa_c + sa_leaf;
-              na_c = na_c + 1;
-              if constexpr (AHMC_LEAF_MICRO) {
-                if (v > 0) { dh_c = maxabs(dh_c, dH); asm volatile(""); }
-                else { dh_c = maxabs(dH, dh_c); asm volatile(""); }
-              } else {
-                dh_c = v > 0 ? maxabs(dh_c, dH) : maxabs(dH, dh_c);
-              }
-            };
-            leaf_stats(neg_energy_sanitized(ea));
-            if (!sub_term) {
-              const T w_p = w_c;
-              const int ck_p = ck_c;
-              leaf_stats(neg_energy_sanitized(eb));
-#endif
               if (!sub_term) {
                 // the level-0 merge: combine(rng, sampler′, sampler′′) and the U-turn test of the pair, as merge_level does them
                 T w_new;
@@ -787,7 +664,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
                 w_c = w_new;
                 sub_term = turn_ab;
                 copy_vec(RF_c, r_a);
-                merged = 1;
                 AHMC_LP_COUNT(9, 1)
               }
             }
@@ -811,7 +687,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
                 s0 += A_c[e] * (minv[e] * RF_m0[e]);
                 s1 += A_c[e] * (minv[e] * cur.r[e]);
               }
-            }, AHMC_HIER_PRE && leaf > 1);
+            }, leaf > 1);
           } else if constexpr (G > 64) {
             // multi-wave chains keep the (ℓπ, ℓκ) pair reduction.  Round 2: with the single-value form the (128,8) instantiation
             // returned wrong candidates — a register-allocation artefact (a spill stored under the lane-0 mask of the cross-wave
@@ -820,7 +696,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
             // 5.36e7) — more scratch traffic in the leaf loop than the barrier pair it saves.  Not taken.
             // (round 6: from the second leaf of a doubling on, μ and log τ of the new position were published by the leaf before — no
             // broadcast exchange of their own)
-            leapfrog_step<T, G, E, TK, false>(cur, minv, v > 0 ? eps : -eps, p.tp, p.lf, lane, d0, 1, 1, AHMC_HIER_PRE && leaf > 1);
+            leapfrog_step<T, G, E, TK, false>(cur, minv, v > 0 ? eps : -eps, p.tp, p.lf, lane, d0, 1, 1, leaf > 1);
             ne_leaf = cur.lp + cur.lk;
           } else {
 #if AHMC_LEAF_PROF
@@ -849,7 +725,9 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #if AHMC_LEAF_PROF
           if (GENERAL || G > 64) AHMC_LP_TICK(0)   // (the other leaf forms: the whole leapfrog incl. its reduction under [0])
 #endif
-          // (TWIN of leaf_stats in the pair step above: from here to the running statistics, the fast kernels' lines are repeated there — change both)
+          // (TWIN of pair_leaf_stats, ahmc_device.hpp, and of leaf_apply in the pair step above: from here to the running statistics, the lines
+          // a fast kernel whose chain owns the wave executes are repeated there — change both, or the first doubling's leaf (this arm)
+          // and the later ones (the pair step) stop agreeing bit for bit: tests/test_leaf_pairs.py's fixture is what notices)
           pos_cur += v;
           const T ne = (GENERAL || (FUSE_M0 && nm > 0)) ? cur.lp + cur.lk : ne_leaf;  // neg_energy(z′)
           const T dH = -ne - H0;
@@ -881,23 +759,21 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
             sub_term = AHMC_UNI(!(-H0 < p.delta_max + ne));  // Termination(::MultinomialTS, ...) (:503-507)
           }
           numerical = numerical || sub_term;
-#if AHMC_RUNNING_STATS
-          sa_c = sa_c + sa_leaf;                                     // over the leaves of this doubling, in build order
+          // Σα, nα and ΔH_max of the subtree a doubling builds are RUNNING values over its leaves in build order — the statistics the
+          // reference carries through every `combine` (src/trajectory.jl:533-542) are a sum, a count and a maximum of |·| over the same
+          // leaves, so only the order of the additions changes (acceptance_rate in the last bit; no decision depends on it): no per-level
+          // Σα / nα / ΔH_max in LDS, nothing to fold in at a merge, at a park or when a subtree ends early.
+          sa_c = sa_c + sa_leaf;
           na_c = na_c + 1;
           // v > 0 ? maxabs(dh_c, dH) : maxabs(dH, dh_c) (maxabs keeps the right-hand one on a tie, :526).  As a select between the two calls
           // the compiler evaluated both (two compares, six v_cndmask per leaf: round 5's census of the leaf loop); a chain that owns its wave
           // has a wave-uniform direction, so it is a scalar branch around ONE of them (the empty asm keeps it a branch).
-          if constexpr (CPW == 1 && AHMC_LEAF_MICRO) {
+          if constexpr (CPW == 1) {
             if (v > 0) { dh_c = maxabs(dh_c, dH); asm volatile(""); }
             else { dh_c = maxabs(dH, dh_c); asm volatile(""); }
           } else {
             dh_c = v > 0 ? maxabs(dh_c, dH) : maxabs(dH, dh_c);
           }
-#else
-          sa_c = sa_leaf;
-          na_c = 1;
-          dh_c = dH;
-#endif
           // a one-leaf subtree has ρ = r (Classic: θ) and first-built r = r of this leaf.  The general kernel copies
           // them into A_c / RF_c here; the fast kernels read cur.r in their place until the first merge (below)
           if constexpr (GENERAL) {
@@ -928,13 +804,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
             }
             if (keep_first) ck_c = S_CK(lvl);
             w_c = w_new;
-            // combine(treeleft, treeright) (:533-542); position order matters for maxabs only
-#if !AHMC_RUNNING_STATS
-            sa_c = S_SA(lvl) + sa_c;
-            na_c = S_NA(lvl) + na_c;
-            const T dh_p = S_DH(lvl);
-            dh_c = v > 0 ? maxabs(dh_p, dh_c) : maxabs(dh_c, dh_p);
-#endif
+            // (combine(treeleft, treeright) (:533-542): the statistics are running values — nothing to fold in here)
             // isterminated(tc, h, tree′, tleft, tright) on the merged subtree (:551-617)
             if (classic) {
               // ends: first-built leaf (A_p, RF_p) and the current leaf; Δθ = θ_right − θ_left
@@ -996,7 +866,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
               sub_term = (dots[0] <= 0) || (dots[1] <= 0) || (dots[2] <= 0) || (dots[3] <= 0) || (dots[4] <= 0) || (dots[5] <= 0);
             }
             if constexpr (pre.value) copy_vec(RF_c, RF_m0); else copy_vec(RF_c, RF_p);
-            merged = lvl + 1;
             AHMC_LP_COUNT(9, 1)
           }
         };
@@ -1026,19 +895,8 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
         }
         AHMC_LP_TICK(3)
         if (alive && sub_term) {
-          // enclosing unfinished subtrees still absorb the statistics of their first halves
-          // (tree′ = combine(treeleft, treeright) at every level that is a second half, :666)
-#if !AHMC_RUNNING_STATS
-          const uint32_t pend = ((leaf - 1u) >> merged) << merged;
-          for (int q = merged; (pend >> q) != 0u; ++q) {
-            if ((pend >> q) & 1u) {
-              sa_c = S_SA(q) + sa_c;
-              na_c = S_NA(q) + na_c;
-              const T dh_p = S_DH(q);
-              dh_c = v > 0 ? maxabs(dh_p, dh_c) : maxabs(dh_c, dh_p);
-            }
-          }
-#endif
+          // (the statistics of the enclosing unfinished subtrees' first halves — tree′ = combine(treeleft, treeright) at every level that
+          // is a second half, :666 — are in the running values already)
           alive = false;
         } else if (alive && leaf < nleaf) {
           // park the finished level-nm subtree until its sibling is built
@@ -1050,11 +908,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           }
           if (strict) sl.store(NV * nm + 2, cur.r);  // r of its last-built leaf
           S_W(nm) = w_c;
-#if !AHMC_RUNNING_STATS
-          S_SA(nm) = sa_c;
-          S_DH(nm) = dh_c;
-          S_NA(nm) = na_c;
-#endif
           S_CK(nm) = ck_c;
         }
         AHMC_LP_TICK(4)
@@ -1236,7 +1089,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
         if (PE.samples_out) store_vec<T, E, TSC>(zc.th, PE.samples_out + (int64_t)kt * PE.D * PE.N, ce * PE.D, d0, PE.D);
         copy_vec(th_cur, zc.th);
         if constexpr (ADAPT) {
-#if AHMC_ADAPT_REREAD
           // The adaptor's argument block is read HERE, once per transition, through a pointer the optimiser cannot see through: its
           // fourteen array pointers and its schedule are loop-invariant, were hoisted out of the transition loop and — with the
           // scalar registers full — lived in per-lane registers that were spilled to scratch and reloaded in every epilogue.
@@ -1245,7 +1097,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           // without it the allocator parks a spill under a narrowed exec mask in k_nuts<float,32,4,4,1>, which isa_check refuses.)
           const AdaptK<T>* ak = ak0;
           if constexpr (!TSC) asm volatile("" : "+s"(ak));
-#endif
           // (one chain per wave: the block's address comes from the re-read arguments — opaque already — and it is read as constant memory)
 #define AK adapt_block_at<TSC>(ak, pe_)
           // adapt!(h, κ, adaptor, i, n_adapts, z, α) + update(h/κ, adaptor) (src/sampler.jl:72-90, :3-22) for this chain —
@@ -1338,9 +1189,6 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
     if (active) save_adapt_state();
   }
 #undef S_W
-#undef S_SA
-#undef S_DH
-#undef S_NA
 #undef S_CK
 #undef A_EPSNOM
 #undef A_DAEPS

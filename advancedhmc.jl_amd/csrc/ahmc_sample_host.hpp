@@ -85,11 +85,11 @@ inline size_t normals_prefetch_max_bytes() {
   return getenv("AHMC_NORMALS_PREFETCH_MAX_MB") ? (size_t)atoll(getenv("AHMC_NORMALS_PREFETCH_MAX_MB")) << 20 : (size_t)2 << 30;
 }
 // does a launch whose successor has `hint` transitions make that successor's normals in its own tail?  (k_nuts, G = 64, MODE 0 / 3:
-// AHMC_TAIL_NORMALS in ahmc_kernels.hpp.)  Mode 1 takes exactly the launches the second stream declines for their size.
+// "tail normals" in ahmc_kernels.hpp.)  Mode 1 takes exactly the launches the second stream declines for their size.
 template <class T>
 bool tail_normals_applies(const Ctx<T>* c, int64_t hint, double refresh_alpha) {
   const int mode = normals_tail_mode();
-  if (!AHMC_TAIL_NORMALS || mode == 0 || c->norm_tail == 0 || c->G != 64 || hint <= 0 || refresh_alpha != 0) return false;
+  if (mode == 0 || c->norm_tail == 0 || c->G != 64 || hint <= 0 || refresh_alpha != 0) return false;
   if (mode == 2) return true;
   if (getenv("AHMC_NORMALS_PREFETCH") && atoi(getenv("AHMC_NORMALS_PREFETCH")) == 0) return false;
   return (size_t)hint * (size_t)c->D * (size_t)c->N * sizeof(T) > normals_prefetch_max_bytes();
@@ -108,7 +108,6 @@ int tail_normals_plan(Ctx<T>* c, KP<T>& p, int64_t hint, int n_trans) {
   if (c->norm_tail != 1 || !c->znorm2 || need2 > c->znorm2_elems) return AHMC_OK;
   // a k_normals of the second stream may still be writing the buffer (its launch was never consumed): behind it
   if (c->z2_norm_stream_busy) { HIPCHK(hipStreamWaitEvent(c->stream, c->ev_norm_ready, 0)); c->z2_norm_stream_busy = false; }
-#if AHMC_TAIL_NORMALS
   const int rows_env = getenv("AHMC_NORMALS_TAIL_ROWS") ? atoi(getenv("AHMC_NORMALS_TAIL_ROWS")) : 0;
   const int64_t rows = hint * c->N, per_wave = rows_env > 0 ? rows_env : 64;
   p.tail_out = c->znorm2;
@@ -116,16 +115,11 @@ int tail_normals_plan(Ctx<T>* c, KP<T>& p, int64_t hint, int n_trans) {
   p.tail_iteration = (uint32_t)(c->iteration + (uint64_t)n_trans);
   p.tail_rows = (int)per_wave;
   p.tail_waves = (unsigned int)((rows + per_wave - 1) / per_wave);
-#endif
   return AHMC_OK;
 }
 template <class T>
 bool tail_normals_planned(const KP<T>& p) {
-#if AHMC_TAIL_NORMALS
   return p.tail_waves != 0;
-#else
-  return false;
-#endif
 }
 // after that launch: what the second buffer will hold, and that the stream is still writing it (a later k_normals of the second stream waits)
 template <class T>
@@ -134,9 +128,7 @@ int tail_normals_done(Ctx<T>* c, const KP<T>& p) {
   c->z2_has_reader = true;
   c->npre.valid = true;
   c->npre.in_tail = true;
-#if AHMC_TAIL_NORMALS
   c->npre.iter = c->iteration; c->npre.n = p.tail_n_trans;
-#endif
   c->npre.k0 = (uint64_t)p.k0; c->npre.k1 = (uint64_t)p.k1; c->npre.chain_offset = (uint64_t)p.chain_offset; c->npre.chain_stride = (uint64_t)p.chain_stride;
   return AHMC_OK;
 }

@@ -1,7 +1,7 @@
 // pair_stats.hip — the scalar work of the two leaves of a pair step of k_nuts in its two forms, on the same data
 // (tests/test_pair_lane_stats.py).  Compiled with the engine's own flags (build.build_probe_object) and loaded through hipModuleLoad.
 //
-// serial form (-DAHMC_PAIR_LANE_STATS=0 in the engine): wave64_pair_reduce, then the lines of k_nuts' leaf_stats on each of the two broadcast
+// serial form (the engine's until round 10; it lives on here): wave64_pair_reduce, then the lines of the scalar block of k_nuts' single-leaf arm on each of the two broadcast
 //   energies, one after the other — BOTH leaves always (the engine drops leaf b when leaf a diverges; the probe compares what is computed);
 // lane-parallel form: wave64_pair_reduce_t, then pair_leaf_stats (ahmc_device.hpp).
 //

@@ -1,11 +1,14 @@
 #!/usr/bin/env python
 """Record tests/golden/leaf_pair_single_loop.npz: the chains of tests/test_leaf_pairs.py as the SINGLE-LEAF loop of k_nuts builds them.
 
-    python scripts/build_variant.py pair0 -DAHMC_LEAF_PAIR=0
-    AHMC_HIP_LIB=advancedhmc.jl_amd/csrc/variants/libahmc_hip_pair0.so python tests/golden/make_leaf_pair_golden.py [OUT.npz]
+The committed fixture was recorded at or before commit 9712c5e, the last one whose engine could still be built with the single-leaf loop
+everywhere (a build-time switch, since retired: DESIGN.md §9).  Regenerating it means building THAT commit:
+
+    git checkout 9712c5e && python scripts/build_variant.py pair0 -DAHMC_LEAF_PAIR=0     # in a checkout of its own
+    AHMC_HIP_LIB=<that checkout>/advancedhmc.jl_amd/csrc/variants/libahmc_hip_pair0.so python tests/golden/make_leaf_pair_golden.py [OUT.npz]
 
 The fixture is recorded from whichever HIP library AHMC_HIP_LIB names (needs the MI355X), so a later toolchain can regenerate it.  The
-shipped library (-DAHMC_LEAF_PAIR=1: two leaves per step where a chain owns a wave) has to reproduce it bit for bit.
+shipped library (two leaves per step where a chain owns a wave) has to reproduce it bit for bit.
 
 What is recorded, per case and per transition, for every chain: n_steps, acceptance_rate, numerical_error, tree_depth, step_size, the
 largest energy error of the tree (ΔH_max, signed: below −600 the chain went through the log-domain redo kernel) and θ —

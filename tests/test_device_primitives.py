@@ -294,7 +294,7 @@ def exp_args():
 
 @pytest.mark.gpu
 def test_table_exp_accuracy(probe, exp_args):
-    """A. leaf_weight_exp<true> (the table form, AHMC_LEAF_EXP 2) against the exact exp."""
+    """A. leaf_weight_exp<true> (the table form) against the exact exp."""
     x = exp_args
     y = _run1(probe, "p_exp_table_uniform", x, np.float64)
     fin = np.isfinite(x)

@@ -1,9 +1,10 @@
-"""The pair step of k_nuts (csrc/ahmc_nuts.hpp: AHMC_LEAF_PAIR — two leaves per step where a chain owns a wave).
+"""The pair step of k_nuts (csrc/ahmc_nuts.hpp: PAIR — two leaves per step where a chain owns a wave).
 
 a. its one reduction, wave64_pair_reduce, alone in tests/device_probe/pair_red.hip next to the primitives it replaces, on the same data:
    each energy with the bits of wave_allsum<64, T, 1>, the U-turn decision of wave64_any_le0_pair;
-b. the shipped library reproduces, bit for bit, tests/golden/leaf_pair_single_loop.npz — the same chains recorded from the
-   -DAHMC_LEAF_PAIR=0 build of the same tree (tests/golden/make_leaf_pair_golden.py: the cases, and how to regenerate it);
+b. the shipped library reproduces, bit for bit, tests/golden/leaf_pair_single_loop.npz — the same chains recorded from a build with
+   the single-leaf loop everywhere.  That was a build-time switch of the engine, since retired: the fixture was recorded at or before
+   commit 9712c5e, and regenerating it means building that commit (tests/golden/make_leaf_pair_golden.py: the cases, and how);
 c. the same configurations against the CPU oracle under the margin rule of tests/parity_util.py: the pair step is held to the
    reference, not only to its predecessor.
 """

@@ -1,5 +1,5 @@
-"""The lane-parallel scalar work of a pair step of k_nuts (csrc/ahmc_device.hpp: wave64_pair_reduce_t + pair_leaf_stats,
-AHMC_PAIR_LANE_STATS) against the serial form it replaces (wave64_pair_reduce, then k_nuts' leaf_stats on each broadcast energy), on the
+"""The lane-parallel scalar work of a pair step of k_nuts (csrc/ahmc_device.hpp: wave64_pair_reduce_t + pair_leaf_stats)
+against the serial form it replaced (wave64_pair_reduce, then the scalar block of k_nuts' single-leaf arm on each broadcast energy), on the
 same data in tests/device_probe/pair_stats.hip: equal BITS for w, sa and ΔH of both leaves, equal redo and divergence flags, for the
 linear-domain (LINW) and the log-domain kernels' expressions, f64 and f32.
 

@@ -1,4 +1,4 @@
-"""The once-per-transition code of k_nuts where one chain owns one wave (G = 64; AHMC_TRANS_SCALAR, csrc/ahmc_nuts.hpp): the chain index
+"""The once-per-transition code of k_nuts where one chain owns one wave (G = 64; TSC in k_nuts, csrc/ahmc_nuts.hpp): the chain index
 lives in scalar registers, per-chain addresses are a 64-bit scalar base plus the lane's 32-bit byte offset
 (load_vec / store_vec <…, SB>, csrc/ahmc_device.hpp), and the kernel-argument fields of the prologue and the epilogue are read where
 they are used.  None of it touches an arithmetic expression, so everything here is BIT FOR BIT: the fused launches (several transitions
