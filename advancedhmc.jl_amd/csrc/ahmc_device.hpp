@@ -184,7 +184,7 @@ static __device__ const unsigned long long EXP2_64_BITS[64] = {
 // the bench's occupancy) against 310 of 1 571 on cfg2, where the entry is a scalar load.  Those kernels evaluate the Horner-11 form
 // (no memory access: 9 more VALU, ≈ 700 fewer cycles).
 // (TWIN: leaf_weight_exp_pair below repeats the table form of this function, statement for statement, for two leaves in the two lane
-// parities of a wave — change both)
+// parities of a wave, and leaf_weight_exp_quad for four leaves in the four lanes of a quad — change all three)
 template <bool UNIFORM>
 __device__ __forceinline__ double leaf_weight_exp(double x) {
   constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
@@ -242,8 +242,8 @@ __device__ __forceinline__ T alpha_from_logweight(T lw) {
 // b's (pair_leaf_stats below), and lanes LA / LB are the ones whose results are read.  The two table entries are two scalar loads issued
 // together — their indices come from lanes LA / LB by v_readlane — and lane parity picks the entry; everything else is lane-local, so
 // each of the two lanes runs the instructions of leaf_weight_exp<true> on its own argument and returns its bits.
-// TWIN of the table form of leaf_weight_exp above, statement for statement: change both.  EVERY lane's argument must be a value whose
-// (int)dk is defined (the caller hands every lane one of the two leaves' arguments, so it is wherever leaf_weight_exp's own is).
+// TWIN of the table form of leaf_weight_exp above and of leaf_weight_exp_quad below, statement for statement: change all three.  EVERY lane's
+// argument must be a value whose (int)dk is defined (the caller hands every lane one of the two leaves' arguments, so it is wherever leaf_weight_exp's own is).
 template <int LA, int LB>
 __device__ __forceinline__ double leaf_weight_exp_pair(double x, bool odd) {
   constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
@@ -264,6 +264,35 @@ __device__ __forceinline__ double leaf_weight_exp_pair(double x, bool odd) {
 }
 template <int LA, int LB>
 __device__ __forceinline__ float leaf_weight_exp_pair(float x, bool) { return exp(x); }
+
+// The same for FOUR leaves (quad_leaf_stats below): leaf k's argument in the lanes with lane & 3 == k, lanes L0 .. L0 + 3 the ones whose
+// results are read.  The four table entries are four scalar loads issued together; lane & 3 picks the entry.
+// TWIN of the table form of leaf_weight_exp and of leaf_weight_exp_pair above, statement for statement: change all three.  The arguments of
+// lanes L0 .. L0 + 3 must be values whose (int)dk is defined, as there; the other lanes' results are never read, and quad_leaf_stats hands
+// eight of them dot-product sums (see there why that is left so).
+template <int L0>
+__device__ __forceinline__ double leaf_weight_exp_quad(double x, bool odd, bool up) {
+  constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
+  const double xc = x < -1100.0 ? -1100.0 : x;
+  const double dk = __builtin_rint(xc * 92.33248261689366);                // 64 / ln 2
+  double t = __builtin_fma(dk, -0x1.62e42fef00000p-7, xc);                  // − k·ln2/64: high part (20 trailing zero bits: exact product)
+  t = __builtin_fma(dk, -0x1.473de6af278edp-40, t);                         // low part
+  const int k = (int)dk;
+  const int k0 = __builtin_amdgcn_readlane(k, L0), k1 = __builtin_amdgcn_readlane(k, L0 + 1);
+  const int k2 = __builtin_amdgcn_readlane(k, L0 + 2), k3 = __builtin_amdgcn_readlane(k, L0 + 3);
+  const double tj0 = C(EXP2_64_BITS[k0 & 63]), tj1 = C(EXP2_64_BITS[k1 & 63]);
+  const double tj2 = C(EXP2_64_BITS[k2 & 63]), tj3 = C(EXP2_64_BITS[k3 & 63]);
+  const double tjl = odd ? tj1 : tj0, tjh = odd ? tj3 : tj2;
+  const double tj = up ? tjh : tjl;
+  double q = __builtin_fma(t, 8.3333333333333332e-03, 4.1666666666666664e-02);  // 1/120, 1/24
+  q = fma3(t, q, 1.6666666666666666e-01);
+  q = fma3(t, q, 0.5);
+  q = fma3(t, q, 1.0);
+  q = q * t;                                                                // e^t − 1
+  return __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
+}
+template <int L0>
+__device__ __forceinline__ float leaf_weight_exp_quad(float x, bool, bool) { return exp(x); }
 
 template <class T> __device__ __forceinline__ T maxabs(T a, T b) { return fabs(a) > fabs(b) ? a : b; }  // :526
 
@@ -498,7 +527,8 @@ __device__ __forceinline__ void wave_allsum4(T& a, T& b, T& c, T& d) {
 //     builds the other one as well).
 // f64: 14 + 7 + 3 + 3 + 5 + 5 + 1 + 4 = 42 VALU, against 22 + 22 + 27 for two leaves' wave_allsum and the merge's predicate.
 // (The engine calls only wave64_pair_reduce_t below.  This function stays because tests/device_probe/pair_red.hip and pair_stats.hip
-// call it: it is what they hold the transposed form to.  TWIN of wave64_pair_reduce_t up to `le0`: change both.)
+// call it: it is what they hold the transposed form to.  TWIN of wave64_pair_reduce_t up to `le0`, and of wave64_quad_reduce_t in what each
+// value goes through: change all.)
 #ifndef AHMC_PAIR_RED_QUAD
 #define AHMC_PAIR_RED_QUAD 1
 #endif
@@ -521,7 +551,8 @@ __device__ __forceinline__ bool wave64_pair_reduce(T da, T db, T& ea, T& eb) {
 // wave64_pair_reduce without the four row_newbcast moves: the same exchanges, additions and decision, and the TRANSPOSED register itself
 // comes back in z — lanes 0 / 1 of a row hold Σda / Σdb, lanes 4q + 2 / 4q + 3 hold Σea / Σeb (with the butterfly's bits in quads 1 and 3,
 // as above).  For pair_leaf_stats (below), which does both leaves' scalar work in the two lane parities instead of once per broadcast
-// value.  TWIN of wave64_pair_reduce up to `le0`: change both (tests/device_probe/pair_stats.hip runs them on the same data).
+// value.  TWIN of wave64_pair_reduce up to `le0`: change both (tests/device_probe/pair_stats.hip runs them on the same data); TWIN of
+// wave64_quad_reduce_t below in what each value goes through (tests/device_probe/quad_red.hip).
 template <class T>
 __device__ __forceinline__ bool wave64_pair_reduce_t(T da, T db, T ea, T eb, T& z) {
   const bool odd = (threadIdx.x & 1u) != 0, up = (threadIdx.x & 2u) != 0;
@@ -534,6 +565,45 @@ __device__ __forceinline__ bool wave64_pair_reduce_t(T da, T db, T ea, T eb, T& 
   z = xor32_sum(z);
   return (__builtin_amdgcn_ballot_w64(z <= T(0)) & 3ull) != 0ull;  // lane 0: Σda, lane 1: Σdb
 }
+
+// What FOUR consecutive NUTS leaves a, b, c, d, their two level-0 merges and the level-1 merge of the two pairs need from the wave, in ONE
+// reduction (the quad step of k_nuts): ten lane partials in — the four energies e[0..3], the dot products of the merges (a,b) and (c,d) and
+// those of the level-1 merge — and one register out.  All FOUR exchanges inside a 16-lane row are transposed (lane & 1, lane & 2, then
+// the quad's index bits lane & 4 and lane & 8), so a row of w holds
+//     lanes 0 / 1: Σdab[0] / Σdab[1]     lanes 2 / 3: Σdcd[0] / Σdcd[1]     lanes 4 .. 7: Σe[0] .. Σe[3]     lanes 8 / 9: Σdl[0] / Σdl[1]
+// and the three U-turn decisions are bits 0-1, 2-3 and 8-9 of ONE compare's lane mask (no sum is broadcast).  The bits are those of the
+// primitives this replaces.  Inside a quad every slot sums (own pair) + (other pair), whichever lane collects it.  Across the quads of a row
+// the rotations join (Qq + Qq−1) + (Qq−2 + Qq−3) in quad q (row_ror:n hands lane l the value of lane l − n, tests/device_probe/pair_red.hip):
+//   * quad 0 has wave_allsum2<64>'s (Q0 + Q3) + (Q2 + Q1) — where wave64_pair_reduce_t and wave64_any_le0_pair read their dot products;
+//     quad 2 has (Q2 + Q1) + (Q0 + Q3), the same two sums added in the other order: the same bits.  The dot products sit in quads 0 and 2;
+//   * quad 1 has the single-value butterfly's (Q1 + Q0) + (Q3 + Q2) — where wave64_pair_reduce_t keeps its energies.  The energies sit in quad 1.
+// The transposed rotation of a stage sends what the receiving quad collects, so a value's partner sums come from the quads the plain
+// rotation would have read.  Rows: xor16 / xor32 add {lower, upper} in the same order on both sides, as everywhere.
+// f64: 5 × 7 + (7 + 7 + 3) + (7 + 3) + 7 + 5 + 5 + 1 = 80 VALU, against 2 × 42 for two pair reductions and 27 for the level-1 merge's predicate.
+// TWIN of wave64_pair_reduce_t and wave64_any_le0_pair in what each value goes through: change all (tests/device_probe/quad_red.hip runs
+// them on the same data).
+// The FIRST exchange is a function of its own (wave64_quad_pair): it needs one pair of values only, so the quad step makes it as soon as
+// a pair's two partials exist and carries ONE register per pair, not two, across the leapfrogs that follow.
+template <class T>
+__device__ __forceinline__ T wave64_quad_pair(T a, T b) {
+  const bool odd = (threadIdx.x & 1u) != 0;
+  return (odd ? b : a) + dpp_mov<0xB1>(odd ? a : b);  // quad_perm [1,0,3,2]: even lanes collect a, odd lanes b
+}
+// xab, xcd, xl: wave64_quad_pair of the dot products of the merges (a,b), (c,d) and of the level-1 merge; yab, ycd: of (e_a, e_b), (e_c, e_d)
+template <class T>
+__device__ __forceinline__ unsigned long long wave64_quad_reduce_t(T xab, T xcd, T xl, T yab, T ycd, T& w) {
+  const bool up = (threadIdx.x & 2u) != 0, oq = (threadIdx.x & 4u) != 0, hq = (threadIdx.x & 8u) != 0;
+  const T rd = (up ? xcd : xab) + dpp_mov<0x4E>(up ? xab : xcd);               // quad_perm [2,3,0,1]
+  const T re = (up ? ycd : yab) + dpp_mov<0x4E>(up ? yab : ycd);
+  const T rl = xl + dpp_mov<0x4E>(xl);
+  const T z = (oq ? re : rd) + dpp_mov<0x124>(oq ? rd : re);                   // row_ror:4
+  const T zl = rl + dpp_mov<0x124>(rl);
+  w = (hq ? zl : z) + dpp_mov<0x128>(hq ? z : zl);                             // row_ror:8
+  w = xor16_sum(w);
+  w = xor32_sum(w);
+  return __builtin_amdgcn_ballot_w64(w <= T(0));
+}
+constexpr unsigned long long QUAD_TURN_AB = 0x3ull, QUAD_TURN_CD = 0xCull, QUAD_TURN_L1 = 0x300ull;  // lanes of the three decisions in that mask
 
 // all-reduce (sum) of K independent values across the G lanes of each group
 template <int G, class T, int K>
@@ -954,7 +1024,7 @@ __device__ __forceinline__ void leapfrog_step(Point<T, E>& z, const T (&minv)[E]
 // −Inf, src/hamiltonian.jl:95-104) is applied to the sum: sanitize(ℓπ) + sanitize(ℓκ) is −Inf exactly when either is
 // non-finite, and then ℓπ + ℓκ is non-finite too (the one exception, two finite values of ≈1e308 that overflow when
 // added, does not occur for a log-density).  Returns neg_energy; z.lp / z.lk are NOT updated.
-// (TWIN: leapfrog_step_ne_partial below repeats the vector work of this function for the pair step of k_nuts — change both)
+// (TWIN: leapfrog_step_ne_partial below repeats the vector work of this function for the pair step and the quad step of k_nuts — change both)
 template <class T, int G, int E, int TK>
 __device__ __forceinline__ T leapfrog_step_ne(Point<T, E>& z, const T (&minv)[E], T eps, const TargetP<T>& tp, int lane, int d0) {
   const T eh = eps / 2;
@@ -973,7 +1043,7 @@ __device__ __forceinline__ T leapfrog_step_ne(Point<T, E>& z, const T (&minv)[E]
 }
 
 // The vector work of leapfrog_step_ne alone (the same expressions): returns this lane's partial of ℓπ − ½ rᵀM⁻¹r, NOT reduced (the pair step of k_nuts
-// carries two leaves' partials through one reduction).
+// carries two leaves' partials through one reduction, the quad step four).
 // TWIN of leapfrog_step_ne above, line for line up to the reduction: change both.  (Two texts on purpose: with leapfrog_step_ne written as a call of this one AND
 // the leaf's scalar work of k_nuts in a shared lambda, the single-leaf loop no longer compiled to the device code it had before — 760 kernels differed; the
 // two rewrites were not tried one by one.  tests/test_leaf_pairs.py holds the twins together.)
@@ -1008,7 +1078,8 @@ template <int L> __device__ __forceinline__ double readlane_t(double v) {
 // masks hand the results back as scalars.  No exec-masked region.  What depends on the ORDER of the two leaves (the running sums, maxabs,
 // redo / numerical / sub_term, the branch that drops leaf b) stays with the caller.
 // TWIN of the single-leaf arm's scalar block in k_nuts (ahmc_nuts.hpp, from `pos_cur += v;` to the running statistics): a change to a
-// leaf's scalar work is made in both (tests/device_probe/pair_stats.hip repeats those lines as its serial reference).
+// leaf's scalar work is made in both, and in quad_leaf_stats below, the TWIN for four leaves (tests/device_probe/pair_stats.hip repeats those lines as its
+// serial reference; tests/device_probe/quad_red.hip holds quad_leaf_stats to this function).
 template <class T> struct PairLeafStats {
   T w[2], sa[2], dH[2];     // leaf weight (LINW: W, else ℓw), α = min(1, W), ΔH
   bool redo[2], div[2];     // ℓw above the linear domain's limit; the divergence test !(−H0 < Δ_max + ne)
@@ -1042,6 +1113,59 @@ __device__ __forceinline__ void pair_leaf_stats(T z, T H0, T delta_max, T lw_lim
   o.redo[1] = LINW && ((m_redo >> LB) & 1ull) != 0ull;
   o.div[0] = ((m_div >> LA) & 1ull) != 0ull;
   o.div[1] = ((m_div >> LB) & 1ull) != 0ull;
+}
+
+// The same for the FOUR leaves of a quad step of k_nuts: w is wave64_quad_reduce_t's register, leaf k in the lanes with lane & 3 == k.
+// Quad 1 of a row of w (lanes 4 .. 7) holds the four energies, and those four lanes are the ONLY ones read: the weight's table indices by
+// v_readlane of lanes 4 .. 7, w / sa / ΔH by v_readlane of lane 4 + k, the flags as bits 4 .. 7 of the compares' lane masks.  Quad 2 takes
+// quad 1's energies by the one row_ror:4 (it held level-1 dot products).  Quads 0 and 3 do NOT hold energies: quad 3 keeps its own level-1
+// dot-product sums and quad 0 receives them, so those eight lanes run the pass on H0 + Σd.  ±Inf and NaN there are sanitised to −Inf like an
+// energy; a large FINITE sum (behind a divergent leaf, where the leapfrogs are speculative) takes such a lane's float-to-int conversion in
+// the weight's exp out of range.  That is the lane's own business — its k feeds only its own ldexp, v_cvt_i32_f64 saturates and does not trap,
+// nothing of lanes 0 .. 3 and 12 .. 15 is ever read — which is why the pass does not spend the two further rotations that would hand them
+// energies too (pair_leaf_stats gets an energy into every lane with the one quad_perm it needs anyway).  tests/device_probe/quad_red.hip
+// puts ±1e300, ±Inf and NaN into those sums.
+// TWIN of pair_leaf_stats above and of the single-leaf arm's scalar block in k_nuts: a change to a leaf's scalar work is made in all three
+// (tests/device_probe/quad_red.hip holds this one to pair_leaf_stats run twice).
+// The results stay in their lanes: leaf k's weight, α and ΔH are read (v_readlane of lane 4 + k) when the caller applies leaf k, not all
+// twelve at once — 24 scalar registers fewer live across the apply sequence, where the kernel's scalar registers are short — and the flags
+// are bits 4 + k of the two compares' lane masks.
+__device__ __forceinline__ float readlane_at(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ double readlane_at(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+template <class T> struct QuadLeafStats {
+  static constexpr int L0 = 4;
+  T w_l, sa_l, dH_l;                   // per lane: leaf (lane & 3)'s weight (LINW: W, else ℓw), α = min(1, W), ΔH
+  unsigned long long m_redo, m_div;    // lane masks: ℓw above the linear domain's limit; the divergence test !(−H0 < Δ_max + ne)
+  __device__ __forceinline__ T w(int k) const { return readlane_at(w_l, L0 + k); }
+  __device__ __forceinline__ T sa(int k) const { return readlane_at(sa_l, L0 + k); }
+  __device__ __forceinline__ T dH(int k) const { return readlane_at(dH_l, L0 + k); }
+  __device__ __forceinline__ bool redo(int k) const { return ((m_redo >> (L0 + k)) & 1ull) != 0ull; }
+  __device__ __forceinline__ bool div(int k) const { return ((m_div >> (L0 + k)) & 1ull) != 0ull; }
+};
+template <class T, bool LINW>
+__device__ __forceinline__ void quad_leaf_stats(T wz, T H0, T delta_max, T lw_limit, QuadLeafStats<T>& o) {
+  constexpr int L0 = QuadLeafStats<T>::L0;
+  const bool odd = (threadIdx.x & 1u) != 0, up = (threadIdx.x & 2u) != 0, oq = (threadIdx.x & 4u) != 0;
+  const T from_prev = dpp_mov<0x124>(wz);  // row_ror:4
+  const T ne = neg_energy_sanitized(oq ? wz : from_prev);
+  const T dH = -ne - H0;
+  const T lw = H0 + ne;
+  T w, sa;
+  if constexpr (LINW) {
+    w = leaf_weight_exp_quad<L0>(lw, odd, up);
+    sa = w >= T(1) ? T(1) : w;
+  } else {
+    const T wa = leaf_weight_exp_quad<L0>(lw > T(0) ? T(0) : lw, odd, up);  // alpha_from_logweight
+    sa = wa >= T(1) ? T(1) : wa;
+    w = lw;
+  }
+  o.m_redo = LINW ? __builtin_amdgcn_ballot_w64(lw > lw_limit) : 0ull;
+  o.m_div = __builtin_amdgcn_ballot_w64(!(-H0 < delta_max + ne));
+  o.w_l = w;
+  o.sa_l = sa;
+  o.dH_l = dH;
 }
 
 // leapfrog_step (untempered) that sums two more caller-supplied partials of the UPDATED point in the same all-reduce

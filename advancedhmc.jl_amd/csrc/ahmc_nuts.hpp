@@ -144,7 +144,11 @@ struct Chunking {
 // ds_read / ds_write with an immediate offset and a global access in the saddr form.
 #define AHMC_AS_LDS __attribute__((address_space(3)))
 #define AHMC_AS_GLB __attribute__((address_space(1)))
-template <class T, int E>
+// SC (round 12; the part measured alone as r11g, profiles/r11_experiments.md): a chain that owns its wave has a wave-uniform global base — the kernel
+// hands it over through v_readfirstlane — and `n_lds` and that base are made opaque at every access, so that `slot < n_lds` is an s_cmp
+// there and the address a scalar base + the lane's 32-bit offset, instead of lane masks and per-lane 64-bit pointers computed at kernel
+// entry and carried (spilled) across the tree.  The same addresses, the same accesses: no result depends on it.
+template <class T, int E, bool SC = false>
 struct Slots {
   AHMC_AS_LDS T* lds;   // first n_lds slots
   AHMC_AS_GLB T* glb;   // the remaining ones
@@ -182,13 +186,39 @@ struct Slots {
 #undef AHMC_SLOT_PUT
   __device__ __forceinline__ void store(int slot, const T (&v)[E]) const {
     constexpr int SE = Chunking<T, E>::NCH * 64 * Chunking<T, E>::CH;
-    if (slot < n_lds) put(lds + slot * SE, lane_off, v);
-    else put(glb + (size_t)(slot - n_lds) * SE, lane_off, v);
+    if constexpr (SC) {
+      int nl = n_lds;
+      AHMC_AS_GLB T* gb = glb;
+      asm volatile("" : "+s"(nl), "+s"(gb));
+      if (slot < nl) {
+        put(lds + slot * SE, lane_off, v);
+      } else {
+        unsigned lo = lane_off;
+        asm volatile("" : "+v"(lo));
+        put(gb + (size_t)(slot - nl) * SE, lo, v);
+      }
+    } else {
+      if (slot < n_lds) put(lds + slot * SE, lane_off, v);
+      else put(glb + (size_t)(slot - n_lds) * SE, lane_off, v);
+    }
   }
   __device__ __forceinline__ void load(int slot, T (&v)[E]) const {
     constexpr int SE = Chunking<T, E>::NCH * 64 * Chunking<T, E>::CH;
-    if (slot < n_lds) get(lds + slot * SE, lane_off, v);
-    else get(glb + (size_t)(slot - n_lds) * SE, lane_off, v);
+    if constexpr (SC) {
+      int nl = n_lds;
+      AHMC_AS_GLB T* gb = glb;
+      asm volatile("" : "+s"(nl), "+s"(gb));
+      if (slot < nl) {
+        get(lds + slot * SE, lane_off, v);
+      } else {
+        unsigned lo = lane_off;
+        asm volatile("" : "+v"(lo));
+        get(gb + (size_t)(slot - nl) * SE, lo, v);
+      }
+    } else {
+      if (slot < n_lds) get(lds + slot * SE, lane_off, v);
+      else get(glb + (size_t)(slot - n_lds) * SE, lane_off, v);
+    }
   }
   // a slot that is NEVER in LDS (the launch plan keeps the checkpoint triples behind n_lds), `extra` more elements into it PER LANE:
   // chains that share a wave may address different triples
@@ -265,6 +295,16 @@ struct DrawStreamT {
 };
 typedef DrawStreamT<false> DrawStream;
 
+// Which one-chain-per-wave instantiations k_nuts<T,64,E,MODE,·> build their subtrees four leaves per step (the quad step) instead of two:
+// a compile-time constant per (T, E, MODE), decided by the static register gate ("Four leaves per step").  Round 12: with the
+// scalar form of the slot addressing (Slots<·,·,true>) every instantiation passes it — E = 1 / 2 / 4 / 8, MODE 0 / 1 / 3 / 4, both types: no more
+// VGPRs and no more scratch per lane than the pair step had, no scratch access and no SGPR restore in the leaf or merge loops
+// (profiles/r12_experiments.md has the table).  An instantiation that stops passing returns false here and keeps the pair step.
+// NO instantiation returns false today: the pair step from the third doubling on is a path that nothing shipped takes and no test runs —
+// whoever turns one off here has to hold it to the fixtures first (tests/test_leaf_pairs.py's is the one the pair step at every doubling was held to).
+template <class T, int E, int MODE>
+constexpr bool nuts_quad_step() { return true; }
+
 // MODE 0: multinomial + generalised, linear-domain weights (the default fast path)
 // MODE 1: multinomial + generalised, log-domain weights (redo pass for chains flagged by MODE 0)
 // MODE 3 / 4: MODE 0 / 1 plus the adaptor's adapt! after every transition, inside the kernel — the warm-up phase in
@@ -327,6 +367,8 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   // loop, and so do the measurement builds, whose stage stamps describe it.
   constexpr bool PAIR = G == 64 && !GENERAL && UTURN_ANY && !AHMC_MFMA_REDUCE && (AHMC_DS_REDUCE & 3) == 0 &&
                         !AHMC_LEAF_PROF && !AHMC_WAVE_TIMELINE;
+  // four leaves per step (the quad step below), from the third doubling on: where the instantiation's registers allow it (nuts_quad_step)
+  constexpr bool QUAD = PAIR && nuts_quad_step<T, E, MODE>();
   const bool strict = GENERAL && p.criterion == 2;
   const int NV = strict ? 3 : 2;  // vectors per pending level: A, RF (, RL)
   const int n_slots = NV * NLEV + NUTS_DORMANT + NUTS_CKPT;
@@ -358,9 +400,10 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
   // one chain per wave: the chain index and the kernel's argument fields on the scalar side ("once per transition" above)
   constexpr bool TSC = G == 64 && !GENERAL;
   const int64_t wave_slot = (int64_t)blockIdx.x * nwaves + wib;
-  Slots<T, E> sl;
+  Slots<T, E, QUAD> sl;   // (the quad step's instantiations: the scalar form, whose registers the quad step needs — Slots)
   sl.lds = (AHMC_AS_LDS T*)lds_vec;
-  sl.glb = (AHMC_AS_GLB T*)(p.scratch + wave_slot * (int64_t)(n_slots - n_lds_slots) * SLOT_ELEMS);
+  if constexpr (QUAD) sl.glb = (AHMC_AS_GLB T*)(p.scratch + wave_scalar64(wave_slot) * (int64_t)(n_slots - n_lds_slots) * SLOT_ELEMS);
+  else sl.glb = (AHMC_AS_GLB T*)(p.scratch + wave_slot * (int64_t)(n_slots - n_lds_slots) * SLOT_ELEMS);
   sl.n_lds = n_lds_slots;
   sl.lane_off = (unsigned)lane64 * CH;
   const int DORM = NV * NLEV;  // first dormant slot (logical numbering: levels first, then the dormant vectors)
@@ -604,67 +647,157 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #endif
         // pair step (PAIR): from the second doubling on an iteration builds the odd leaf `leaf` AND the even leaf behind it with
         // their level-0 merge; `leaf` is the even one from here on — its trailing zero bits are the merges that follow
+        // quad step (QUAD): from the third doubling on an iteration builds FOUR leaves a, b, c, d with their two level-0 merges and the
+        // level-1 merge of the two pairs; `leaf` is d from here on
+        // (everything of the quad step stands inside `if constexpr (PAIR)` or folds to a constant where QUAD is false: the kernels without
+        // it compile to the device code they had)
         bool pair = false;
         if constexpr (PAIR) {
           pair = jw > 0;
           if (pair) ++leaf;
+          if constexpr (QUAD) {
+            if (jw > 1) leaf += 2;
+          }
         }
         // merges after this leaf: one per trailing zero bit of `leaf` (:649-673); the count is wave-uniform
         const int nm = __builtin_ctz(leaf);
         T dots_m0[2] = {0, 0}, RF_m0[E];  // fast kernels: U-turn dot products / first-built r of the FIRST merge
         if (pair) {
           if constexpr (PAIR) {
-            // (a chain owns the wave: `alive` holds for the whole wave here, and every predicate below is wave-uniform)
-            const T es = v > 0 ? eps : -eps;
-            T ea = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
-            T r_a[E];  // the level-0 pending half: ρ and first-built r of a one-leaf subtree are its r
-            copy_vec(r_a, cur.r);
-            T eb = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
-            T dots[2] = {0, 0};  // the expressions of merge_level(0, …)
+            // (QUAD is a constant: where it is false the quad arm below is dead code and this is the pair step alone.  No shipped instantiation
+            // is in that case — nuts_quad_step is true for all of them — so the pair arm runs at jw == 1 only, and only there is it tested.)
+            if (QUAD && jw > 1) {
+              // Vector work first: nothing in the leapfrog of c or d needs an energy or a decision of a or b, and ρ of the level-1 merge is a
+              // vector sum.  The level-1 pending half (ρ_ab, r_a, its weight and candidate) is never parked inside a quad: it stays in registers.
+              const T es = v > 0 ? eps : -eps;
+              T dab[2] = {0, 0}, dcd[2] = {0, 0}, dl[2] = {0, 0};
+              const T e_a = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+              copy_vec(RF_c, cur.r);  // r of leaf a: the first-built r of the pair (a,b) and of the quad
+              const T e_b = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
 #pragma unroll
-            for (int e = 0; e < E; ++e) {
-              A_c[e] = r_a[e] + cur.r[e];  // ρ = ρ_left + ρ_right
-              dots[0] += A_c[e] * (minv[e] * r_a[e]);
-              dots[1] += A_c[e] * (minv[e] * cur.r[e]);
-            }
-            // The reduction hands back its transposed register, and what the two leaves' scalar work computes that does not depend on
-            // their order — sanitised energy, ΔH, ℓw, the weight's exp, min(1, W), the redo and divergence compares — runs ONCE, leaf a in
-            // the even lanes and leaf b in the odd ones (ahmc_device.hpp: pair_leaf_stats, the TWIN of the single-leaf arm's scalar block
-            // below): one exp chain with its scalar table load on the leaf loop's chain of dependent stages instead of two back to back.
-            // What depends on the order is applied here, in the single-leaf arm's order; if leaf a diverges nothing of leaf b is applied,
-            // its redo bit included.
-            T z_t;
-            const bool turn_ab = wave64_pair_reduce_t(dots[0], dots[1], ea, eb, z_t);
-            PairLeafStats<T> ps;
-            pair_leaf_stats<T, LINW>(z_t, H0, p.delta_max, sizeof(T) == 4 ? T(60) : T(LINW_LIMIT), ps);
-            auto leaf_apply = [&](const int i) {
-              pos_cur += v;
-              ck_c = pos_cur;
-              w_c = ps.w[i];
-              if constexpr (LINW) redo = redo || ps.redo[i];
-              sub_term = ps.div[i];
-              numerical = numerical || sub_term;
-              sa_c = sa_c + ps.sa[i];
-              na_c = na_c + 1;
-              if (v > 0) { dh_c = maxabs(dh_c, ps.dH[i]); asm volatile(""); }
-              else { dh_c = maxabs(ps.dH[i], dh_c); asm volatile(""); }
-            };
-            leaf_apply(0);
-            if (!sub_term) {
-              const T w_p = w_c;
-              const int ck_p = ck_c;
-              leaf_apply(1);
-              if (!sub_term) {
-                // the level-0 merge: combine(rng, sampler′, sampler′′) and the U-turn test of the pair, as merge_level does them
+              for (int e = 0; e < E; ++e) {  // the expressions of merge_level(0, …) for (a,b)
+                A_c[e] = RF_c[e] + cur.r[e];
+                dab[0] += A_c[e] * (minv[e] * RF_c[e]);
+                dab[1] += A_c[e] * (minv[e] * cur.r[e]);
+              }
+              // (the reduction's first exchange of a pair, made as soon as the pair is there: one register per pair across leaves c and d)
+              const T yab = wave64_quad_pair(e_a, e_b), xab = wave64_quad_pair(dab[0], dab[1]);
+              const T e_c = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+              T r_c[E];
+              copy_vec(r_c, cur.r);
+              const T e_d = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+#pragma unroll
+              for (int e = 0; e < E; ++e) {
+                const T rho_cd = r_c[e] + cur.r[e];  // merge_level(0, …) for (c,d)
+                dcd[0] += rho_cd * (minv[e] * r_c[e]);
+                dcd[1] += rho_cd * (minv[e] * cur.r[e]);
+                A_c[e] = A_c[e] + rho_cd;           // merge_level(1, …): ρ = ρ_left + ρ_right, against r_a and r_d
+                dl[0] += A_c[e] * (minv[e] * RF_c[e]);
+                dl[1] += A_c[e] * (minv[e] * cur.r[e]);
+              }
+              // ONE reduction of the ten numbers, ONE lane-parallel pass for the four leaves' scalar work (ahmc_device.hpp: wave64_quad_reduce_t,
+              // quad_leaf_stats — the TWINs of the pair step's two), then everything that depends on the order, in the reference's order:
+              // a, b, merge (a,b), c, d, merge (c,d), the level-1 merge.  At the first divergence or U-turn nothing behind it is applied or drawn,
+              // its redo bit included; the leapfrogs behind it (at most three) were speculative.
+              T w_t;
+              const unsigned long long turns =
+                  wave64_quad_reduce_t(xab, wave64_quad_pair(dcd[0], dcd[1]), wave64_quad_pair(dl[0], dl[1]), yab, wave64_quad_pair(e_c, e_d), w_t);
+              QuadLeafStats<T> qs;
+              quad_leaf_stats<T, LINW>(w_t, H0, p.delta_max, sizeof(T) == 4 ? T(60) : T(LINW_LIMIT), qs);
+              auto leaf_apply = [&](const int i) {
+                pos_cur += v;
+                ck_c = pos_cur;
+                w_c = qs.w(i);
+                if constexpr (LINW) redo = redo || qs.redo(i);
+                sub_term = qs.div(i);
+                numerical = numerical || sub_term;
+                sa_c = sa_c + qs.sa(i);
+                na_c = na_c + 1;
+                const T dH_i = qs.dH(i);
+                if (v > 0) { dh_c = maxabs(dh_c, dH_i); asm volatile(""); }
+                else { dh_c = maxabs(dH_i, dh_c); asm volatile(""); }
+              };
+              // combine(rng, sampler′, sampler′′) of a pending half (w_p, ck_p) with the half just completed (w_c, ck_c), as merge_level does it
+              auto merge_apply = [&](const T w_p, const int ck_p, const bool turn) {
                 T w_new;
                 if constexpr (LINW) w_new = w_p + w_c; else w_new = logaddexp(w_p, w_c);
                 bool keep_first;
                 if constexpr (LINW) keep_first = AHMC_UNI((T)ds.uniform() * w_new < w_p); else keep_first = AHMC_UNI(w_new < w_p + (T)ds.randexp());
                 if (keep_first) ck_c = ck_p;
                 w_c = w_new;
-                sub_term = turn_ab;
-                copy_vec(RF_c, r_a);
+                sub_term = turn;
                 AHMC_LP_COUNT(9, 1)
+              };
+              // the two leaves 2h, 2h + 1 and their level-0 merge
+              auto pair_apply = [&](const int h, const bool turn) {
+                leaf_apply(2 * h);
+                if (!sub_term) {
+                  const T w_p = w_c;
+                  const int ck_p = ck_c;
+                  leaf_apply(2 * h + 1);
+                  if (!sub_term) merge_apply(w_p, ck_p, turn);
+                }
+              };
+              pair_apply(0, (turns & QUAD_TURN_AB) != 0ull);
+              if (!sub_term) {
+                const T w_ab = w_c;
+                const int ck_ab = ck_c;
+                pair_apply(1, (turns & QUAD_TURN_CD) != 0ull);
+                if (!sub_term) merge_apply(w_ab, ck_ab, (turns & QUAD_TURN_L1) != 0ull);
+              }
+            } else {   // the second doubling: the pair step
+              // (a chain owns the wave: `alive` holds for the whole wave here, and every predicate below is wave-uniform)
+              const T es = v > 0 ? eps : -eps;
+              T ea = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+              T r_a[E];  // the level-0 pending half: ρ and first-built r of a one-leaf subtree are its r
+              copy_vec(r_a, cur.r);
+              T eb = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+              T dots[2] = {0, 0};  // the expressions of merge_level(0, …)
+#pragma unroll
+              for (int e = 0; e < E; ++e) {
+                A_c[e] = r_a[e] + cur.r[e];  // ρ = ρ_left + ρ_right
+                dots[0] += A_c[e] * (minv[e] * r_a[e]);
+                dots[1] += A_c[e] * (minv[e] * cur.r[e]);
+              }
+              // The reduction hands back its transposed register, and what the two leaves' scalar work computes that does not depend on
+              // their order — sanitised energy, ΔH, ℓw, the weight's exp, min(1, W), the redo and divergence compares — runs ONCE, leaf a in
+              // the even lanes and leaf b in the odd ones (ahmc_device.hpp: pair_leaf_stats, the TWIN of the single-leaf arm's scalar block
+              // below): one exp chain with its scalar table load on the leaf loop's chain of dependent stages instead of two back to back.
+              // What depends on the order is applied here, in the single-leaf arm's order; if leaf a diverges nothing of leaf b is applied,
+              // its redo bit included.
+              T z_t;
+              const bool turn_ab = wave64_pair_reduce_t(dots[0], dots[1], ea, eb, z_t);
+              PairLeafStats<T> ps;
+              pair_leaf_stats<T, LINW>(z_t, H0, p.delta_max, sizeof(T) == 4 ? T(60) : T(LINW_LIMIT), ps);
+              auto leaf_apply = [&](const int i) {
+                pos_cur += v;
+                ck_c = pos_cur;
+                w_c = ps.w[i];
+                if constexpr (LINW) redo = redo || ps.redo[i];
+                sub_term = ps.div[i];
+                numerical = numerical || sub_term;
+                sa_c = sa_c + ps.sa[i];
+                na_c = na_c + 1;
+                if (v > 0) { dh_c = maxabs(dh_c, ps.dH[i]); asm volatile(""); }
+                else { dh_c = maxabs(ps.dH[i], dh_c); asm volatile(""); }
+              };
+              leaf_apply(0);
+              if (!sub_term) {
+                const T w_p = w_c;
+                const int ck_p = ck_c;
+                leaf_apply(1);
+                if (!sub_term) {
+                  // the level-0 merge: combine(rng, sampler′, sampler′′) and the U-turn test of the pair, as merge_level does them
+                  T w_new;
+                  if constexpr (LINW) w_new = w_p + w_c; else w_new = logaddexp(w_p, w_c);
+                  bool keep_first;
+                  if constexpr (LINW) keep_first = AHMC_UNI((T)ds.uniform() * w_new < w_p); else keep_first = AHMC_UNI(w_new < w_p + (T)ds.randexp());
+                  if (keep_first) ck_c = ck_p;
+                  w_c = w_new;
+                  sub_term = turn_ab;
+                  copy_vec(RF_c, r_a);
+                  AHMC_LP_COUNT(9, 1)
+                }
               }
             }
           }
@@ -725,9 +858,9 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
 #if AHMC_LEAF_PROF
           if (GENERAL || G > 64) AHMC_LP_TICK(0)   // (the other leaf forms: the whole leapfrog incl. its reduction under [0])
 #endif
-          // (TWIN of pair_leaf_stats, ahmc_device.hpp, and of leaf_apply in the pair step above: from here to the running statistics, the lines
+          // (TWIN of pair_leaf_stats and quad_leaf_stats, ahmc_device.hpp, and of leaf_apply in the pair and quad steps above: from here to the running statistics, the lines
           // a fast kernel whose chain owns the wave executes are repeated there — change both, or the first doubling's leaf (this arm)
-          // and the later ones (the pair step) stop agreeing bit for bit: tests/test_leaf_pairs.py's fixture is what notices)
+          // and the later ones (the pair step, the quad step) stop agreeing bit for bit: the fixtures of tests/test_leaf_pairs.py and tests/test_leaf_quads.py are what notices)
           pos_cur += v;
           const T ne = (GENERAL || (FUSE_M0 && nm > 0)) ? cur.lp + cur.lk : ne_leaf;  // neg_energy(z′)
           const T dH = -ne - H0;
@@ -886,7 +1019,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           bool m = AHMC_UNI(alive && !sub_term);
           if (AHMC_ANY(m)) {
             if (m && !pair) merge_level(0, cur.r, cur.r, std::bool_constant<FUSE_M0>{});  // (a pair step made its level-0 merge above)
-            for (int lvl = 1; lvl < nm; ++lvl) {
+            for (int lvl = 1 + (QUAD && jw > 1 ? 1 : 0); lvl < nm; ++lvl) {  // (a quad step made its level-1 merge as well)
               m = AHMC_UNI(alive && !sub_term);
               if (!AHMC_ANY(m)) break;
               if (m) merge_level(lvl, A_c, RF_c, std::false_type{});
