@@ -184,7 +184,7 @@ static __device__ const unsigned long long EXP2_64_BITS[64] = {
 // the bench's occupancy) against 310 of 1 571 on cfg2, where the entry is a scalar load.  Those kernels evaluate the Horner-11 form
 // (no memory access: 9 more VALU, ≈ 700 fewer cycles).
 // (TWIN: leaf_weight_exp_pair below repeats the table form of this function, statement for statement, for two leaves in the two lane
-// parities of a wave, and leaf_weight_exp_quad for four leaves in the four lanes of a quad — change all three)
+// parities of a wave, and leaf_weight_exp_quad for four leaves in the four lanes of a quad, leaf_weight_exp_oct for eight — change all four)
 template <bool UNIFORM>
 __device__ __forceinline__ double leaf_weight_exp(double x) {
   constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
@@ -242,7 +242,7 @@ __device__ __forceinline__ T alpha_from_logweight(T lw) {
 // b's (pair_leaf_stats below), and lanes LA / LB are the ones whose results are read.  The two table entries are two scalar loads issued
 // together — their indices come from lanes LA / LB by v_readlane — and lane parity picks the entry; everything else is lane-local, so
 // each of the two lanes runs the instructions of leaf_weight_exp<true> on its own argument and returns its bits.
-// TWIN of the table form of leaf_weight_exp above and of leaf_weight_exp_quad below, statement for statement: change all three.  EVERY lane's
+// TWIN of the table form of leaf_weight_exp above and of leaf_weight_exp_quad / _oct below, statement for statement: change all four.  EVERY lane's
 // argument must be a value whose (int)dk is defined (the caller hands every lane one of the two leaves' arguments, so it is wherever leaf_weight_exp's own is).
 template <int LA, int LB>
 __device__ __forceinline__ double leaf_weight_exp_pair(double x, bool odd) {
@@ -267,7 +267,7 @@ __device__ __forceinline__ float leaf_weight_exp_pair(float x, bool) { return ex
 
 // The same for FOUR leaves (quad_leaf_stats below): leaf k's argument in the lanes with lane & 3 == k, lanes L0 .. L0 + 3 the ones whose
 // results are read.  The four table entries are four scalar loads issued together; lane & 3 picks the entry.
-// TWIN of the table form of leaf_weight_exp and of leaf_weight_exp_pair above, statement for statement: change all three.  The arguments of
+// TWIN of the table form of leaf_weight_exp and of leaf_weight_exp_pair above and of leaf_weight_exp_oct below, statement for statement: change all four.  The arguments of
 // lanes L0 .. L0 + 3 must be values whose (int)dk is defined, as there; the other lanes' results are never read, and quad_leaf_stats hands
 // eight of them dot-product sums (see there why that is left so).
 template <int L0>
@@ -293,6 +293,47 @@ __device__ __forceinline__ double leaf_weight_exp_quad(double x, bool odd, bool 
 }
 template <int L0>
 __device__ __forceinline__ float leaf_weight_exp_quad(float x, bool, bool) { return exp(x); }
+
+// a in the even 16-lane rows, b in the odd ones: a DPP move under row_mask 0b1010 — a select that needs no lane mask in scalar registers,
+// which the draws kernel is short of
+__device__ __forceinline__ double sel_odd_rows(double a, double b) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(a), __double2loint(b), 0xE4, 0xA, 0xF, false);  // quad_perm [0,1,2,3]
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(a), __double2hiint(b), 0xE4, 0xA, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+// The same for EIGHT leaves (oct_leaf_stats below): leaves a .. d in lanes L0 .. L0 + 3, leaves e .. h in lanes L1 .. L1 + 3, one 16-lane row
+// apart (L1 = L0 + 16).  The eight table entries are eight scalar loads issued together; lane & 3 and the row (sel_odd_rows) pick the entry.
+// TWIN of the table form of leaf_weight_exp, of leaf_weight_exp_pair and of leaf_weight_exp_quad above, statement for statement: change all
+// four.  The arguments of the eight lanes read must be values whose (int)dk is defined, as there; the other lanes' results are never read.
+template <int L0, int L1>
+__device__ __forceinline__ double leaf_weight_exp_oct(double x, bool odd, bool up) {
+  constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
+  const double xc = x < -1100.0 ? -1100.0 : x;
+  const double dk = __builtin_rint(xc * 92.33248261689366);                // 64 / ln 2
+  double t = __builtin_fma(dk, -0x1.62e42fef00000p-7, xc);                  // − k·ln2/64: high part (20 trailing zero bits: exact product)
+  t = __builtin_fma(dk, -0x1.473de6af278edp-40, t);                         // low part
+  const int k = (int)dk;
+  const int k0 = __builtin_amdgcn_readlane(k, L0), k1 = __builtin_amdgcn_readlane(k, L0 + 1);
+  const int k2 = __builtin_amdgcn_readlane(k, L0 + 2), k3 = __builtin_amdgcn_readlane(k, L0 + 3);
+  const int k4 = __builtin_amdgcn_readlane(k, L1), k5 = __builtin_amdgcn_readlane(k, L1 + 1);
+  const int k6 = __builtin_amdgcn_readlane(k, L1 + 2), k7 = __builtin_amdgcn_readlane(k, L1 + 3);
+  const double tj0 = C(EXP2_64_BITS[k0 & 63]), tj1 = C(EXP2_64_BITS[k1 & 63]);
+  const double tj2 = C(EXP2_64_BITS[k2 & 63]), tj3 = C(EXP2_64_BITS[k3 & 63]);
+  const double tj4 = C(EXP2_64_BITS[k4 & 63]), tj5 = C(EXP2_64_BITS[k5 & 63]);
+  const double tj6 = C(EXP2_64_BITS[k6 & 63]), tj7 = C(EXP2_64_BITS[k7 & 63]);
+  const double tjl = odd ? tj1 : tj0, tjh = odd ? tj3 : tj2;
+  const double tjl2 = odd ? tj5 : tj4, tjh2 = odd ? tj7 : tj6;
+  const double tja = up ? tjh : tjl, tjb = up ? tjh2 : tjl2;
+  const double tj = sel_odd_rows(tja, tjb);
+  double q = __builtin_fma(t, 8.3333333333333332e-03, 4.1666666666666664e-02);  // 1/120, 1/24
+  q = fma3(t, q, 1.6666666666666666e-01);
+  q = fma3(t, q, 0.5);
+  q = fma3(t, q, 1.0);
+  q = q * t;                                                                // e^t − 1
+  return __builtin_ldexp(__builtin_fma(tj, q, tj), k >> 6);
+}
+template <int L0, int L1>
+__device__ __forceinline__ float leaf_weight_exp_oct(float x, bool, bool) { return exp(x); }
 
 template <class T> __device__ __forceinline__ T maxabs(T a, T b) { return fabs(a) > fabs(b) ? a : b; }  // :526
 
@@ -604,6 +645,64 @@ __device__ __forceinline__ unsigned long long wave64_quad_reduce_t(T xab, T xcd,
   return __builtin_amdgcn_ballot_w64(w <= T(0));
 }
 constexpr unsigned long long QUAD_TURN_AB = 0x3ull, QUAD_TURN_CD = 0xCull, QUAD_TURN_L1 = 0x300ull;  // lanes of the three decisions in that mask
+
+// What EIGHT consecutive NUTS leaves a .. h, their four level-0 merges, their two level-1 merges and the level-2 merge of the two halves need
+// from the wave, in ONE reduction (the octo step of k_nuts): 22 lane partials in — eight energies and seven pairs of dot products — and one
+// register out.  Each half (a,b,c,d) / (e,f,g,h) goes through the four in-row exchanges of wave64_quad_reduce_t on its own, as soon as it is
+// complete (wave64_oct_rows_de + wave64_oct_rows: ONE register per half crosses the other half's leapfrogs); the second half carries the level-2 merge's pair in the
+// slots of quad 2 where the first has its level-1 sums a second time:
+//     lanes 0 / 1: Σd(ab | ef)   lanes 2 / 3: Σd(cd | gh)   lanes 4 .. 7: Σe   lanes 8 / 9: Σd level 1   lanes 10 / 11: Σd level 2 (second half)
+// Dot products sit in quads 0 and 2 and energies in quad 1 — where the groupings of the primitives this replaces hold, as derived at
+// wave64_quad_reduce_t: quad 2 joins (Q2 + Q1) + (Q0 + Q3), wave_allsum2<64>'s two sums added in the other order, so the level-2 pair has
+// wave64_any_le0_pair's bits there.  Inside a quad a slot of the upper two lanes sums (own pair) + (other pair) like one of the lower two.
+// The xor-16 exchange is TRANSPOSED as well: v_permlane16_swap of the two halves' registers hands rows 0 / 2 the first half's
+// {row 2k, row 2k + 1} and rows 1 / 3 the second half's, so one addition makes lower + upper for both — the order of xor16_sum — and ONE
+// register goes through the xor-32 exchange: rows 0 and 2 hold the first half's sixteen slots, rows 1 and 3 the second half's.
+// All seven U-turn decisions are bits of ONE compare's lane mask; no sum is broadcast.
+// f64: 2 × 69 (the halves' in-row stages) + 7 + 3 (the level-2 pair) + 3 + 5 + 1 = 157 VALU, against 2 × 80 for two quad reductions and 27
+// for the level-2 merge's predicate — and one chain of dependent stages instead of three.
+// TWIN of wave64_quad_reduce_t (each half) and of wave64_any_le0_pair (the level-2 pair) in what each value goes through: change all
+// (tests/device_probe/oct_red.hip runs them on the same data).
+// xab, xcd, yab, ycd: as for wave64_quad_reduce_t; xl: wave64_quad_pair of the half's level-1 dot products; xl2: of the level-2 merge's (second
+// half), or xl again (first half)
+// (two steps: the four level-0 / energy pair registers are one register after wave64_oct_rows_de, made as soon as the half's last leapfrog
+// is through, so that only it and the level-1 pair wait for the level-2 merge's vector work)
+template <class T>
+__device__ __forceinline__ T wave64_oct_rows_de(T xab, T xcd, T yab, T ycd) {
+  const bool up = (threadIdx.x & 2u) != 0, oq = (threadIdx.x & 4u) != 0;
+  const T rd = (up ? xcd : xab) + dpp_mov<0x4E>(up ? xab : xcd);               // quad_perm [2,3,0,1]
+  const T re = (up ? ycd : yab) + dpp_mov<0x4E>(up ? yab : ycd);
+  return (oq ? re : rd) + dpp_mov<0x124>(oq ? rd : re);                        // row_ror:4
+}
+template <class T>
+__device__ __forceinline__ T wave64_oct_rows(T z, T xl, T xl2) {
+  const bool up = (threadIdx.x & 2u) != 0, hq = (threadIdx.x & 8u) != 0;
+  const T rl = (up ? xl2 : xl) + dpp_mov<0x4E>(up ? xl : xl2);                 // quad_perm [2,3,0,1]
+  const T zl = rl + dpp_mov<0x124>(rl);                                        // row_ror:4
+  return (hq ? zl : z) + dpp_mov<0x128>(hq ? z : zl);                          // row_ror:8
+}
+// own half's {row 2k} + {row 2k + 1}: even rows collect h1, odd rows h2 (v_permlane16_swap swaps the odd rows of its first operand with the
+// even rows of its second)
+__device__ __forceinline__ float xor16_sum_t(float h1, float h2) {
+  auto p = __builtin_amdgcn_permlane16_swap(__float_as_int(h1), __float_as_int(h2), false, false);
+  return __int_as_float(p[0]) + __int_as_float(p[1]);
+}
+__device__ __forceinline__ double xor16_sum_t(double h1, double h2) {
+  auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(h1), __double2loint(h2), false, false);
+  auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(h1), __double2hiint(h2), false, false);
+  return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
+}
+// h1, h2: wave64_oct_rows of the two halves
+template <class T>
+__device__ __forceinline__ unsigned long long wave64_oct_reduce_t(T h1, T h2, T& w) {
+  w = xor16_sum_t(h1, h2);
+  w = xor32_sum(w);
+  return __builtin_amdgcn_ballot_w64(w <= T(0));
+}
+// lanes of the seven decisions in that mask: the first half's as in a quad, the second half's one row up
+constexpr unsigned long long OCT_TURN_AB = QUAD_TURN_AB, OCT_TURN_CD = QUAD_TURN_CD, OCT_TURN_ABCD = QUAD_TURN_L1;
+constexpr unsigned long long OCT_TURN_EF = QUAD_TURN_AB << 16, OCT_TURN_GH = QUAD_TURN_CD << 16, OCT_TURN_EFGH = QUAD_TURN_L1 << 16;
+constexpr unsigned long long OCT_TURN_L2 = 0xC00ull << 16;
 
 // all-reduce (sum) of K independent values across the G lanes of each group
 template <int G, class T, int K>
@@ -1163,6 +1262,53 @@ __device__ __forceinline__ void quad_leaf_stats(T wz, T H0, T delta_max, T lw_li
   }
   o.m_redo = LINW ? __builtin_amdgcn_ballot_w64(lw > lw_limit) : 0ull;
   o.m_div = __builtin_amdgcn_ballot_w64(!(-H0 < delta_max + ne));
+  o.w_l = w;
+  o.sa_l = sa;
+  o.dH_l = dH;
+}
+
+// The same for the EIGHT leaves of an octo step of k_nuts: w is wave64_oct_reduce_t's register — row 0 holds the first half's slots and row 1
+// the second half's, each laid out as wave64_quad_reduce_t's row, so leaf k < 4 is read in lane 4 + k and leaf k >= 4 in lane 16 + k (quad 1
+// of its row).  ONE pass: one row_ror:4, one exp chain, eight table indices by v_readlane and eight scalar table loads issued together.  What
+// quad_leaf_stats says about the lanes that do not hold energies holds here row by row (quads 0 and 3 run the pass on H0 + Σd; nothing of
+// them is read).
+// TWIN of quad_leaf_stats and pair_leaf_stats above and of the single-leaf arm's scalar block in k_nuts: a change to a leaf's scalar work is
+// made in all four (tests/device_probe/oct_red.hip holds this one to quad_leaf_stats run on each half).
+template <class T> struct OctLeafStats {
+  static constexpr int L0 = 4, L1 = 20;
+  T w_l, sa_l, dH_l;                   // per lane: the row's leaf (lane & 3)'s weight (LINW: W, else ℓw), α = min(1, W), ΔH
+  // the two compares' lane masks — the divergence test !(−H0 < Δ_max + ne); ℓw above the linear domain's limit — cut to the eight lanes that
+  // are read and packed into ONE 32-bit scalar (divergence: bit lane_of(k); redo: bit lane_of(k) + 8, the lanes of quad 3, which hold no
+  // energy): five scalar registers fewer live across the apply sequence, where the draws kernel is short of them
+  unsigned m_flags;
+  static constexpr unsigned LANES = (0xFu << L0) | (0xFu << L1);
+  static __device__ __forceinline__ int lane_of(int k) { return k < 4 ? L0 + k : L1 + (k - 4); }
+  __device__ __forceinline__ T w(int k) const { return readlane_at(w_l, lane_of(k)); }
+  __device__ __forceinline__ T sa(int k) const { return readlane_at(sa_l, lane_of(k)); }
+  __device__ __forceinline__ T dH(int k) const { return readlane_at(dH_l, lane_of(k)); }
+  __device__ __forceinline__ bool redo(int k) const { return ((m_flags >> (lane_of(k) + 8)) & 1u) != 0u; }
+  __device__ __forceinline__ bool div(int k) const { return ((m_flags >> lane_of(k)) & 1u) != 0u; }
+};
+template <class T, bool LINW>
+__device__ __forceinline__ void oct_leaf_stats(T wz, T H0, T delta_max, T lw_limit, OctLeafStats<T>& o) {
+  constexpr int L0 = OctLeafStats<T>::L0, L1 = OctLeafStats<T>::L1;
+  const bool odd = (threadIdx.x & 1u) != 0, up = (threadIdx.x & 2u) != 0, oq = (threadIdx.x & 4u) != 0;
+  const T from_prev = dpp_mov<0x124>(wz);  // row_ror:4
+  const T ne = neg_energy_sanitized(oq ? wz : from_prev);
+  const T dH = -ne - H0;
+  const T lw = H0 + ne;
+  T w, sa;
+  if constexpr (LINW) {
+    w = leaf_weight_exp_oct<L0, L1>(lw, odd, up);
+    sa = w >= T(1) ? T(1) : w;
+  } else {
+    const T wa = leaf_weight_exp_oct<L0, L1>(lw > T(0) ? T(0) : lw, odd, up);  // alpha_from_logweight
+    sa = wa >= T(1) ? T(1) : wa;
+    w = lw;
+  }
+  const unsigned m_redo = LINW ? (unsigned)__builtin_amdgcn_ballot_w64(lw > lw_limit) : 0u;
+  const unsigned m_div = (unsigned)__builtin_amdgcn_ballot_w64(!(-H0 < delta_max + ne));
+  o.m_flags = (m_div & OctLeafStats<T>::LANES) | ((m_redo & OctLeafStats<T>::LANES) << 8);
   o.w_l = w;
   o.sa_l = sa;
   o.dH_l = dH;

@@ -305,6 +305,27 @@ typedef DrawStreamT<false> DrawStream;
 template <class T, int E, int MODE>
 constexpr bool nuts_quad_step() { return true; }
 
+// Which of those build their subtrees EIGHT leaves per step from the fourth doubling on (the octo step), by the same static gate against the
+// parent build: no more VGPRs and no more scratch per lane, no scratch access and no SGPR restore in the leaf or merge loops
+// (profiles/r13_experiments.md has the table).  Round 13: E = 1 and E = 2, except Float64 in MODE 1 (the draws' redo kernels), which restore scalars in
+// their leaf loop with it (E = 2: 45, and 20 without it).  E = 4 and E = 8 keep the quad step: Float64 E = 8 takes more registers or scratch with the arm, and none of them was timed
+// at D = 256 / 512.  The gate was passed for the IsoGaussian family (TK = 0: cfg2's kernels 125 / 121 -> 119 / 118 VGPRs, no scratch); the
+// other families' kernels gained scratch in several instantiations, so k_nuts takes the arm for TK = 0 alone (`OCT` there).  An instantiation
+// without the arm compiles to the device code it had.
+// Is doubling jw the fourth or a later one (an octo step)?  Compared anew at each of its four uses in k_nuts, on a copy of jw the optimiser
+// cannot see through: as a loop-invariant predicate it is hoisted into a scalar register pair that lives around the whole leaf loop, and the
+// draws kernel, short of scalar registers, then parks other loop-invariant scalars and restores them inside the loop.
+__device__ __forceinline__ bool nuts_oct_doubling(int jw) {
+  asm volatile("" : "+s"(jw));
+  return jw > 2;
+}
+template <class T, int E, int MODE>
+constexpr bool nuts_oct_step() {
+  if (E > 2) return false;
+  if (sizeof(T) == 8 && MODE == 1) return false;
+  return true;
+}
+
 // MODE 0: multinomial + generalised, linear-domain weights (the default fast path)
 // MODE 1: multinomial + generalised, log-domain weights (redo pass for chains flagged by MODE 0)
 // MODE 3 / 4: MODE 0 / 1 plus the adaptor's adapt! after every transition, inside the kernel — the warm-up phase in
@@ -369,6 +390,8 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
                         !AHMC_LEAF_PROF && !AHMC_WAVE_TIMELINE;
   // four leaves per step (the quad step below), from the third doubling on: where the instantiation's registers allow it (nuts_quad_step)
   constexpr bool QUAD = PAIR && nuts_quad_step<T, E, MODE>();
+  // eight leaves per step (the octo step below), from the fourth doubling on: where the static register gate lets it (nuts_oct_step)
+  constexpr bool OCT = QUAD && TK == 0 && nuts_oct_step<T, E, MODE>();
   const bool strict = GENERAL && p.criterion == 2;
   const int NV = strict ? 3 : 2;  // vectors per pending level: A, RF (, RL)
   const int n_slots = NV * NLEV + NUTS_DORMANT + NUTS_CKPT;
@@ -649,6 +672,12 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
         // their level-0 merge; `leaf` is the even one from here on — its trailing zero bits are the merges that follow
         // quad step (QUAD): from the third doubling on an iteration builds FOUR leaves a, b, c, d with their two level-0 merges and the
         // level-1 merge of the two pairs; `leaf` is d from here on
+        // octo step (OCT): from the fourth doubling on an iteration builds EIGHT leaves a .. h with their four level-0 merges, two level-1
+        // merges and the level-2 merge; `leaf` is h from here on.  Which arm runs at which doubling, and where each is held to the bits:
+        //   first doubling   single-leaf arm                                    tests/test_leaf_pairs.py (max_depth 1)
+        //   second           pair step                                          tests/test_leaf_pairs.py
+        //   third            quad step (where OCT: through the octo's reduction and pass, second half empty)   tests/test_leaf_quads.py
+        //   fourth and later octo step where OCT, else quad step                tests/test_leaf_octs.py / tests/test_leaf_quads.py
         // (everything of the quad step stands inside `if constexpr (PAIR)` or folds to a constant where QUAD is false: the kernels without
         // it compile to the device code they had)
         bool pair = false;
@@ -657,6 +686,9 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           if (pair) ++leaf;
           if constexpr (QUAD) {
             if (jw > 1) leaf += 2;
+            if constexpr (OCT) {
+              if (nuts_oct_doubling(jw)) leaf += 4;
+            }
           }
         }
         // merges after this leaf: one per trailing zero bit of `leaf` (:649-673); the count is wave-uniform
@@ -667,6 +699,139 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
             // (QUAD is a constant: where it is false the quad arm below is dead code and this is the pair step alone.  No shipped instantiation
             // is in that case — nuts_quad_step is true for all of them — so the pair arm runs at jw == 1 only, and only there is it tested.)
             if (QUAD && jw > 1) {
+              if constexpr (OCT) {
+              // (the kernels with the octo step: the quad step of the third doubling and the octo step share the vector helper, the apply
+              // sequence and ONE body of reduction and pass)
+              // Vector work first: nothing in the leapfrog of c or d needs an energy or a decision of a or b, and ρ of the level-1 merge is a
+              // vector sum.  The level-1 pending half (ρ_ab, r_a, its weight and candidate) is never parked inside a quad: it stays in registers.
+              const T es = v > 0 ? eps : -eps;
+              // Four leapfrogs from `cur` and the lane partials of their three merges, each pair through the reduction's first exchange
+              // (wave64_quad_pair) as soon as it exists: one register per pair across the leapfrogs that follow.  On exit RF_q is r of the
+              // first of the four leaves, A_q their ρ and cur.r the r of the last — what merge_level(1, …) leaves.  The quad step is one of
+              // these; the octo step's two halves are two.
+              auto quad_vec = [&](T (&RF_q)[E], T (&A_q)[E], T& xab, T& xcd, T& xl, T& yab, T& ycd) {
+                T dab[2] = {0, 0}, dcd[2] = {0, 0}, dl[2] = {0, 0};
+                const T e_a = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+                copy_vec(RF_q, cur.r);  // r of leaf a: the first-built r of the pair (a,b) and of the quad
+                const T e_b = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {  // the expressions of merge_level(0, …) for (a,b)
+                  A_q[e] = RF_q[e] + cur.r[e];
+                  dab[0] += A_q[e] * (minv[e] * RF_q[e]);
+                  dab[1] += A_q[e] * (minv[e] * cur.r[e]);
+                }
+                yab = wave64_quad_pair(e_a, e_b);
+                xab = wave64_quad_pair(dab[0], dab[1]);
+                const T e_c = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+                T r_c[E];
+                copy_vec(r_c, cur.r);
+                const T e_d = leapfrog_step_ne_partial<T, G, E, TK>(cur, minv, es, p.tp, lane, d0);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                  const T rho_cd = r_c[e] + cur.r[e];  // merge_level(0, …) for (c,d)
+                  dcd[0] += rho_cd * (minv[e] * r_c[e]);
+                  dcd[1] += rho_cd * (minv[e] * cur.r[e]);
+                  A_q[e] = A_q[e] + rho_cd;           // merge_level(1, …): ρ = ρ_left + ρ_right, against r_a and r_d
+                  dl[0] += A_q[e] * (minv[e] * RF_q[e]);
+                  dl[1] += A_q[e] * (minv[e] * cur.r[e]);
+                }
+                xcd = wave64_quad_pair(dcd[0], dcd[1]);
+                xl = wave64_quad_pair(dl[0], dl[1]);
+                ycd = wave64_quad_pair(e_c, e_d);
+              };
+              // Everything that depends on the order, in the reference's order; `st` is the lane-parallel pass's result (QuadLeafStats /
+              // OctLeafStats), leaf i of it.  At the first divergence or U-turn nothing behind it is applied or drawn, its redo bit included.
+              auto leaf_apply = [&](const auto& st, const int i) {
+                pos_cur += v;
+                ck_c = pos_cur;
+                w_c = st.w(i);
+                if constexpr (LINW) redo = redo || st.redo(i);
+                sub_term = st.div(i);
+                numerical = numerical || sub_term;
+                sa_c = sa_c + st.sa(i);
+                na_c = na_c + 1;
+                const T dH_i = st.dH(i);
+                if (v > 0) { dh_c = maxabs(dh_c, dH_i); asm volatile(""); }
+                else { dh_c = maxabs(dH_i, dh_c); asm volatile(""); }
+              };
+              // combine(rng, sampler′, sampler′′) of a pending half (w_p, ck_p) with the half just completed (w_c, ck_c), as merge_level does it
+              auto merge_apply = [&](const T w_p, const int ck_p, const bool turn) {
+                T w_new;
+                if constexpr (LINW) w_new = w_p + w_c; else w_new = logaddexp(w_p, w_c);
+                bool keep_first;
+                if constexpr (LINW) keep_first = AHMC_UNI((T)ds.uniform() * w_new < w_p); else keep_first = AHMC_UNI(w_new < w_p + (T)ds.randexp());
+                if (keep_first) ck_c = ck_p;
+                w_c = w_new;
+                sub_term = turn;
+                AHMC_LP_COUNT(9, 1)
+              };
+              // the two leaves i0, i0 + 1 and their level-0 merge
+              auto pair_apply = [&](const auto& st, const int i0, const bool turn) {
+                leaf_apply(st, i0);
+                if (!sub_term) {
+                  const T w_p = w_c;
+                  const int ck_p = ck_c;
+                  leaf_apply(st, i0 + 1);
+                  if (!sub_term) merge_apply(w_p, ck_p, turn);
+                }
+              };
+              // the four leaves i0 .. i0 + 3: a, b, merge (a,b), c, d, merge (c,d), the level-1 merge
+              auto quad_apply = [&](const auto& st, const int i0, const bool turn_ab, const bool turn_cd, const bool turn_l1) {
+                pair_apply(st, i0, turn_ab);
+                if (!sub_term) {
+                  const T w_ab = w_c;
+                  const int ck_ab = ck_c;
+                  pair_apply(st, i0 + 2, turn_cd);
+                  if (!sub_term) merge_apply(w_ab, ck_ab, turn_l1);
+                }
+              };
+              T xab, xcd, xl, yab, ycd;
+              quad_vec(RF_c, A_c, xab, xcd, xl, yab, ycd);
+              // The octo step, and the quad step of the third doubling as its first half alone.  The first half's five pair registers go
+              // through the in-row exchanges now (wave64_oct_rows_de, wave64_oct_rows), so ONE register, r_a (RF_c) and ρ_abcd (A_c)
+              // cross the second half's leapfrogs.  The level-2 pending half is never parked inside an octo step: neither its two vector
+              // slots nor S_W(2) / S_CK(2) are touched.
+              const T h1 = wave64_oct_rows(wave64_oct_rows_de(xab, xcd, yab, ycd), xl, xl);
+              // (the third doubling: the second half's row is the first half's again — ONE body of reduction, pass and apply in the
+              // kernel instead of a quad's next to an octo's; the first half's slots hold wave64_quad_reduce_t's bits either way)
+              T h2 = h1;
+              if (nuts_oct_doubling(jw)) {
+                // r_a and ρ_abcd wait in the level-1 slots, the first in the slot order (LDS): no kernel with the quad step parks a level-1
+                // half there.  (In registers across the second half the cfg2 kernels need 24 / 16 B of scratch per lane.)
+                sl.store(LA(1), A_c);
+                sl.store(LRF(1), RF_c);
+                T RF_e[E], A_e[E];
+                quad_vec(RF_e, A_e, xab, xcd, xl, yab, ycd);
+                T z2 = wave64_oct_rows_de(xab, xcd, yab, ycd);
+                asm volatile("" : "+v"(z2));  // (made before the parked vectors come back: one register waits, not four)
+                sl.load(LA(1), A_c);
+                sl.load(LRF(1), RF_c);
+                T d2[2] = {0, 0};
+#pragma unroll
+                for (int e = 0; e < E; ++e) {  // merge_level(2, …): ρ = ρ_abcd + ρ_efgh, against r_a and r_h
+                  A_c[e] = A_c[e] + A_e[e];
+                  d2[0] += A_c[e] * (minv[e] * RF_c[e]);
+                  d2[1] += A_c[e] * (minv[e] * cur.r[e]);
+                }
+                h2 = wave64_oct_rows(z2, xl, wave64_quad_pair(d2[0], d2[1]));
+              }
+              // ONE reduction of the 22 numbers, ONE lane-parallel pass for the eight leaves' scalar work (ahmc_device.hpp:
+              // wave64_oct_reduce_t, oct_leaf_stats — the TWINs of the quad step's two), then a, b, m(ab), c, d, m(cd), m₁(abcd),
+              // e, f, m(ef), g, h, m(gh), m₁(efgh), m₂; the leapfrogs behind the first divergence or U-turn (at most seven) were speculative.
+              T w_t;
+              const unsigned turns = (unsigned)wave64_oct_reduce_t(h1, h2, w_t);  // (all seven decisions lie in lanes 0 .. 31)
+              OctLeafStats<T> os;
+              oct_leaf_stats<T, LINW>(w_t, H0, p.delta_max, sizeof(T) == 4 ? T(60) : T(LINW_LIMIT), os);
+              quad_apply(os, 0, (turns & (unsigned)OCT_TURN_AB) != 0u, (turns & (unsigned)OCT_TURN_CD) != 0u, (turns & (unsigned)OCT_TURN_ABCD) != 0u);
+              if (!sub_term && nuts_oct_doubling(jw)) {
+                const T w_abcd = w_c;
+                const int ck_abcd = ck_c;
+                quad_apply(os, 4, (turns & (unsigned)OCT_TURN_EF) != 0u, (turns & (unsigned)OCT_TURN_GH) != 0u, (turns & (unsigned)OCT_TURN_EFGH) != 0u);
+                if (!sub_term) merge_apply(w_abcd, ck_abcd, (turns & (unsigned)OCT_TURN_L2) != 0u);
+              }
+              } else {
+              // (the kernels without the octo step: the quad step as it was, statement for statement — these instantiations compile to the
+              // device code they had.  TWIN of the arm above in what a leaf and a merge apply: change both.)
               // Vector work first: nothing in the leapfrog of c or d needs an energy or a decision of a or b, and ρ of the level-1 merge is a
               // vector sum.  The level-1 pending half (ρ_ab, r_a, its weight and candidate) is never parked inside a quad: it stays in registers.
               const T es = v > 0 ? eps : -eps;
@@ -744,6 +909,7 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
                 const int ck_ab = ck_c;
                 pair_apply(1, (turns & QUAD_TURN_CD) != 0ull);
                 if (!sub_term) merge_apply(w_ab, ck_ab, (turns & QUAD_TURN_L1) != 0ull);
+              }
               }
             } else {   // the second doubling: the pair step
               // (a chain owns the wave: `alive` holds for the whole wave here, and every predicate below is wave-uniform)
@@ -1019,10 +1185,18 @@ __global__ __launch_bounds__((G > 256 ? G : 256), (E >= 16 ? 1 : (MODE == 2 ? (E
           bool m = AHMC_UNI(alive && !sub_term);
           if (AHMC_ANY(m)) {
             if (m && !pair) merge_level(0, cur.r, cur.r, std::bool_constant<FUSE_M0>{});  // (a pair step made its level-0 merge above)
+            if constexpr (OCT) {
+              for (int lvl = 1 + (jw > 1 ? 1 : 0) + (nuts_oct_doubling(jw) ? 1 : 0); lvl < nm; ++lvl) {  // (an octo step made its level-2 merge as well)
+                m = AHMC_UNI(alive && !sub_term);
+                if (!AHMC_ANY(m)) break;
+                if (m) merge_level(lvl, A_c, RF_c, std::false_type{});
+              }
+            } else {
             for (int lvl = 1 + (QUAD && jw > 1 ? 1 : 0); lvl < nm; ++lvl) {  // (a quad step made its level-1 merge as well)
               m = AHMC_UNI(alive && !sub_term);
               if (!AHMC_ANY(m)) break;
               if (m) merge_level(lvl, A_c, RF_c, std::false_type{});
+            }
             }
           }
         }
